@@ -2,7 +2,7 @@
 """Headline benchmark: contact-constraints x iterations / sec, LargePyramid base-200, TGS_Soft
 (8 sub-steps, relax on) -- BASELINE.json's metric on BASELINE.json's config (configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one s2Solve_TGS_Soft (the hot path of one s2World_Step) over the resident world: the
 pyramid's step-0 solver input (solver2d_amd.synthetic.pyramid == the reference's own captured
@@ -12,6 +12,9 @@ back round 3's form: the step-0 bodies copied back before every step).  Inputs a
 the timed region.
 `value` = C x solve_sweeps x K x N / wall seconds, with solve sweeps counted as executed
 (TGS_Soft 8/4: 16 per step, reference src/solve_tgs_soft.c:211-269).
+`--dump-outputs DIR`: right after the K timed steps, the resident world as a caller of the path would download it
+(s2amd_download: every field of the body and contact records, DIR/bodies_<field>.npy, DIR/contacts_points_<field>.npy, ...)
+in float32 (int32 fields in float64), 64 MB at most; the inputs are the same on every run with the same arguments.
 
 N > 1: one process per GPU (torch.distributed / RCCL), each rank owns one independent pyramid
 island (weak scaling); the only exchange is the per-step all-gather of per-island body poses.
@@ -71,6 +74,40 @@ PMC_DURATION_TOLERANCE = 0.03
 
 def pmc_same_build(pass_us, live_us):
     return live_us is None or (pass_us is not None and abs(pass_us - live_us) <= PMC_DURATION_TOLERANCE * live_us)
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 20240611
+
+
+def record_fields(prefix, records):
+    """{prefix_field: array} for every field of a wire-record array (nested fields flattened: contacts_points_normalImpulse);
+    float32 fields as they are, int32 fields as float64 (exact)"""
+    out = {}
+    for name in records.dtype.names:
+        col = records[name]
+        if col.dtype.names:
+            out.update(record_fields("%s_%s" % (prefix, name), col))
+        else:
+            out["%s_%s" % (prefix, name)] = col.astype(np.float32 if col.dtype.base == np.float32 else np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, DUMP_LIMIT_BYTES at most in all.  Above that, every array keeps the same fixed, seeded
+    sample of its rows (the chosen row numbers of the arrays with n rows: DIR/sampled_rows_of_<n>.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items() if v.size}
+    total = sum(v.nbytes for v in arrays.values())
+    row_counts = sorted(set(len(v) for v in arrays.values()))
+    keep = {}
+    if total > DUMP_LIMIT_BYTES:
+        frac = 0.99 * DUMP_LIMIT_BYTES / (total + 8 * sum(row_counts))
+        for n in row_counts:
+            keep[n] = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=max(1, int(n * frac)), replace=False))
+            np.save(os.path.join(directory, "sampled_rows_of_%d.npy" % n), keep[n].astype(np.float64))
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr[keep[len(arr)]] if keep else arr)
 
 
 def cpu_baseline(base, vel, pos, budget_s):
@@ -224,7 +261,7 @@ class Ranks:
         return float(t.item())
 
 
-def island_sharded_leg(ranks, islands, base, vel, pos, steps, warmup, graph=True, dump=None, weak=False):
+def island_sharded_leg(ranks, islands, base, vel, pos, steps, warmup, graph=True, dump=None, weak=False, dump_dir=None):
     """BASELINE.json configs[4]: ONE world of `islands` base-`base` pyramids, islands sharded over the ranks, every shard
     resident, one all-gather of pose records per step (ResidentShardedWorld).  Strong scaling.
     weak: `islands` pyramids PER RANK instead (a world of islands x N, every rank building and owning its own -- the partition an
@@ -247,6 +284,8 @@ def island_sharded_leg(ranks, islands, base, vel, pos, steps, warmup, graph=True
     elapsed = ranks.max_over_ranks(time.perf_counter() - t0)
     if dump and ranks.rank == 0:
         np.save(dump, rs.world_bodies())
+    if dump_dir and ranks.rank == 0:
+        dump_outputs(dump_dir, {"world_bodies": rs.world_bodies()})
     gpu.set_option("async", 0)
     gpu.step_resident(params)
     st = gpu.stats()
@@ -641,7 +680,12 @@ def main():
     ap.add_argument("--no-fast", action="store_true", help="skip the value_fast object (the headline loop on the tolerance-mode build)")
     ap.add_argument("--no-extras", action="store_true", help="only the headline line (no whole_step / configs / island_sharded objects)")
     ap.add_argument("--restore", action="store_true", help="copy the step-0 bodies back before every step (round 3's headline loop) instead of consecutive steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy: every field of the downloaded body and "
+                         "contact records (--config 5: the gathered body poses of the whole world)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.sharded_abi_devices:
         lists = [[int(d) for d in part.split(",")] for part in args.sharded_abi_devices.split(";") if part]
@@ -698,7 +742,7 @@ def main():
     if args.config == 5:
         # the island-sharded job as the line itself (strong scaling); the contract's keys, its own roofline
         line = island_sharded_leg(ranks, args.islands, args.island_base, args.vel_iters, args.pos_iters, args.steps, args.warmup,
-                                  graph=not args.no_graph, dump=os.environ.get("S2AMD_BENCH_DUMP"), weak=args.weak)
+                                  graph=not args.no_graph, dump=os.environ.get("S2AMD_BENCH_DUMP"), weak=args.weak, dump_dir=args.dump_outputs)
         line.update({"higher_is_better": True, "vs_baseline": None, "dtype": "f32", "data": "synthetic", "ranks_seen": ranks_seen, "devices": devices})
         if rank == 0:
             print(json.dumps(line))
@@ -781,6 +825,10 @@ def main():
     run(args.steps)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        got = tuple(a.copy() for a in pre)
+        gpu.download(*got)
+        dump_outputs(args.dump_outputs, dict(record_fields("bodies", got[0]), **record_fields("contacts", got[1]), **record_fields("joints", got[2])))
     gpu.set_option("async", 0)
     if args.restore:
         gpu.restore_bodies()

@@ -10,8 +10,10 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "shim", "_build", "libsolver2d_amd.so")
-DEMO = os.path.join(ROOT, "tools", "dropin_product_demo.bin")
+# built by shim/Makefile's recipe where the reference checkout is (`make -C oracle dropin`, part of build()); under oracle/_ref/
+# they travel with the compiled reference
+LIB = os.path.join(ROOT, "oracle", "_ref", "dropin", "libsolver2d_amd.so")
+DEMO = os.path.join(ROOT, "oracle", "_ref", "dropin", "dropin_product_demo.bin")
 HAVE_REF = os.path.exists("/root/reference/src/world.c")
 
 # include/solver2d/solver2d.h:22-70 ...
@@ -33,9 +35,9 @@ def built():
     if HAVE_REF:
         out = subprocess.run(["make", "-n", "-B", "-C", os.path.join(ROOT, "shim")], stdout=subprocess.PIPE, check=True).stdout.decode()
         assert "oracle" not in out and "tests/" not in out, "the product build must not need the test rig"
-        subprocess.check_call([os.path.join(ROOT, "tools", "dropin_product_demo.sh"), "build"])
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "dropin"])
     if not os.path.exists(LIB):
-        pytest.skip("shim/_build/libsolver2d_amd.so is built where the reference checkout is (make -C shim REF=...)")
+        pytest.skip("oracle/_ref/dropin/libsolver2d_amd.so is built where the reference checkout is (make -C oracle dropin)")
     return LIB
 
 
@@ -53,7 +55,10 @@ def test_the_patch_form_of_the_call_sites_applies_to_the_reference(tmp_path):
     if not HAVE_REF:
         pytest.skip("needs the reference checkout")
     for d in ("src", "include"):
-        shutil.copytree(os.path.join("/root/reference", d), str(tmp_path / d))
+        shutil.copytree(os.path.join("/root/reference", d), str(tmp_path / d), copy_function=shutil.copyfile)
+    # (a read-only checkout copies as read-only directories: patch and the copies below write beside its files)
+    for dirpath, _, _ in os.walk(str(tmp_path)):
+        os.chmod(dirpath, 0o755)
     patch = open(os.path.join(ROOT, "shim", "call_sites.patch"), encoding="latin-1").read()
     assert not [l for l in patch.splitlines() if l.startswith("-") and not l.startswith("---")], "the patch only adds lines"
     # a device error must never fall through to the reference's CPU solver on the same world: the patched call sites abort

@@ -56,6 +56,39 @@ def test_single_gpu_line():
     assert ch["steps_that_built_a_structure"] <= 10 and 0 < ch["churn_step_median_ms"] < 2.0, ch
 
 
+def test_dump_outputs_are_the_world_after_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: every field of the records a caller downloads after the timed steps, float32 / float64, 64 MB at most --
+    bit for bit the world that warmup + steps resident steps of the same input leave in a solver of this process."""
+    import numpy as np
+    import bench
+    from solver2d_amd import hip, synthetic, wire
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, "bench.py", "--base", "100", "--steps", "12", "--warmup", "3", "--no-cpu", "--no-fast", "--no-extras",
+                          "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = last_json(out.stdout)
+    assert d["steps"] == 12 and d["ms_per_step"] > 0
+    files = sorted(os.listdir(str(dump)))
+    assert sum(os.path.getsize(str(dump / f)) for f in files) <= 64 * 1000 * 1000
+    pre = synthetic.pyramid(100)
+    params = wire.StepParams.make("TGS_Soft", 1.0 / 60.0, 8, 4, True)
+    with hip.Solver(0) as s:
+        s.set_option("async", 1)
+        s.set_option("strip_patience", 0)
+        s.upload(*pre)
+        for _ in range(3 + 12):
+            s.step_resident(params)
+        s.synchronize()
+        got = tuple(a.copy() for a in pre)
+        s.download(*got)
+    want = dict(bench.record_fields("bodies", got[0]), **bench.record_fields("contacts", got[1]))
+    assert files == sorted(k + ".npy" for k in want), files
+    for name, arr in want.items():
+        saved = np.load(str(dump / (name + ".npy")))
+        assert saved.dtype in (np.float32, np.float64) and saved.dtype == arr.dtype and saved.shape == arr.shape, name
+        assert saved.tobytes() == arr.tobytes(), name
+
+
 def test_two_ranks_on_one_device():
     env = dict(os.environ, S2AMD_BENCH_BACKEND="gloo", S2AMD_BENCH_SINGLE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
