@@ -460,6 +460,15 @@ int s2amd_get_stats(s2amdSolver* solver, s2amdStepStats* stats);
  * body every sweep, else -1.  Either array may be NULL; capacity = entries each can hold (>= the body capacity of the world).
  * *stripCount = number of strips.  Tests use it to build contacts whose place in the structure they know. */
 int s2amd_get_strip_owners(s2amdSolver* solver, int32_t* ownerStrip, int32_t* onSeam, int32_t capacity, int32_t* stripCount);
+/* (additive, API 5) Which kernel swept the resident islands -- the LDS groups of small islands a soft solver keeps in registers for the
+ * whole step -- in the last step, and in which variant: *rounds = 6 or 8, the colour rounds per lane the variant holds (0 with kernel 0).
+ * Either pointer may be NULL.  Nothing about the results depends on it: tests use it to know which code they compared. */
+#define S2AMD_RESIDENT_NONE 0             /* the last step had no resident islands */
+#define S2AMD_RESIDENT_INTERPRETER 1      /* the group interpreter (group_kernel.hip), e.g. beside a persistent strip launch */
+#define S2AMD_RESIDENT_ISLAND 2           /* islandStepKernel (strip_kernel.hip): any soft kind; option "wide" = 0 */
+#define S2AMD_RESIDENT_WIDE 3             /* the 512-thread island kernel (wide_kernel.hip) between the body prologue and epilogue */
+#define S2AMD_RESIDENT_WIDE_ONLY_LAUNCH 4 /* ... as the step's only launch (a world of resident islands only) */
+int s2amd_get_resident_kernel(s2amdSolver* solver, int32_t* kernel, int32_t* rounds);
 /* Live timing of the dominant kernel on the solver's own stream: the first contact solve sweep of
  * the step plan (all its colour-batch launches) is enqueued `repeats` times back to back in one
  * hipGraph and bracketed by a HIP event pair; *usPerLaunch = elapsed / launches, i.e. the time one
@@ -473,7 +482,7 @@ int s2amd_measure_dominant(s2amdSolver* solver, const s2amdStepParams* params, i
  * "strips" (0/1 cut islands that fit no LDS group into strips of BFS levels: two launches per sweep), "strip_bodies" (target
  * bodies per strip, default 8 = strips of two BFS levels), "near_handoff" (0/1, default 1: hand-offs between workgroups the per-launch census finds on one XCD stay in its L2), "strip_retry" (0/1 rebuild the partition with other strip widths when the persistent kernel cannot take this one or it needs more than five interior colour rounds), "strip_min_bodies" (loose bodies below which the colour-batch path is kept), "strip_patience" (steps the constraint graph must
  * stay unchanged before the strip structure is built: its host build costs ~3 ms at 60k constraints, the colour-batch one ~1 ms), "async" (0/1, see s2amd_synchronize), "strip_lean" (0/1 dedicated strip
- * kernel for the soft sweeps), "persist" (0/1 whole step of the strips in one persistent launch), "wide" (0/1 TGS_Soft's persistent launch runs 512 threads per strip: wide_kernel.hip),
+ * kernel for the soft sweeps), "persist" (0/1 whole step of the strips in one persistent launch), "wide" (0/1 the persistent launch of TGS_Soft, SoftStep and PGS_Soft runs 512 threads per strip, and their resident islands run on the 512-thread island kernel: wide_kernel.hip; 0 = the 256-thread kernels of strip_kernel.hip),
  * "generic" (0/1 every other Gauss-Seidel solver, and any big island with joints, runs its whole step as one launch of the op interpreter over the
  * same strips: generic_kernel.hip; 0 = colour batches for them), "persist_retry" (steps a solver whose persistent launch lost a hand-off stays on the
  * fallback path before the one-launch kernels get another chance -- the wait doubles with every further time-out; default 256, 0 = for ever),
@@ -486,7 +495,9 @@ int s2amd_measure_dominant(s2amdSolver* solver, const s2amdStepParams* params, i
  * contacts are placed into the existing structure when they fit; 0 = every created contact rebuilds it), "defer" (0/1 a created
  * contact that cannot be placed and has no manifold points yet is only watched until it gets its first points; 0 = it rebuilds the
  * structure when it is created), "island_resident" (0/1 small islands under the soft contact solvers keep their constraints in
- * registers for the whole step: one read of every record per step).  None of them changes a result beyond the sweep order the
+ * registers for the whole step: one read of every record per step -- TGS_Soft, PGS_Soft and, up to six colour rounds, SoftStep on the
+ * 512-thread island kernel, which is the step's only launch in a world of such islands only; 0 = the group interpreter;
+ * s2amd_get_resident_kernel tells which one ran).  None of them changes a result beyond the sweep order the
  * library reports. */
 int s2amd_set_option(s2amdSolver* solver, const char* key, int32_t value);
 

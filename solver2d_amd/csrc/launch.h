@@ -174,10 +174,15 @@ struct WideSelf
 // (parked rounds, staged positions, the warm start's term table); -1: no variant takes the partition
 int wideExtraRecords(const PersistView& pv, int selfContained, int bodyWarm, int kind = SOFT_TGS);
 int wideBodyWarmVariant(const PersistView& pv);
-int wideIslandLocalRecords(int maxRounds); // LDS records the resident-island kernel's eight-round variant keeps local anchors in // the variant for this partition has the body-centric warm start
-// ... and the resident islands' step (strip_kernel.hip: launchIslandStep) for TGS_Soft with the current-anchor warm start
+// LDS records the resident-island kernel keeps per-lane anchors in beside the bodies: the local anchors of TGS_Soft's eight-round variant, the
+// arms rA0 / rB0 of seven records of PGS_Soft's eight-round and of all six of SoftStep's (six-round) variant
+int wideIslandLocalRecords(int maxRounds, int kind = SOFT_TGS);
+// does the resident-island kernel exist for this kind with this many colour rounds?  (SoftStep: up to S2_STRIP_ROUNDS only)
+int wideIslandForm(int kind, int maxRounds);
+// ... and the resident islands' step (strip_kernel.hip: launchIslandStep) for TGS_Soft and PGS_Soft with the current-anchor warm start
+// (kind SOFT_TGS / SOFT_PGS) and for SoftStep with the fixed-anchor one (SOFT_FIXED)
 // selfContained: the kernel also stages its bodies from the wire records and writes them back (no prologue / epilogue launch)
-void launchWideIsland(hipStream_t s, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops, int opCount,
+void launchWideIsland(hipStream_t s, int kind, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops, int opCount,
 					  int maxRounds, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const StepConsts& sc, float unpackH,
 					  int selfContained, const unsigned int* stepFailed, int allTwoPoints);
 // self != nullptr: the self-contained variant (the step is this one launch); pv.bodyWarm: the body-centric warm start

@@ -631,6 +631,25 @@ int s2amd_get_joint_order(s2amdSolver* s, int32_t* order, int32_t orderCapacity,
 	return copyOrder(s->joints.order, s->joints.colorOffsets, order, orderCapacity, colorOffsets, colorCapacity, jointCount, colorCount);
 }
 
+int s2amd_get_resident_kernel(s2amdSolver* s, int32_t* kernel, int32_t* rounds)
+{
+	if (!s)
+	{
+		return fail(S2AMD_E_INVALID, "null solver");
+	}
+	// (recorded where the step's launches are enqueued -- Executor::runResidentGroups --: a replayed step graph holds the launch it recorded)
+	const int k = s->dResident.view.groupCount > 0 ? s->residentKernel : S2AMD_RESIDENT_NONE;
+	if (kernel)
+	{
+		*kernel = k;
+	}
+	if (rounds)
+	{
+		*rounds = k != S2AMD_RESIDENT_NONE ? s->residentKernelRounds : 0;
+	}
+	return S2AMD_OK;
+}
+
 int s2amd_get_strip_owners(s2amdSolver* s, int32_t* ownerStrip, int32_t* onSeam, int32_t capacity, int32_t* stripCount)
 {
 	if (!s)

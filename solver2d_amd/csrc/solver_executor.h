@@ -549,12 +549,20 @@ struct Executor
 
 	// the groups that were laid out for the resident-island kernel: on it when the plan allows, else through the generic
 	// group interpreter (the table is an ordinary group table too)
-	// the resident islands on wide_kernel.hip: wideIslandKernel (TGS_Soft with the current-anchor warm start)
+	// the resident islands on wide_kernel.hip: wideIslandKernel (TGS_Soft with the current-anchor warm start) and wideIslandKernelOf
+	// (PGS_Soft with the current-anchor, SoftStep with the fixed-anchor warm start) -- where the kernel has a form for the groups' colour
+	// rounds (SoftStep: up to six) and the LDS of THAT form fits beside the bodies (SoftStep: six records' arms, 96 KB); else islandStepKernel
 	bool wideIslandPlan() const
 	{
 		int kind, warm;
-		return residentPlan(kind, warm) && s->optWide && kind == SOFT_TGS && warm == WARM_CURRENT &&
-			   s->residentView.ldsRecords + 2 + wideIslandLocalRecords(s->residentRounds) + 2 * s->residentOpCount <= (160 * 1024) / 16;
+		if (!residentPlan(kind, warm) || !s->optWide)
+		{
+			return false;
+		}
+		const bool current = (kind == SOFT_TGS || kind == SOFT_PGS) && warm == WARM_CURRENT;
+		const bool fixed = kind == SOFT_FIXED && warm == WARM_FIXED; // s2Solve_SoftStep: s2WarmStartContacts_Fixed
+		return (current || fixed) && wideIslandForm(kind, s->residentRounds) != 0 &&
+			   s->residentView.ldsRecords + 2 + wideIslandLocalRecords(s->residentRounds, kind) + 2 * s->residentOpCount <= (160 * 1024) / 16;
 	}
 
 	// ... and nothing else in the world: every body is owned by a resident island, every constraint is one of theirs, no joints, and
@@ -571,8 +579,11 @@ struct Executor
 	{
 		if (s->dResident.view.groupCount <= 0)
 		{
+			s->residentKernel = S2AMD_RESIDENT_NONE;
 			return;
 		}
+		// (s2amd_get_resident_kernel)
+		s->residentKernelRounds = s->residentRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX;
 		const unsigned int* stepFailed = nullptr; // (see residentPlan: these kernels never share a step with a launch that can fail)
 		int kind, warm;
 		if (residentPlan(kind, warm))
@@ -585,18 +596,21 @@ struct Executor
 			// (the LDS budget of the resident groups leaves room for the two coefficient records: buildResidentTables)
 			if (wideIslandPlan())
 			{
-				launchWideIsland(st, s->cv, s->bv, s->residentView, coef, (const Op*)s->dResidentOps.p, s->residentOpCount, s->residentRounds, wireContacts(),
+				s->residentKernel = selfContained ? S2AMD_RESIDENT_WIDE_ONLY_LAUNCH : S2AMD_RESIDENT_WIDE;
+				launchWideIsland(st, kind, s->cv, s->bv, s->residentView, coef, (const Op*)s->dResidentOps.p, s->residentOpCount, s->residentRounds, wireContacts(),
 								 wireBodies(), (const uint32_t*)s->dBodyFlags.p, p.sc.warmStart, p.sc, p.unpackH, selfContained ? 1 : 0, stepFailed,
 								 (s->residentAllTwoPoints && s->pointsKnown) ? 1 : 0); // (manifolds recomputed on the device: any point count)
 			}
 			else
 			{
+				s->residentKernel = S2AMD_RESIDENT_ISLAND;
 				launchIslandStep(st, kind, warm, s->cv, s->bv, s->residentView, coef, (const Op*)s->dResidentOps.p, s->residentOpCount, s->residentRounds,
 								 wireContacts(), wireBodies(), (const uint32_t*)s->dBodyFlags.p, p.sc.warmStart, stepFailed);
 			}
 		}
 		else
 		{
+			s->residentKernel = S2AMD_RESIDENT_INTERPRETER;
 			launchGroupKernel(st, s->cv, s->jv, s->bv, s->dResident.view, deviceOps(), (int)p.ops.size(), p.sc, wireContacts(), s->dResident.maxBodies,
 							  p.usesDq0 ? 1 : 0);
 		}

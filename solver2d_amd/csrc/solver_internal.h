@@ -388,6 +388,7 @@ struct SolverStructure
 	DevBuf dResidentDesc, dResidentOps;
 	StripTableView residentView{};
 	int residentRounds = 0;
+	int residentKernel = 0, residentKernelRounds = 0; // s2amd_get_resident_kernel: what Executor::runResidentGroups launched last
 	int residentK0 = 0, residentK1 = 0; // their range in contacts.order
 	bool residentRejected = false; // some group's colouring needs more rounds than the kernel holds: plain LDS groups for this graph
 	uint64_t residentOpsGeneration = ~0ull;

@@ -531,7 +531,9 @@ S2_DEV WideRegs unparkWide(const float4* slot, int stride)
 	return p;
 }
 
-S2_DEV WideRegs wideFromSoft(const SoftRegs<SOFT_TGS>& t)
+// (SOFT_PGS: lA / lB hold perp(rA0) / perp(rB0) and p0 the plain separation, as loadWide<SOFT_PGS> leaves them; SOFT_FIXED: the local
+// anchors and the adjusted separation as for SOFT_TGS -- its arms rA0 / rB0 go to LDS: wideArmsOf)
+template <int KIND> S2_DEV WideRegs wideFromSoft(const SoftRegs<KIND>& t)
 {
 	WideRegs p;
 	p.idx = (uint32_t)t.h.ia | ((uint32_t)t.h.ib << 13) | (((uint32_t)t.h.pointCount & 3u) << 26) | (t.h.writeA ? 1u << 28 : 0u) | (t.h.writeB ? 1u << 29 : 0u);
@@ -539,12 +541,23 @@ S2_DEV WideRegs wideFromSoft(const SoftRegs<SOFT_TGS>& t)
 #pragma unroll
 	for (int j = 0; j < 2; ++j)
 	{
-		p.lA[j] = lo2(t.an[j]), p.lB[j] = hi2(t.an[j]);
-		p.p0[j] = t.par[j].x, p.p1[j] = t.par[j].y, p.p2[j] = t.par[j].z;
+		if constexpr (KIND == SOFT_PGS)
+		{
+			p.lA[j] = f2{-t.r0[j].y, t.r0[j].x}, p.lB[j] = f2{-t.r0[j].w, t.r0[j].z};
+			p.p0[j] = t.par[j].w;
+		}
+		else
+		{
+			p.lA[j] = lo2(t.an[j]), p.lB[j] = hi2(t.an[j]);
+			p.p0[j] = t.par[j].x;
+		}
+		p.p1[j] = t.par[j].y, p.p2[j] = t.par[j].z;
 		p.imp[j] = f2{t.imp[j].x, t.imp[j].y};
 	}
 	return p;
 }
+// {perp(rA0), perp(rB0)} of a manifold point: the record warmWide / prepWide read of the arms that wait in LDS (wideLdsArms)
+S2_DEV float4 wideArmsOf(float4 r0) { return make_float4(-r0.y, r0.x, -r0.w, r0.z); }
 
 // MODE bits
 #define S2_WIDE_SELF 1 // the kernel is the step's prologue and epilogue too (Executor::selfContainedStrips): ONE launch per step
@@ -2280,306 +2293,58 @@ void launchWideStep(hipStream_t s, int kind, const ContactView& c, const BodyVie
 // (the eight-round variant keeps the local anchors of its last six records in LDS -- wideStepKernel: wideLocalsInLds --: eight
 // 22-dword records spilled 140-172 bytes per lane)
 constexpr int wideIslandLocalsInLds(int ROUNDS) { return ROUNDS > S2_STRIP_ROUNDS ? 6 : 0; }
-int wideIslandLocalRecords(int maxRounds) { return 2 * wideIslandLocalsInLds(maxRounds > S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS_MAX : S2_STRIP_ROUNDS) * S2_WIDE_THREADS; }
+// KIND: the same kernel for the two sibling soft solvers (strip_kernel.hip: islandStepKernel<KIND, WARM> is the general form of each).
+//   SOFT_PGS   (s2Solve_PGS_Soft, current-anchor warm start) needs nothing but the arms rA0 / rB0 and the plain separation: the record has
+//              the TGS size, the six-round variant no LDS extras; the eight-round variant keeps the arms of its last SEVEN records in LDS
+//              (S2_WIDE_PGS_ARMS) where the TGS one keeps six records' local anchors: with six, its two forms between the body launches
+//              spilled 1-2 VGPRs (8-12 bytes of scratch per lane; make resources).
+//   SOFT_FIXED (s2Solve_SoftStep, s2WarmStartContacts_Fixed) needs the local anchors (the separation as the bodies stand now) AND the arms
+//              (warm start, impulses): 30 dwords.  The arms of ALL six records wait in LDS ({perp(rA0), perp(rB0)} per point and lane, as
+//              wideStepKernel's larms), the local anchors stay in the record.  There is no eight-round variant: with eight records' arms
+//              in LDS (128 KB) the local anchors of eight records in registers are the 22-dword x 8 case that spilled for TGS, and both
+//              in LDS do not fit beside the bodies -- such a world stays on islandStepKernel (wideIslandForm).
+constexpr int wideIslandArmsInLds(int KIND, int ROUNDS) { return KIND == SOFT_FIXED ? ROUNDS : (KIND == SOFT_PGS && ROUNDS > S2_STRIP_ROUNDS ? 7 : 0); }
+int wideIslandForm(int kind, int maxRounds) { return (kind == SOFT_TGS || kind == SOFT_PGS || (kind == SOFT_FIXED && maxRounds <= S2_STRIP_ROUNDS)) ? 1 : 0; }
+int wideIslandLocalRecords(int maxRounds, int kind)
+{
+	const int rounds = maxRounds > S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS_MAX : S2_STRIP_ROUNDS;
+	return 2 * (kind == SOFT_TGS ? wideIslandLocalsInLds(rounds) : wideIslandArmsInLds(kind, rounds)) * S2_WIDE_THREADS;
+}
 
 template <int ROUNDS, bool SELF, int POINTS>
 __global__ __launch_bounds__(S2_WIDE_THREADS) void wideIslandKernel(ContactView c, BodyView g, StripTableView ta, float4 softCoef0, float4 softCoef1, const Op* ops,
 																	 int opCount, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart,
 																	 StepConsts sc, float unpackH, const unsigned int* stepFailed)
 {
-	extern __shared__ __attribute__((aligned(16))) float4 lds[];
-	if (stepFailed != nullptr && *stepFailed != 0u)
-	{
-		return; // a persistent strip kernel of this step lost a hand-off: the step will be repeated, nothing of it may reach the wire arrays
-	}
-	const int tid = (int)threadIdx.x;
-	const StripDesc* da = ta.descs + blockIdx.x;
-	const int bodyBase = da->bodyBase, nb = da->bodyCount, roundsA = da->batchCount;
-	int2 batchA[ROUNDS];
-#pragma unroll
-	for (int i = 0; i < ROUNDS; ++i)
-	{
-		batchA[i] = make_int2(da->batch[i].x, da->batch[i].y);
-	}
-	float4* lvel = lds;
-	float4* ldq = lds + nb;
-	float4* linteg = lds + 2 * nb;
-	float* langDamp = (float*)(lds + 3 * nb);
-	float2* lmass = (float2*)(lds + 3 * nb + (nb + 3) / 4);
-	float2* llc = (float2*)(lds + 3 * nb + (nb + 3) / 4 + (nb + 1) / 2); // the bodies' local centres (soft_from_wire.h: prepareSoftFromWire)
-	const int bodyRecords = 3 * nb + (nb + 3) / 4 + 2 * ((nb + 1) / 2);
-	Op* lops = (Op*)(lds + bodyRecords);
-	float4* lcoef = lds + bodyRecords + 2 * opCount; // 2 records (the launch adds them to the size)
-	constexpr int LA = wideIslandLocalsInLds(ROUNDS), LL0 = ROUNDS - LA;
-	float4* llocals = lcoef + 2 + tid; // [record - LL0][point][lane] {lA, lB}
-	auto localsOf = [&](int r) { return llocals + 2 * (r - LL0 > 0 ? r - LL0 : 0) * S2_WIDE_THREADS; };
-
-	uint32_t id[S2_STRIP_BODY_CHUNKS];
-#pragma unroll
-	for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
-	{
-		const int i = tid + ch * S2_WIDE_THREADS;
-		id[ch] = i < nb ? (uint32_t)ta.bodyIds[bodyBase + i] : 0u;
-	}
-	for (int i = tid; i < opCount * 8; i += S2_WIDE_THREADS)
-	{
-		((int*)lops)[i] = ((const int*)ops)[i];
-	}
-	if (tid < 2)
-	{
-		lcoef[tid] = tid ? softCoef1 : softCoef0;
-	}
-	auto kOfRound = [&](int i) {
-		const int k = batchA[i].x + tid;
-		return (i < roundsA && k < batchA[i].y) ? k : -1;
-	};
-	// this thread's constraints: pool slot and group-local body slots (the wire records follow once the bodies are staged)
-	int slotOf[ROUNDS];
-	int2 localOf[ROUNDS];
-#pragma unroll
-	for (int i = 0; i < ROUNDS; ++i)
-	{
-		slotOf[i] = -1;
-		localOf[i] = make_int2(0, 0);
-		if (kOfRound(i) >= 0)
-		{
-			slotOf[i] = c.contactIndex[kOfRound(i)];
-			localOf[i] = c.localBodies[kOfRound(i)];
-		}
-	}
-	uint32_t flags[S2_STRIP_BODY_CHUNKS];
-	float2 pos[S2_STRIP_BODY_CHUNKS]; // SELF: the positions of the bodies this lane stages (s2FinalizePositions adds to them)
-#pragma unroll
-	for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
-	{
-		const int i = tid + ch * S2_WIDE_THREADS;
-		flags[ch] = 0u;
-		pos[ch] = make_float2(0.0f, 0.0f);
-		if (i < nb)
-		{
-			const int gi = (int)(id[ch] & ~S2G_OWNED);
-			if constexpr (SELF)
-			{
-				// body_ops.h: unpackBodyOne, into LDS instead of the SoA arrays
-				const s2amdBody* w = wireBodies + gi;
-				const int type = w->type;
-				uint32_t f = 0x80000000u;
-				if (type != S2AMD_BODY_FREE)
-				{
-					f |= S2F_LIVE | (type == S2AMD_BODY_DYNAMIC ? S2F_DYNAMIC : 0u) | (type != S2AMD_BODY_STATIC ? S2F_MOVES : 0u);
-				}
-				flags[ch] = f;
-				lvel[i] = make_float4(w->linearVelocity[0], w->linearVelocity[1], w->angularVelocity, 0.0f);
-				ldq[i] = make_float4(w->deltaPosition[0], w->deltaPosition[1], w->rot[0], w->rot[1]);
-				pos[ch] = make_float2(w->position[0], w->position[1]);
-				lmass[i] = make_float2(w->invMass, w->invI);
-				llc[i] = make_float2(w->localCenter[0], w->localCenter[1]);
-				const V2 gravity = v2(sc.gravityX, sc.gravityY);
-				const V2 force = v2(w->force[0], w->force[1]);
-				const V2 inner = mulAdd(force, w->mass * w->gravityScale, gravity);
-				const V2 a = mulSV(unpackH * w->invMass, inner);
-				const float aw = unpackH * w->invI * w->torque;
-				const float ld = 1.0f / (1.0f + unpackH * w->linearDamping);
-				const float ad = 1.0f / (1.0f + unpackH * w->angularDamping);
-				linteg[i] = make_float4(a.x, a.y, aw, ld);
-				langDamp[i] = ad;
-			}
-			else
-			{
-				lvel[i] = g.vel[gi];
-				ldq[i] = g.dq[gi];
-				flags[ch] = g.flags[gi] | 0x80000000u;
-				linteg[i] = g.integ[gi];
-				langDamp[i] = g.angDamp[gi];
-				lmass[i] = g.massInv[gi];
-				llc[i] = make_float2(wireBodies[gi].localCenter[0], wireBodies[gi].localCenter[1]);
-			}
-		}
-	}
-	__syncthreads();
-
-	LdsBodies lb{lvel, ldq};
-	WideRegs rA[ROUNDS];
-#pragma unroll
-	for (int i = 0; i < ROUNDS; ++i)
-	{
-		if (slotOf[i] >= 0)
-		{
-			rA[i] = wideFromSoft(prepareSoftFromWire<SOFT_TGS>(wire + slotOf[i], wireBodies, hostFlags, lb, lmass, localOf[i], g.capacity, warmStart, llc));
-			const bool st = lmass[localOf[i].x].x == 0.0f || lmass[localOf[i].y].x == 0.0f; // the doubled contact hertz of a static side
-			rA[i].idx |= st ? 1u << 30 : 0u;
-			if (i >= LL0)
-			{
-#pragma unroll
-				for (int j = 0; j < 2; ++j)
-				{
-					localsOf(i)[j * S2_WIDE_THREADS] = make_float4(rA[i].lA[j].x, rA[i].lA[j].y, rA[i].lB[j].x, rA[i].lB[j].y);
-				}
-			}
-		}
-	}
-	for (int oi = 0; oi < opCount; ++oi)
-	{
-		const Op op = lops[oi];
-		uint32_t salt;
-		asm volatile("s_mov_b32 %0, 0" : "=s"(salt));
-		if (op.code == OP_INTEGRATE_VEL)
-		{
-#pragma unroll
-			for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
-			{
-				if ((flags[ch] & S2F_DYNAMIC) != 0)
-				{
-					const int i = tid + ch * S2_WIDE_THREADS;
-					float4 v = lvel[i], k = linteg[i];
-					V2 lv = add(v2(v.x, v.y), v2(k.x, k.y));
-					float w = v.z + k.z;
-					lv = mulSV(k.w, lv);
-					w *= langDamp[i];
-					lvel[i] = make_float4(lv.x, lv.y, w, 0.0f);
-				}
-			}
-			__syncthreads();
-		}
-		else if (op.code == OP_INTEGRATE_POS)
-		{
-#pragma unroll
-			for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
-			{
-				if ((flags[ch] & S2F_MOVES) != 0)
-				{
-					const int i = tid + ch * S2_WIDE_THREADS;
-					float4 v = lvel[i], d = ldq[i];
-					V2 dpos = mulAdd(v2(d.x, d.y), op.h, v2(v.x, v.y));
-					Rot q;
-					q.s = d.z, q.c = d.w;
-					q = integrateRot(q, op.h * v.z);
-					ldq[i] = make_float4(dpos.x, dpos.y, q.s, q.c);
-				}
-			}
-			__syncthreads();
-		}
-		else if (op.code == OP_FINALIZE)
-		{
-#pragma unroll
-			for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
-			{
-				if constexpr (SELF)
-				{
-					// s2FinalizePositions (solve_common.c:70-91; body_ops.h: finalizePositionsOne) on the lane's own copy of the position
-					if ((flags[ch] & (op.flag ? S2F_DYNAMIC : S2F_MOVES)) != 0)
-					{
-						const int i = tid + ch * S2_WIDE_THREADS;
-						const float4 d = ldq[i];
-						const V2 np = add(v2(pos[ch].x, pos[ch].y), v2(d.x, d.y));
-						pos[ch] = make_float2(np.x, np.y);
-						ldq[i] = make_float4(0.0f, 0.0f, d.z, d.w);
-					}
-				}
-				else if (flags[ch] != 0u)
-				{
-					finalizePositionsOne(lb, tid + ch * S2_WIDE_THREADS, g, (int)(id[ch] & ~S2G_OWNED), op.flag, (id[ch] & S2G_OWNED) != 0);
-				}
-			}
-			__syncthreads();
-		}
-		else if (op.code == OP_WARM)
-		{
-#pragma unroll
-			for (int i = 0; i < ROUNDS; ++i)
-			{
-				if (i < roundsA)
-				{
-					if (kOfRound(i) >= 0)
-					{
-						if (i >= LL0)
-						{
-							warmWide<SOFT_TGS, POINTS, true>(rA[i], lvel, ldq, lmass, salt, nullptr, localsOf(i));
-						}
-						else
-						{
-							warmWide<SOFT_TGS, POINTS>(rA[i], lvel, ldq, lmass, salt);
-						}
-					}
-					__syncthreads();
-				}
-			}
-		}
-		else if (op.code == OP_SOLVE_SOFT)
-		{
-#pragma unroll
-			for (int i = 0; i < ROUNDS; ++i)
-			{
-				if (i < roundsA)
-				{
-					if (kOfRound(i) >= 0)
-					{
-						const WidePrep pre = (i >= LL0) ? prepWide<SOFT_TGS, POINTS, true>(rA[i], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(i))
-													  : prepWide<SOFT_TGS, POINTS>(rA[i], ldq, lcoef, op.inv_h, op.useBias, salt);
-						chainWide<POINTS>(rA[i], pre, lvel, lmass, lcoef, salt);
-					}
-					__syncthreads();
-				}
-			}
-		}
-	}
-#pragma unroll
-	for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
-	{
-		const int i = tid + ch * S2_WIDE_THREADS;
-		if (i < nb && (id[ch] & S2G_OWNED) != 0)
-		{
-			const int gi = (int)(id[ch] & ~S2G_OWNED);
-			if constexpr (SELF)
-			{
-				if ((flags[ch] & S2F_LIVE) != 0) // body_ops.h: packBodyOne
-				{
-					s2amdBody* w = wireBodies + gi;
-					const float4 v = lvel[i], d = ldq[i];
-					w->position[0] = pos[ch].x, w->position[1] = pos[ch].y;
-					w->rot[0] = d.z, w->rot[1] = d.w;
-					w->linearVelocity[0] = v.x, w->linearVelocity[1] = v.y;
-					w->angularVelocity = v.z;
-					w->deltaPosition[0] = d.x, w->deltaPosition[1] = d.y;
-				}
-			}
-			else
-			{
-				g.vel[gi] = lvel[i];
-				g.dq[gi] = ldq[i];
-			}
-		}
-	}
-	// s2StoreContactImpulses (solve_common.c:396-410): straight into the manifolds
-#pragma unroll
-	for (int i = 0; i < ROUNDS; ++i)
-	{
-		if (slotOf[i] >= 0)
-		{
-			const int pointCount = (int)((rA[i].idx >> 26) & 3u);
-			s2amdContact* contact = wire + slotOf[i];
-#pragma unroll
-			for (int j = 0; j < 2; ++j)
-			{
-				if (j < pointCount)
-				{
-					contact->points[j].normalImpulse = rA[i].imp[j].x;
-					contact->points[j].tangentImpulse = rA[i].imp[j].y;
-				}
-			}
-		}
-	}
+	constexpr int KIND = SOFT_TGS;
+#include "wide_island_body.h"
+}
+// ... for s2Solve_SoftStep (KIND = SOFT_FIXED: six rounds) and s2Solve_PGS_Soft (SOFT_PGS: six and eight)
+template <int KIND, int ROUNDS, bool SELF, int POINTS>
+__global__ __launch_bounds__(S2_WIDE_THREADS) void wideIslandKernelOf(ContactView c, BodyView g, StripTableView ta, float4 softCoef0, float4 softCoef1, const Op* ops,
+																		 int opCount, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart,
+																		 StepConsts sc, float unpackH, const unsigned int* stepFailed)
+{
+#include "wide_island_body.h"
 }
 
 // t.ldsRecords: body records of the largest group; maxRounds: colour rounds of the group with the most
-template <int ROUNDS>
+template <int KIND, int ROUNDS>
 static void launchWideIslandRounds(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef,
 								   const Op* ops, int opCount, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const StepConsts& sc,
 								   float unpackH, int selfContained, const unsigned int* stepFailed, int allTwoPoints)
 {
-#define S2_LAUNCH_ISLAND(SELF, POINTS)                                                                                                                        \
-	wideIslandKernel<ROUNDS, SELF, POINTS>                                                                                                                    \
-		<<<grid, dim3(S2_WIDE_THREADS), lds, s>>>(c, g, t, softCoef[0], softCoef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed)
+#define S2_LAUNCH_ISLAND(SELF, POINTS)                                                                                                                             \
+	if constexpr (KIND == SOFT_TGS)                                                                                                                                \
+	{                                                                                                                                                              \
+		wideIslandKernel<ROUNDS, SELF, POINTS>                                                                                                                     \
+			<<<grid, dim3(S2_WIDE_THREADS), lds, s>>>(c, g, t, softCoef[0], softCoef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed); \
+	}                                                                                                                                                              \
+	else                                                                                                                                                           \
+	{                                                                                                                                                              \
+		wideIslandKernelOf<KIND, ROUNDS, SELF, POINTS>                                                                                                           \
+			<<<grid, dim3(S2_WIDE_THREADS), lds, s>>>(c, g, t, softCoef[0], softCoef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed); \
+	}
 	if (selfContained)
 	{
 		if (allTwoPoints)
@@ -2602,28 +2367,56 @@ static void launchWideIslandRounds(hipStream_t s, dim3 grid, size_t lds, const C
 #undef S2_LAUNCH_ISLAND
 }
 
-void launchWideIsland(hipStream_t s, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops, int opCount,
+// kind: SOFT_TGS, SOFT_PGS or SOFT_FIXED, in a form that exists (wideIslandForm: Executor::wideIslandPlan has asked)
+void launchWideIsland(hipStream_t s, int kind, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops, int opCount,
 					  int maxRounds, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const StepConsts& sc, float unpackH,
 					  int selfContained, const unsigned int* stepFailed, int allTwoPoints)
 {
 	const dim3 grid((unsigned)t.groupCount);
-	const size_t lds = (size_t)(t.ldsRecords + 2 + wideIslandLocalRecords(maxRounds)) * sizeof(float4) + (size_t)opCount * sizeof(Op);
-	if (maxRounds <= S2_STRIP_ROUNDS)
+	const size_t lds = (size_t)(t.ldsRecords + 2 + wideIslandLocalRecords(maxRounds, kind)) * sizeof(float4) + (size_t)opCount * sizeof(Op);
+#define S2_ISLAND_ROUNDS(KIND, ROUNDS) \
+	launchWideIslandRounds<KIND, ROUNDS>(s, grid, lds, c, g, t, softCoef, ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, selfContained, stepFailed, allTwoPoints)
+	if (kind == SOFT_FIXED)
 	{
-		launchWideIslandRounds<S2_STRIP_ROUNDS>(s, grid, lds, c, g, t, softCoef, ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, selfContained, stepFailed, allTwoPoints);
+		if (maxRounds <= S2_STRIP_ROUNDS)
+		{
+			S2_ISLAND_ROUNDS(SOFT_FIXED, S2_STRIP_ROUNDS);
+		}
+	}
+	else if (kind == SOFT_PGS)
+	{
+		if (maxRounds <= S2_STRIP_ROUNDS)
+		{
+			S2_ISLAND_ROUNDS(SOFT_PGS, S2_STRIP_ROUNDS);
+		}
+		else
+		{
+			S2_ISLAND_ROUNDS(SOFT_PGS, S2_STRIP_ROUNDS_MAX);
+		}
+	}
+	else if (maxRounds <= S2_STRIP_ROUNDS)
+	{
+		S2_ISLAND_ROUNDS(SOFT_TGS, S2_STRIP_ROUNDS);
 	}
 	else
 	{
-		launchWideIslandRounds<S2_STRIP_ROUNDS_MAX>(s, grid, lds, c, g, t, softCoef, ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, selfContained, stepFailed, allTwoPoints);
+		S2_ISLAND_ROUNDS(SOFT_TGS, S2_STRIP_ROUNDS_MAX);
 	}
+#undef S2_ISLAND_ROUNDS
 }
 
 int wideKernelSetup()
 {
+#define S2_ISLAND_FORMS(KIND, ROUNDS)                                                                                                   \
+	(const void*)wideIslandKernelOf<KIND, ROUNDS, false, 0>, (const void*)wideIslandKernelOf<KIND, ROUNDS, true, 0>,                 \
+		(const void*)wideIslandKernelOf<KIND, ROUNDS, false, 2>, (const void*)wideIslandKernelOf<KIND, ROUNDS, true, 2>
 	for (const void* f : {(const void*)wideIslandKernel<S2_STRIP_ROUNDS, false, 0>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, false, 0>,
 						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, true, 0>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, true, 0>,
 						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, false, 2>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, false, 2>,
-						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, true, 2>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, true, 2>})
+						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, true, 2>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, true, 2>,
+						  // every form of the other two kinds the launch can pick (launchWideIsland)
+						  S2_ISLAND_FORMS(SOFT_FIXED, S2_STRIP_ROUNDS), S2_ISLAND_FORMS(SOFT_PGS, S2_STRIP_ROUNDS), S2_ISLAND_FORMS(SOFT_PGS, S2_STRIP_ROUNDS_MAX)})
+#undef S2_ISLAND_FORMS
 	{
 		if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
 		{

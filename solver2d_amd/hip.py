@@ -25,7 +25,7 @@ EXPORTS = [
     "s2amd_set_option", "s2amd_export_poses", "s2amd_export_poses_async", "s2amd_export_bodies_async", "s2amd_export_wait", "s2amd_measure_dominant", "s2amd_refit_shapes", "s2amd_find_pairs", "s2amd_synchronize", "s2amd_update_contacts", "s2amd_find_islands", "s2amd_color_constraints",
     "s2amd_world_upload", "s2amd_world_step", "s2amd_world_download", "s2amd_world_find_pairs", "s2amd_world_set_contacts",
     "s2amd_device_alloc", "s2amd_device_free", "s2amd_device_read", "s2amd_world_separated", "s2amd_world_download_boxes", "s2amd_world_set_refit_order", "s2amd_world_download_step", "s2amd_world_set_tree", "s2amd_world_get_tree",
-    "s2amd_get_strip_owners",
+    "s2amd_get_strip_owners", "s2amd_get_resident_kernel",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
     "s2amd_sharded_step_async", "s2amd_sharded_wait", "s2amd_sharded_get_step_ops", "s2amd_sharded_count_ops",
@@ -67,6 +67,7 @@ def load(fast=False):
     L.s2amd_get_joint_order.argtypes = [vp, vp, i32, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.s2amd_get_writable_bodies.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_get_strip_owners.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_get_resident_kernel.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.s2amd_get_stats.argtypes = [vp, ctypes.POINTER(wire.StepStats)]
     L.s2amd_set_option.argtypes = [vp, ctypes.c_char_p, i32]
     L.s2amd_export_poses.argtypes = [vp, vp, i32]
@@ -419,6 +420,12 @@ class Solver:
         n = ctypes.c_int32()
         self._ck(self._L.s2amd_get_strip_owners(self._h, owner.ctypes.data, seam.ctypes.data, len(owner), ctypes.byref(n)))
         return owner[:body_capacity], seam[:body_capacity], n.value
+
+    def resident_kernel(self):
+        """(kernel, rounds) of the resident islands in the last step; see s2amd_get_resident_kernel."""
+        kernel, rounds = ctypes.c_int32(), ctypes.c_int32()
+        self._ck(self._L.s2amd_get_resident_kernel(self._h, ctypes.byref(kernel), ctypes.byref(rounds)))
+        return kernel.value, rounds.value
 
     def joint_order(self):
         return self._order(self._L.s2amd_get_joint_order)

@@ -1,0 +1,99 @@
+"""The 512-thread resident-island kernel for s2Solve_SoftStep and s2Solve_PGS_Soft (wide_kernel.hip: wideIslandKernelOf), as far as
+it can be checked without a GPU:
+
+  * the host's choice of kernel for a world of resident islands only, on the stand-in HIP runtime of tests/hostcheck (kernels never
+    run; launch counts, group tables and s2amd_get_resident_kernel are host state): all three soft solvers take the world in ONE launch
+    per step from the second step on (kernel 4), and option "wide" = 0 puts all three back on islandStepKernel between the body
+    prologue and epilogue (kernel 2, three launches);
+  * the compiler's register report: every instantiation the launch can pick exists, has no scratch and keeps two waves per SIMD,
+    and the eight TGS_Soft instantiations kept their names.
+
+tests/test_gpu_wide_island_kinds.py checks what the kernels compute."""
+import glob
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOSTCHECK = os.path.join(ROOT, "tests", "hostcheck")
+sys.path.insert(0, ROOT)
+from tools import kernel_resources  # noqa: E402
+
+# launch.h: SOFT_TGS 0, SOFT_PGS 1, SOFT_FIXED 3 -- as the demangled names print them.  (kind, rounds) of every form that exists:
+# s2Solve_SoftStep has the six-round form only (wide_kernel.hip: wideIslandForm)
+NEW_FORMS = [(3, 6), (1, 6), (1, 8)]
+
+
+def _asan_runtime():
+    hits = sorted(glob.glob("/opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so"))
+    return hits[-1] if hits else None
+
+
+@pytest.fixture(scope="module")
+def cases():
+    if not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None:
+        pytest.skip("needs hipcc and clang's ASan runtime")
+    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
+    env = dict(os.environ)
+    env["LD_PRELOAD"] = _asan_runtime()
+    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
+    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
+    env["S2AMD_LIB"] = os.path.join(HOSTCHECK, "_build", "libs2amd_hostcheck.so")
+    p = subprocess.run([sys.executable, os.path.join(HOSTCHECK, "drive_island_kinds.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       timeout=900)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0 and "ISLAND KINDS DRIVER OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    found = [json.loads(line[5:]) for line in out.splitlines() if line.startswith("CASE ")]
+    assert len(found) == 2 * 3 * 2, out[-4000:]
+    return found
+
+
+@pytest.mark.parametrize("solver_name", ["TGS_Soft", "SoftStep", "PGS_Soft"])
+@pytest.mark.parametrize("world", ["pyramid10x8", "pyramid40x4"])
+def test_an_islands_only_world_is_one_launch_per_step(cases, world, solver_name):
+    (case,) = [c for c in cases if c["world"] == world and c["solver"] == solver_name and c["wide"] == 1]
+    print(case)
+    for step in case["steps"][1:]:  # (the first step builds the structure and runs with the body prologue and epilogue)
+        assert step["kernelLaunches"] == 1 and step["groupCount"] == 4 and step["stripCount"] == 0, case
+        assert step["kernel"] == 4 and step["rounds"] in (6, 8), case
+
+
+@pytest.mark.parametrize("solver_name", ["TGS_Soft", "SoftStep", "PGS_Soft"])
+@pytest.mark.parametrize("world", ["pyramid10x8", "pyramid40x4"])
+def test_option_wide_off_keeps_the_256_thread_island_kernel(cases, world, solver_name):
+    (case,) = [c for c in cases if c["world"] == world and c["solver"] == solver_name and c["wide"] == 0]
+    print(case)
+    for step in case["steps"]:
+        assert step["kernelLaunches"] == 3 and step["groupCount"] == 4 and step["stripCount"] == 0, case
+        assert step["kernel"] == 2, case
+
+
+@pytest.fixture(scope="module")
+def rows():
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("needs hipcc")
+    subprocess.check_call(["make", "-s", "-j4", "-C", os.path.join(ROOT, "solver2d_amd", "csrc"), "resources"])
+    return kernel_resources.parse()
+
+
+def test_every_form_the_island_launch_can_pick_is_register_resident(rows):
+    by_name = {r["name"]: r for r in rows}
+    for kind, rounds in NEW_FORMS:
+        for self_contained in ("false", "true"):
+            for points in (0, 2):
+                name = "wideIslandKernelOf<%d, %d, %s, %d>" % (kind, rounds, self_contained, points)
+                assert name in by_name, name
+                r = by_name[name]
+                print("%s: %d VGPRs, %d B scratch, %d waves/SIMD" % (name, r["VGPRs"], r["ScratchSize"], r["Occupancy"]))
+                assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["Occupancy"] >= 2, r
+                assert not r.get("scratch_instructions"), r  # (counted only for a kernel that declares a frame)
+    # nothing but those: an instantiation the launch cannot pick is compile time for nothing
+    assert len([n for n in by_name if n.startswith("wideIslandKernelOf<")]) == 4 * len(NEW_FORMS)
+    # s2Solve_TGS_Soft's kernels kept the names tests/test_kernel_resources.py looks them up by
+    for rounds in (6, 8):
+        for self_contained in ("false", "true"):
+            for points in (0, 2):
+                assert "wideIslandKernel<%d, %s, %d>" % (rounds, self_contained, points) in by_name
