@@ -503,7 +503,7 @@ __global__ __launch_bounds__(S2_GENERIC_THREADS) void genericStepKernel(ContactV
 
 int genericKernelSetup()
 {
-	hipError_t e = hipFuncSetAttribute((const void*)genericStepKernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+	hipError_t e = hipFuncSetAttribute((const void*)genericStepKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_LIMIT);
 	return e == hipSuccess ? 0 : (int)e;
 }
 

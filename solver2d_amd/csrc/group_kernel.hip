@@ -425,10 +425,10 @@ __global__ __launch_bounds__(THREADS) void groupKernel(ContactView c, JointView 
 int groupKernelSetup()
 {
 	// allow a group to use the full 160 KiB of LDS
-	hipError_t e = hipFuncSetAttribute((const void*)groupKernel<S2_GROUP_THREADS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+	hipError_t e = hipFuncSetAttribute((const void*)groupKernel<S2_GROUP_THREADS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_LIMIT);
 	if (e == hipSuccess)
 	{
-		e = hipFuncSetAttribute((const void*)groupKernel<S2_STRIP_THREADS, S2_STRIP_PRELOAD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		e = hipFuncSetAttribute((const void*)groupKernel<S2_STRIP_THREADS, S2_STRIP_PRELOAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_LIMIT);
 	}
 	return e == hipSuccess ? 0 : (int)e;
 }
@@ -457,7 +457,7 @@ void launchGroupKernel(hipStream_t s, const ContactView& c, const JointView& j, 
 	// (the staged tables behind the bodies of the largest group: 16-byte aligned, and only where 160 KiB hold them too -- a whole-step
 	// launch; the one-op launches of a sequential tail have one batch and one op to read)
 	const size_t staged = (((size_t)maxBodies + 1) / 2 * 16 + (size_t)(useDq0 ? 3 : 2) * maxBodies * 16) + (size_t)S2_GROUP_STAGED_BATCHES * 16 + (size_t)S2_GROUP_STAGED_OPS * sizeof(Op);
-	const int stage = opCount > 1 && staged <= 160 * 1024 ? 1 : 0;
+	const int stage = opCount > 1 && staged <= S2_LDS_LIMIT ? 1 : 0;
 	lds = stage ? std::max(lds, staged) : lds;
 	groupKernel<S2_GROUP_THREADS, 0><<<dim3((unsigned)gt.groupCount), dim3(S2_GROUP_THREADS), lds, s>>>(c, j, g, gt, ops, opCount, sc, wire, useDq0, stage);
 }

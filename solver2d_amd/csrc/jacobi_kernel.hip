@@ -444,7 +444,7 @@ int jacobiKernelSetup()
 {
 	for (const void* f : {(const void*)jacobiStepKernel<1>, (const void*)jacobiStepKernel<2>})
 	{
-		if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+		if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_LIMIT) != hipSuccess)
 		{
 			return 1;
 		}

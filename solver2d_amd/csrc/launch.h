@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "solver2d_amd.h"
 
 struct BodyView;
@@ -144,8 +146,57 @@ void launchWarmStartJointsBodies(hipStream_t s, const JointView& j, const BodyVi
 void launchWarmStartBodies(hipStream_t s, int kind, const ContactView& c, const BodyView& b, const int2* adjRange, const int* adjList,
 						   int integrateFirst, const int* heavy, int heavyCount);
 
+// Dynamic LDS a workgroup may ask for: every xxxKernelSetup() raises its kernels' limit to this, every plan is checked against it
+constexpr size_t S2_LDS_LIMIT = 160 * 1024;
+
+// One instantiation of a kernel family: its template arguments as plain numbers, and its address.  A family (wideStepKernel, wideIslandKernel,
+// stripStepKernel, islandStepKernel, stripSoftKernel, pairStepKernel) keeps ONE list of these beside its launcher, which looks the kernel for
+// its input up in it -- the rules are in the key it asks for, what exists is in the list -- and whose xxxKernelSetup() walks it.
+template <int N> struct KernelVariant
+{
+	int arg[N];
+	const void* fn;
+};
+template <int N> const KernelVariant<N>* findVariant(const std::vector<KernelVariant<N>>& list, const int (&key)[N])
+{
+	for (const KernelVariant<N>& v : list)
+	{
+		bool same = true;
+		for (int i = 0; i < N; ++i)
+		{
+			same = same && v.arg[i] == key[i];
+		}
+		if (same)
+		{
+			return &v;
+		}
+	}
+	return nullptr;
+}
+template <int N> int raiseLdsLimit(const std::vector<KernelVariant<N>>& list)
+{
+	for (const KernelVariant<N>& v : list)
+	{
+		const hipError_t e = hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_LIMIT);
+		if (e != hipSuccess)
+		{
+			return (int)e;
+		}
+	}
+	return 0;
+}
+// (every variant of a family has the same parameter list; args: objects of exactly the kernel's parameter types, in its order)
+template <int N, typename... Args> void launchVariant(const KernelVariant<N>& v, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args)
+{
+	void* ptrs[] = {(void*)&args...};
+	(void)hipLaunchKernel(v.fn, grid, block, ptrs, lds, s);
+}
+
 // strip_kernel.hip
 int stripKernelSetup();
+// dynamic LDS of stripStepKernel, pairStepKernel, islandStepKernel (and, without ops, stripSoftKernel): the records of the largest group of the
+// table -- bodies, seam constraint records, warm-start slots -- and the ops behind them
+size_t stripStepLds(int ldsRecords, int opCount);
 void launchIslandStep(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops,
 					  int opCount, int maxRounds, s2amdContact* wire, const s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart,
 					  const unsigned int* stepFailed);
@@ -170,15 +221,12 @@ struct WideSelf
 	int warmStart;
 	float gravityX, gravityY, unpackH;
 };
-// float4 records of dynamic LDS the kernel variant for this partition needs beside the bodies, the ops and its three fixed records
-// (parked rounds, staged positions, the warm start's term table); -1: no variant takes the partition
-int wideExtraRecords(const PersistView& pv, int selfContained, int bodyWarm, int kind = SOFT_TGS);
-int wideBodyWarmVariant(const PersistView& pv);
-// LDS records the resident-island kernel keeps per-lane anchors in beside the bodies: the local anchors of TGS_Soft's eight-round variant, the
-// arms rA0 / rB0 of seven records of PGS_Soft's eight-round and of all six of SoftStep's (six-round) variant
-int wideIslandLocalRecords(int maxRounds, int kind = SOFT_TGS);
-// does the resident-island kernel exist for this kind with this many colour rounds?  (SoftStep: up to S2_STRIP_ROUNDS only)
-int wideIslandForm(int kind, int maxRounds);
+// dynamic LDS of the variant that takes this partition with these two features, everything included (bodies, fixed records, ops, parked rounds,
+// arms / local anchors, staged positions, the warm start's term table); 0: no variant takes it.  launchWideStep passes the same number.
+size_t wideStepLds(int kind, const PersistView& pv, int opCount, bool selfContained, bool bodyWarm);
+// dynamic LDS of the resident-island kernel for this kind and this many colour rounds, everything included (bodies, coefficient records, ops, the
+// per-lane local anchors / arms of the records that keep them in LDS); 0: there is no such kernel (SoftStep: up to S2_STRIP_ROUNDS rounds only)
+size_t wideIslandLds(int kind, int maxRounds, int ldsRecords, int opCount);
 // ... and the resident islands' step (strip_kernel.hip: launchIslandStep) for TGS_Soft and PGS_Soft with the current-anchor warm start
 // (kind SOFT_TGS / SOFT_PGS) and for SoftStep with the fixed-anchor one (SOFT_FIXED)
 // selfContained: the kernel also stages its bodies from the wire records and writes them back (no prologue / epilogue launch)

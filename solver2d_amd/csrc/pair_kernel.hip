@@ -655,19 +655,23 @@ __global__ __launch_bounds__(S2_PAIR_THREADS) void pairStepKernel(ContactView c,
 	}
 }
 
-template <int KIND, int WARM>
-static void launchPair(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops,
-					   int opCount)
+// pairStepKernel by {KIND, WARM, POINTS}
+typedef KernelVariant<3> PairVariant;
+template <int KIND, int WARM> static void addPairs(std::vector<PairVariant>& list)
 {
-	const dim3 block(S2_PAIR_THREADS);
-	if (pv.allTwoPoints)
-	{
-		pairStepKernel<KIND, WARM, 2, S2_STRIP_ROUNDS><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-	}
-	else
-	{
-		pairStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-	}
+	list.push_back({{KIND, WARM, 0}, (const void*)pairStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS>});
+	list.push_back({{KIND, WARM, 2}, (const void*)pairStepKernel<KIND, WARM, 2, S2_STRIP_ROUNDS>});
+}
+static const std::vector<PairVariant>& pairVariants()
+{
+	static const std::vector<PairVariant> list = [] {
+		std::vector<PairVariant> v;
+		addPairs<SOFT_TGS, WARM_CURRENT>(v), addPairs<SOFT_TGS, WARM_FIXED>(v);
+		addPairs<SOFT_PGS, WARM_CURRENT>(v), addPairs<SOFT_PGS, WARM_FIXED>(v);
+		addPairs<SOFT_FIXED, WARM_CURRENT>(v), addPairs<SOFT_FIXED, WARM_FIXED>(v);
+		return v;
+	}();
+	return list;
 }
 
 // Eligibility (checked by the caller, solver_executor.h runPersistent): pv.pairLanes -- no strip has more than
@@ -675,42 +679,13 @@ static void launchPair(hipStream_t s, dim3 grid, size_t lds, const ContactView& 
 void launchPairStep(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops,
 					int opCount)
 {
-	const dim3 grid((unsigned)a.groupCount);
-	const size_t lds = (size_t)pv.ldsRecords * sizeof(float4) + (size_t)opCount * sizeof(Op);
-	if (kind == SOFT_TGS)
+	const PairVariant* v = findVariant(pairVariants(), {kind, warm, pv.allTwoPoints ? 2 : 0});
+	if (v != nullptr)
 	{
-		warm == WARM_FIXED ? launchPair<SOFT_TGS, WARM_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount)
-						   : launchPair<SOFT_TGS, WARM_CURRENT>(s, grid, lds, c, g, a, pv, ops, opCount);
-	}
-	else if (kind == SOFT_PGS)
-	{
-		warm == WARM_FIXED ? launchPair<SOFT_PGS, WARM_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount)
-						   : launchPair<SOFT_PGS, WARM_CURRENT>(s, grid, lds, c, g, a, pv, ops, opCount);
-	}
-	else
-	{
-		warm == WARM_FIXED ? launchPair<SOFT_FIXED, WARM_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount)
-						   : launchPair<SOFT_FIXED, WARM_CURRENT>(s, grid, lds, c, g, a, pv, ops, opCount);
+		launchVariant(*v, dim3((unsigned)a.groupCount), dim3(S2_PAIR_THREADS), stripStepLds(pv.ldsRecords, opCount), s, c, g, a, pv, ops, opCount);
 	}
 }
 
-int pairKernelSetup()
-{
-	const void* steps[] = {
-#define S2_PAIR_VARIANTS(K, W) (const void*)pairStepKernel<K, W, 0, S2_STRIP_ROUNDS>, (const void*)pairStepKernel<K, W, 2, S2_STRIP_ROUNDS>
-		S2_PAIR_VARIANTS(SOFT_TGS, WARM_CURRENT),	S2_PAIR_VARIANTS(SOFT_TGS, WARM_FIXED),	  S2_PAIR_VARIANTS(SOFT_PGS, WARM_CURRENT),
-		S2_PAIR_VARIANTS(SOFT_PGS, WARM_FIXED),		S2_PAIR_VARIANTS(SOFT_FIXED, WARM_CURRENT), S2_PAIR_VARIANTS(SOFT_FIXED, WARM_FIXED),
-#undef S2_PAIR_VARIANTS
-	};
-	for (const void* f : steps)
-	{
-		hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		if (e != hipSuccess)
-		{
-			return (int)e;
-		}
-	}
-	return 0;
-}
+int pairKernelSetup() { return raiseLdsLimit(pairVariants()); }
 
 S2_DEFINE_WARM(pair_kernel)

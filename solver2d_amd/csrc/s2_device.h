@@ -453,6 +453,7 @@ struct Op
 	int code, kind, useBias, flag;
 	float h, inv_h, f0, f1;
 };
+static_assert(sizeof(Op) == 32, "the kernels that stage their ops in LDS count them as two float4 records each (2 * opCount)");
 
 // batches: {begin, end, sequential?, 0} ranges into the constraint / joint SoA
 struct GroupTable

@@ -357,21 +357,14 @@ struct Executor
 		return true;
 	}
 
-	// Can the whole plan run as ONE persistent launch over the strips (strip_kernel.hip: stripStepKernel)?
-	bool persistPlan(int& kind, int& warm) const
+	// Is the plan one of the soft contact drivers -- body stages, one kind of current- or fixed-anchor warm start, one kind of soft sweep --, and
+	// which?  skipJointSweeps: joint sweeps have nothing to sweep where the plan is to run
+	bool softPlan(int& kind, int& warm, bool skipJointSweeps) const
 	{
-		if (!s->persistValid || s->persistFailed || p.ops.size() > 128 || p.solveSweeps > 63) // one hand-off epoch per sweep, 64 per step
-		{
-			return false;
-		}
 		kind = -1, warm = -1;
 		for (const Op& o : p.ops)
 		{
-			if (o.code == OP_INTEGRATE_VEL || o.code == OP_INTEGRATE_POS || o.code == OP_FINALIZE)
-			{
-				continue;
-			}
-			if (o.code == OP_JOINT_SWEEP && s->joints.stripCount == 0)
+			if (o.code == OP_INTEGRATE_VEL || o.code == OP_INTEGRATE_POS || o.code == OP_FINALIZE || (o.code == OP_JOINT_SWEEP && skipJointSweeps))
 			{
 				continue;
 			}
@@ -387,13 +380,23 @@ struct Executor
 			}
 			return false;
 		}
-		if (kind < 0)
+		if (kind >= 0 && warm < 0)
+		{
+			warm = kind == SOFT_FIXED ? WARM_FIXED : WARM_CURRENT;
+		}
+		return kind >= 0;
+	}
+
+	// Can the whole plan run as ONE persistent launch over the strips (strip_kernel.hip: stripStepKernel)?
+	bool persistPlan(int& kind, int& warm) const
+	{
+		if (!s->persistValid || s->persistFailed || p.ops.size() > 128 || p.solveSweeps > 63) // one hand-off epoch per sweep, 64 per step
 		{
 			return false;
 		}
-		if (warm < 0)
+		if (!softPlan(kind, warm, s->joints.stripCount == 0))
 		{
-			warm = kind == SOFT_FIXED ? WARM_FIXED : WARM_CURRENT;
+			return false;
 		}
 		if (widePlan(kind, warm))
 		{
@@ -403,10 +406,12 @@ struct Executor
 		{
 			return false; // (rounds opened since the build that only that kernel's tables and budgets know: IncrementalStrips)
 		}
-		const bool narrow = kind == SOFT_TGS && warm == WARM_CURRENT;
-		const int records = (narrow ? s->persist.ldsRecords : s->persistRecordsWide) + 2 * (int)p.ops.size();
-		return records <= (160 * 1024) / 16;
+		return stripStepLds(persistRecords(kind, warm), (int)p.ops.size()) <= S2_LDS_LIMIT;
 	}
+
+	// LDS records of stripStepKernel / pairStepKernel: the seam constraint records are S2_PERSIST_Q_NARROW float4 each for TGS_Soft with the
+	// current-anchor warm start, S2_PERSIST_Q_WIDE for the other kinds
+	int persistRecords(int kind, int warm) const { return kind == SOFT_TGS && warm == WARM_CURRENT ? s->persist.ldsRecords : s->persistRecordsWide; }
 
 	// Can the whole plan run as ONE launch of the op interpreter over the strips (generic_kernel.hip: genericStepKernel)?  Every
 	// Gauss-Seidel family and joints; not s2Solve_Jacobi (its body-centric apply needs the incidence lists).
@@ -423,7 +428,7 @@ struct Executor
 				return false;
 			}
 		}
-		return genericStepLds(s->genericBodies, s->genericSeamBodies, s->genericExports, (int)p.ops.size(), p.usesDq0 ? 1 : 0) <= 160 * 1024;
+		return genericStepLds(s->genericBodies, s->genericSeamBodies, s->genericExports, (int)p.ops.size(), p.usesDq0 ? 1 : 0) <= S2_LDS_LIMIT;
 	}
 
 	// one launch for the strips, whichever kernel: the register-resident soft kernels where they apply, else the op interpreter
@@ -437,16 +442,21 @@ struct Executor
 	// warm start on a partition with at most six interior colour batches per strip and two per seam.
 	bool widePlan(int kind, int warm) const
 	{
-		const bool current = (kind == SOFT_TGS || kind == SOFT_PGS) && warm == WARM_CURRENT;
-		const bool fixed = kind == SOFT_FIXED && warm == WARM_FIXED; // s2Solve_SoftStep: s2WarmStartContacts_Fixed
-		return s->optWide && (current || fixed) && wideFits(false, false, kind);
+		return s->optWide && wideKindAndWarm(kind, warm) && wideFits(false, false, kind);
+	}
+
+	// what the 512-thread kernels exist for: TGS_Soft and PGS_Soft with the current-anchor warm start, SoftStep with the fixed-anchor one
+	// (s2WarmStartContacts_Fixed)
+	static bool wideKindAndWarm(int kind, int warm)
+	{
+		return ((kind == SOFT_TGS || kind == SOFT_PGS) && warm == WARM_CURRENT) || (kind == SOFT_FIXED && warm == WARM_FIXED);
 	}
 
 	// the kernel variant for this partition with these two features: does its dynamic LDS fit?
 	bool wideFits(bool selfContained, bool bodyWarm, int kind = SOFT_TGS) const
 	{
-		const int extra = wideExtraRecords(s->persist, selfContained ? 1 : 0, bodyWarm ? 1 : 0, kind);
-		return extra >= 0 && s->persist.bodyRecords + 3 + extra + 2 * s->persistOpCount <= (160 * 1024) / 16;
+		const size_t lds = wideStepLds(kind, s->persist, s->persistOpCount, selfContained, bodyWarm);
+		return lds != 0 && lds <= S2_LDS_LIMIT;
 	}
 
 	// ... as the step's ONLY launch (wide_kernel.hip: S2_WIDE_SELF): the strips are all there is -- every movable body is owned by one,
@@ -463,7 +473,7 @@ struct Executor
 	// s2WarmStartContacts body-centric inside that kernel: a variant without parked rounds whose term table fits LDS
 	bool wideBodyWarm(bool selfContained) const
 	{
-		return s->optWideBodyWarm != 0 && wideBodyWarmVariant(s->persist) != 0 && wideFits(selfContained, true);
+		return s->optWideBodyWarm != 0 && wideFits(selfContained, true);
 	}
 
 	// Can the plan run on the resident-island kernel (strip_kernel.hip: islandStepKernel)?  The soft contact drivers: body
@@ -484,33 +494,7 @@ struct Executor
 		{
 			return false;
 		}
-		for (const Op& o : p.ops)
-		{
-			if (o.code == OP_INTEGRATE_VEL || o.code == OP_INTEGRATE_POS || o.code == OP_FINALIZE || o.code == OP_JOINT_SWEEP)
-			{
-				continue;
-			}
-			if (o.code == OP_WARM && (o.kind == WARM_CURRENT || o.kind == WARM_FIXED) && (warm < 0 || warm == o.kind))
-			{
-				warm = o.kind;
-				continue;
-			}
-			if (leanSoftKind(o) && (kind < 0 || kind == o.kind))
-			{
-				kind = o.kind;
-				continue;
-			}
-			return false;
-		}
-		if (kind < 0)
-		{
-			return false;
-		}
-		if (warm < 0)
-		{
-			warm = kind == SOFT_FIXED ? WARM_FIXED : WARM_CURRENT;
-		}
-		return true;
+		return softPlan(kind, warm, true);
 	}
 
 	int uploadResidentOps()
@@ -549,8 +533,8 @@ struct Executor
 
 	// the groups that were laid out for the resident-island kernel: on it when the plan allows, else through the generic
 	// group interpreter (the table is an ordinary group table too)
-	// the resident islands on wide_kernel.hip: wideIslandKernel (TGS_Soft with the current-anchor warm start) and wideIslandKernelOf
-	// (PGS_Soft with the current-anchor, SoftStep with the fixed-anchor warm start) -- where the kernel has a form for the groups' colour
+	// the resident islands on wide_kernel.hip: wideIslandKernel (TGS_Soft and PGS_Soft with the current-anchor, SoftStep with the
+	// fixed-anchor warm start) -- where the kernel has a form for the groups' colour
 	// rounds (SoftStep: up to six) and the LDS of THAT form fits beside the bodies (SoftStep: six records' arms, 96 KB); else islandStepKernel
 	bool wideIslandPlan() const
 	{
@@ -559,10 +543,8 @@ struct Executor
 		{
 			return false;
 		}
-		const bool current = (kind == SOFT_TGS || kind == SOFT_PGS) && warm == WARM_CURRENT;
-		const bool fixed = kind == SOFT_FIXED && warm == WARM_FIXED; // s2Solve_SoftStep: s2WarmStartContacts_Fixed
-		return (current || fixed) && wideIslandForm(kind, s->residentRounds) != 0 &&
-			   s->residentView.ldsRecords + 2 + wideIslandLocalRecords(s->residentRounds, kind) + 2 * s->residentOpCount <= (160 * 1024) / 16;
+		const size_t lds = wideIslandLds(kind, s->residentRounds, s->residentView.ldsRecords, s->residentOpCount);
+		return wideKindAndWarm(kind, warm) && lds != 0 && lds <= S2_LDS_LIMIT;
 	}
 
 	// ... and nothing else in the world: every body is owned by a resident island, every constraint is one of theirs, no joints, and
@@ -667,6 +649,20 @@ struct Executor
 		return kept;
 	}
 
+	// the partition's view as a launch of this step takes it: where hand-offs may go through L2 now, the step's soft coefficients, the LDS records
+	// of the kind's seam constraints
+	PersistView launchView(int kind, int warm) const
+	{
+		PersistView pv = s->persist;
+		pv.nearHandoff = s->nearHandoffNow;
+		for (int i = 0; i < 2; ++i)
+		{
+			pv.softCoef[i] = make_float4(p.sc.softCoef[i][0], p.sc.softCoef[i][1], p.sc.softCoef[i][2], 0.0f);
+		}
+		pv.ldsRecords = persistRecords(kind, warm);
+		return pv;
+	}
+
 	// contacts in the overflow region behind the strips (solver_internal.h: IncrementalStrips): the step runs sliced
 	bool slicedPlan() const { return s->stripInc.valid && s->stripInc.overflowUsed > 0; }
 
@@ -679,16 +675,7 @@ struct Executor
 	{
 		const std::vector<Op> kept = keptOps();
 		const int n = (int)kept.size();
-		PersistView pv = s->persist;
-		pv.nearHandoff = s->nearHandoffNow;
-		for (int i = 0; i < 2; ++i)
-		{
-			pv.softCoef[i] = make_float4(p.sc.softCoef[i][0], p.sc.softCoef[i][1], p.sc.softCoef[i][2], 0.0f);
-		}
-		if (!(kind == SOFT_TGS && warm == WARM_CURRENT))
-		{
-			pv.ldsRecords = s->persistRecordsWide;
-		}
+		PersistView pv = launchView(kind, warm);
 		pv.bodyWarm = 0;
 		pv.clearOwn = 1; // (every launch leaves the buffers it read at zero tags for the next one: no memset between the slices)
 		const IncrementalStrips& m = s->stripInc;
@@ -737,16 +724,7 @@ struct Executor
 		{
 			recordEvent();
 		}
-		PersistView pv = s->persist;
-		pv.nearHandoff = s->nearHandoffNow;
-		for (int i = 0; i < 2; ++i)
-		{
-			pv.softCoef[i] = make_float4(p.sc.softCoef[i][0], p.sc.softCoef[i][1], p.sc.softCoef[i][2], 0.0f);
-		}
-		if (!(kind == SOFT_TGS && warm == WARM_CURRENT))
-		{
-			pv.ldsRecords = s->persistRecordsWide;
-		}
+		PersistView pv = launchView(kind, warm);
 		if (widePlan(kind, warm))
 		{
 			WideSelf self{};
@@ -791,7 +769,7 @@ struct Executor
 		}
 		// the strips' joints resident in LDS when every strip's fit beside its bodies (JointGrid: 176 B x ~400 joints per strip)
 		const size_t withJoints = genericStepLds(s->genericBodies, s->genericSeamBodies, s->genericExports, s->persistOpCount, p.usesDq0 ? 1 : 0, s->genericJoints);
-		const bool stage = s->optStageJoints != 0 && s->genericJoints > 0 && withJoints <= 160 * 1024;
+		const bool stage = s->optStageJoints != 0 && s->genericJoints > 0 && withJoints <= S2_LDS_LIMIT;
 		const size_t lds = stage ? withJoints : genericStepLds(s->genericBodies, s->genericSeamBodies, s->genericExports, s->persistOpCount, p.usesDq0 ? 1 : 0);
 		PersistView gpv = s->persist;
 		gpv.nearHandoff = s->nearHandoffNow;
@@ -927,7 +905,7 @@ struct Executor
 				return false;
 			}
 		}
-		return sweeps && jacobiStepLds(s->jacobiMaxOwned, s->jacobiMaxImports, s->jacobiMaxConstraints, (int)p.ops.size()) <= 160 * 1024;
+		return sweeps && jacobiStepLds(s->jacobiMaxOwned, s->jacobiMaxImports, s->jacobiMaxConstraints, (int)p.ops.size()) <= S2_LDS_LIMIT;
 	}
 
 	void run()

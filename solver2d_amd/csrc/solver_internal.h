@@ -275,7 +275,7 @@ struct IncrementalStrips
 	std::vector<int> positionOfSlot;	// contact slot -> strip position, -1
 	long placed = 0, roundsOpened = 0;
 	// rounds a strip / a seam may have OPEN under the solver these strips were built for: s2Solve_SoftStep's resident kernel exists in
-	// the <3, 2> layout only (wide_kernel.hip: wideExtraRecords) -- a seventh interior or third seam round opened for a created contact
+	// the <3, 2> layout only (wide_kernel.hip: wideVariants) -- a seventh interior or third seam round opened for a created contact
 	// left it without a kernel, and the step rebuilt the strips instead (wreck-200 under SoftStep, r6: 50 such steps of 200, 5-40 ms each)
 	int roundLimit[2] = {S2_STRIP_ROUNDS_MAX, S2_PERSIST_B_ROUNDS};
 	// strips the OP INTERPRETER sweeps (generic_kernel.hip: every solver family but the soft ones): it finds its rounds and body lists in the

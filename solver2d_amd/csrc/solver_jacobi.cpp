@@ -321,7 +321,7 @@ int buildJacobiBlocks(s2amdSolver* s)
 			ints.push_back((ownedBody(b) && blockOf[(size_t)b] == g) ? slotOf[(size_t)b] : -1);
 		}
 	}
-	if (jacobiStepLds(maxOwned, maxImports, maxConstraints, 64) > 160 * 1024)
+	if (jacobiStepLds(maxOwned, maxImports, maxConstraints, 64) > S2_LDS_LIMIT)
 	{
 		return S2AMD_OK;
 	}

@@ -1020,11 +1020,11 @@ static int buildLeanStripTables(s2amdSolver* s, const StripPartition& strips, co
 				d.slotCount = (int)slotList.size() - d.slotBase;
 			}
 			int records = 2 * d.bodyCount + 2 * d.slotCount;
-			if (ok && records > (160 * 1024) / 16)
+			if (ok && stripStepLds(records, 0) > S2_LDS_LIMIT)
 			{
 				leanWhy = "LDS: bodies + warm-start slots";
 			}
-			ok = ok && records <= (160 * 1024) / 16;
+			ok = ok && stripStepLds(records, 0) <= S2_LDS_LIMIT;
 			ldsRecords = std::max(ldsRecords, records);
 			out.push_back(d);
 		}
@@ -1317,8 +1317,8 @@ do                                                                              
 			// bodies, seam constraints (S2_PERSIST_Q_NARROW records each for TGS_Soft, S2_PERSIST_Q_WIDE for the other kinds)
 			int fixedRecords = 3 * nt + (nt + 3) / 4 + (nt + 1) / 2; // velocity, pose, integrator constants, angular damping, inverse masses
 			const int seamRecordsNarrow = seamRegs ? 0 : S2_PERSIST_Q_NARROW * seamSlots;
-			NEEDSOFT(fixedRecords + seamRecordsNarrow + 2 * 16 <= (160 * 1024) / 16 && nt < 16384); // the plan's own records are checked when it is known (persistPlan)
-			NEED(genericStepLds(nt, genericSeamBodies, genericExports, 16, 0) <= 160 * 1024); // (with the plan's ops and its XPBD history: Executor::genericPlan)
+			NEEDSOFT(stripStepLds(fixedRecords + seamRecordsNarrow, 16) <= S2_LDS_LIMIT && nt < 16384); // the plan's own records are checked when it is known (persistPlan)
+			NEED(genericStepLds(nt, genericSeamBodies, genericExports, 16, 0) <= S2_LDS_LIMIT); // (with the plan's ops and its XPBD history: Executor::genericPlan)
 			ldsRecords = std::max(ldsRecords, fixedRecords + seamRecordsNarrow);
 			bodyRecordsMax = std::max(bodyRecordsMax, fixedRecords);
 			ldsRecordsWide = std::max(ldsRecordsWide, fixedRecords + S2_PERSIST_Q_WIDE * seamSlots);
@@ -1513,7 +1513,7 @@ static int buildResidentTables(s2amdSolver* s)
 		}
 		const int nbG = d.bodyCount;
 		const int records = 3 * nbG + (nbG + 3) / 4 + 2 * ((nbG + 1) / 2); // (+ the local centres wide_kernel.hip: wideIslandKernel stages)
-		ok = ok && (size_t)records * 16 + 128 * sizeof(Op) <= 160 * 1024;
+		ok = ok && stripStepLds(records, 128) <= S2_LDS_LIMIT; // (islandStepKernel with the longest plan)
 		ldsRecords = std::max(ldsRecords, records);
 		s->residentRounds = std::max(s->residentRounds, d.batchCount);
 	}

@@ -1161,194 +1161,90 @@ __global__ __launch_bounds__(THREADS) void islandStepKernel(ContactView c, BodyV
 	}
 }
 
+size_t stripStepLds(int ldsRecords, int opCount) { return (size_t)ldsRecords * sizeof(float4) + (size_t)opCount * sizeof(Op); }
+
+// Every instantiation of the three kernel families of this file that exists: islandStepKernel by {KIND, WARM, ROUNDS}, stripStepKernel by
+// {KIND, WARM, POINTS, ROUNDS, SEAMREG}, stripSoftKernel by {KIND, WARM} (WARM -1: no warm start in the launch)
 #define S2_ISLAND_THREADS 512
-template <int KIND, int WARM>
-static void launchIsland(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* coef, const Op* ops,
-						 int opCount, int rounds, s2amdContact* wire, const s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const unsigned int* stepFailed)
+struct StripVariants
 {
-	if (rounds <= S2_STRIP_ROUNDS)
-	{
-		islandStepKernel<KIND, WARM, S2_STRIP_ROUNDS, S2_ISLAND_THREADS>
-			<<<grid, dim3(S2_ISLAND_THREADS), lds, s>>>(c, g, t, coef[0], coef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, stepFailed);
-	}
-	else
-	{
-		islandStepKernel<KIND, WARM, S2_STRIP_ROUNDS_MAX, S2_ISLAND_THREADS>
-			<<<grid, dim3(S2_ISLAND_THREADS), lds, s>>>(c, g, t, coef[0], coef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, stepFailed);
-	}
+	std::vector<KernelVariant<3>> island;
+	std::vector<KernelVariant<5>> step;
+	std::vector<KernelVariant<2>> soft;
+};
+template <int KIND, int WARM> static void addStripVariants(StripVariants& v)
+{
+	v.island.push_back({{KIND, WARM, S2_STRIP_ROUNDS}, (const void*)islandStepKernel<KIND, WARM, S2_STRIP_ROUNDS, S2_ISLAND_THREADS>});
+	v.island.push_back({{KIND, WARM, S2_STRIP_ROUNDS_MAX}, (const void*)islandStepKernel<KIND, WARM, S2_STRIP_ROUNDS_MAX, S2_ISLAND_THREADS>});
+	v.step.push_back({{KIND, WARM, 0, S2_STRIP_ROUNDS, 0}, (const void*)stripStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS, 0>});
+	v.step.push_back({{KIND, WARM, 2, S2_STRIP_ROUNDS, 0}, (const void*)stripStepKernel<KIND, WARM, 2, S2_STRIP_ROUNDS, 0>});
+	v.step.push_back({{KIND, WARM, 0, S2_STRIP_ROUNDS_MAX, 0}, (const void*)stripStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS_MAX, 0>});
+	v.step.push_back({{KIND, WARM, 2, S2_STRIP_ROUNDS_MAX, 0}, (const void*)stripStepKernel<KIND, WARM, 2, S2_STRIP_ROUNDS_MAX, 0>});
+	v.soft.push_back({{KIND, WARM}, (const void*)stripSoftKernel<KIND, WARM>});
+}
+template <int KIND> static void addStripVariants(StripVariants& v)
+{
+	addStripVariants<KIND, WARM_CURRENT>(v);
+	addStripVariants<KIND, WARM_FIXED>(v);
+	v.soft.push_back({{KIND, -1}, (const void*)stripSoftKernel<KIND, -1>});
+}
+static const StripVariants& stripVariants()
+{
+	static const StripVariants all = [] {
+		StripVariants v;
+		addStripVariants<SOFT_TGS>(v);
+		addStripVariants<SOFT_PGS>(v);
+		addStripVariants<SOFT_FIXED>(v);
+		// seam records in registers -- TGS_Soft only: the other kinds' records are 30-32 dwords and four more of them spill; and the two-point fast
+		// path does not fit the register file together with them either (249 spilled registers), so this is the per-point variant
+		v.step.push_back({{SOFT_TGS, WARM_CURRENT, 0, S2_STRIP_ROUNDS, 1}, (const void*)stripStepKernel<SOFT_TGS, WARM_CURRENT, 0, S2_STRIP_ROUNDS, 1>});
+		return v;
+	}();
+	return all;
 }
 
 // t.ldsRecords: body records of the largest group; maxRounds: colour rounds of the group with the most
 void launchIslandStep(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops,
 					  int opCount, int maxRounds, s2amdContact* wire, const s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const unsigned int* stepFailed)
 {
-	if (t.groupCount <= 0)
+	const auto* v = findVariant(stripVariants().island, {kind, warm, maxRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX});
+	if (t.groupCount <= 0 || v == nullptr)
 	{
 		return;
 	}
-	dim3 grid((unsigned)t.groupCount);
-	size_t lds = (size_t)t.ldsRecords * sizeof(float4) + (size_t)opCount * sizeof(Op);
-	if (kind == SOFT_TGS)
-	{
-		warm == WARM_FIXED ? launchIsland<SOFT_TGS, WARM_FIXED>(s, grid, lds, c, g, t, softCoef, ops, opCount, maxRounds, wire, wireBodies, hostFlags, warmStart, stepFailed)
-						   : launchIsland<SOFT_TGS, WARM_CURRENT>(s, grid, lds, c, g, t, softCoef, ops, opCount, maxRounds, wire, wireBodies, hostFlags, warmStart, stepFailed);
-	}
-	else if (kind == SOFT_PGS)
-	{
-		warm == WARM_FIXED ? launchIsland<SOFT_PGS, WARM_FIXED>(s, grid, lds, c, g, t, softCoef, ops, opCount, maxRounds, wire, wireBodies, hostFlags, warmStart, stepFailed)
-						   : launchIsland<SOFT_PGS, WARM_CURRENT>(s, grid, lds, c, g, t, softCoef, ops, opCount, maxRounds, wire, wireBodies, hostFlags, warmStart, stepFailed);
-	}
-	else
-	{
-		warm == WARM_FIXED ? launchIsland<SOFT_FIXED, WARM_FIXED>(s, grid, lds, c, g, t, softCoef, ops, opCount, maxRounds, wire, wireBodies, hostFlags, warmStart, stepFailed)
-						   : launchIsland<SOFT_FIXED, WARM_CURRENT>(s, grid, lds, c, g, t, softCoef, ops, opCount, maxRounds, wire, wireBodies, hostFlags, warmStart, stepFailed);
-	}
-}
-
-template <int KIND, int WARM>
-static void launchStep(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv,
-					   const Op* ops, int opCount)
-{
-	dim3 block(S2_STRIP_THREADS);
-	if (pv.wideRounds)
-	{
-		if (pv.allTwoPoints)
-		{
-			stripStepKernel<KIND, WARM, 2, S2_STRIP_ROUNDS_MAX, 0><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-		}
-		else
-		{
-			stripStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS_MAX, 0><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-		}
-	}
-	else if (pv.seamRegs && KIND == SOFT_TGS && WARM == WARM_CURRENT)
-	{
-		// TGS_Soft only: the other kinds' records are 30-32 dwords and four more of them spill; and the two-point fast path
-		// does not fit the register file together with them either (249 spilled registers), so this is the per-point variant
-		if constexpr (KIND == SOFT_TGS && WARM == WARM_CURRENT)
-		{
-			stripStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS, 1><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-		}
-	}
-	else if (pv.allTwoPoints)
-	{
-		stripStepKernel<KIND, WARM, 2, S2_STRIP_ROUNDS, 0><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-	}
-	else
-	{
-		stripStepKernel<KIND, WARM, 0, S2_STRIP_ROUNDS, 0><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount);
-	}
+	launchVariant(*v, dim3((unsigned)t.groupCount), dim3(S2_ISLAND_THREADS), stripStepLds(t.ldsRecords, opCount), s, c, g, t, softCoef[0], softCoef[1], ops, opCount, wire,
+				  wireBodies, hostFlags, warmStart, stepFailed);
 }
 
 void launchStripStep(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv,
 					 const Op* ops, int opCount)
 {
-	dim3 grid((unsigned)a.groupCount);
-	size_t lds = (size_t)pv.ldsRecords * sizeof(float4) + (size_t)opCount * sizeof(Op); // ldsRecords: bodies + seam constraint records
-	if (kind == SOFT_TGS)
+	// (seam records in registers: TGS_Soft with the current-anchor warm start on six rounds; the other kinds keep theirs in LDS on such a partition too)
+	const bool seamRegs = !pv.wideRounds && pv.seamRegs && kind == SOFT_TGS && warm == WARM_CURRENT;
+	const auto* v = findVariant(stripVariants().step, {kind, warm, !seamRegs && pv.allTwoPoints ? 2 : 0, pv.wideRounds ? S2_STRIP_ROUNDS_MAX : S2_STRIP_ROUNDS, seamRegs ? 1 : 0});
+	if (v != nullptr)
 	{
-		warm == WARM_FIXED ? launchStep<SOFT_TGS, WARM_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount)
-						   : launchStep<SOFT_TGS, WARM_CURRENT>(s, grid, lds, c, g, a, pv, ops, opCount);
-	}
-	else if (kind == SOFT_PGS)
-	{
-		warm == WARM_FIXED ? launchStep<SOFT_PGS, WARM_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount)
-						   : launchStep<SOFT_PGS, WARM_CURRENT>(s, grid, lds, c, g, a, pv, ops, opCount);
-	}
-	else
-	{
-		warm == WARM_FIXED ? launchStep<SOFT_FIXED, WARM_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount)
-						   : launchStep<SOFT_FIXED, WARM_CURRENT>(s, grid, lds, c, g, a, pv, ops, opCount);
-	}
-}
-
-template <int KIND>
-static void launchKind(hipStream_t s, int warm, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& t, const StripOps& ops)
-{
-	switch (warm)
-	{
-		case WARM_CURRENT:
-			stripSoftKernel<KIND, WARM_CURRENT><<<grid, dim3(S2_STRIP_THREADS), lds, s>>>(c, g, t.descs, t.bodyIds, t.slots, t.slotOffsets, ops);
-			break;
-		case WARM_FIXED:
-			stripSoftKernel<KIND, WARM_FIXED><<<grid, dim3(S2_STRIP_THREADS), lds, s>>>(c, g, t.descs, t.bodyIds, t.slots, t.slotOffsets, ops);
-			break;
-		default:
-			stripSoftKernel<KIND, -1><<<grid, dim3(S2_STRIP_THREADS), lds, s>>>(c, g, t.descs, t.bodyIds, t.slots, t.slotOffsets, ops);
-			break;
+		// pv.ldsRecords: bodies + seam constraint records
+		launchVariant(*v, dim3((unsigned)a.groupCount), dim3(S2_STRIP_THREADS), stripStepLds(pv.ldsRecords, opCount), s, c, g, a, pv, ops, opCount);
 	}
 }
 
 void launchStripSoft(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& t, const StripOps& ops)
 {
-	if (t.groupCount <= 0)
+	const auto* v = findVariant(stripVariants().soft, {kind, warm == WARM_CURRENT || warm == WARM_FIXED ? warm : -1});
+	if (t.groupCount <= 0 || v == nullptr)
 	{
 		return;
 	}
-	dim3 grid((unsigned)t.groupCount);
-	size_t lds = (size_t)t.ldsRecords * sizeof(float4);
-	switch (kind)
-	{
-		case SOFT_TGS:
-			launchKind<SOFT_TGS>(s, warm, grid, lds, c, g, t, ops);
-			break;
-		case SOFT_PGS:
-			launchKind<SOFT_PGS>(s, warm, grid, lds, c, g, t, ops);
-			break;
-		case SOFT_FIXED:
-			launchKind<SOFT_FIXED>(s, warm, grid, lds, c, g, t, ops);
-			break;
-	}
+	launchVariant(*v, dim3((unsigned)t.groupCount), dim3(S2_STRIP_THREADS), stripStepLds(t.ldsRecords, 0), s, c, g, t.descs, t.bodyIds, t.slots, t.slotOffsets, ops);
 }
 
 int stripKernelSetup()
 {
-	const void* fns[] = {
-		(const void*)stripSoftKernel<SOFT_TGS, WARM_CURRENT>,	(const void*)stripSoftKernel<SOFT_TGS, WARM_FIXED>,	  (const void*)stripSoftKernel<SOFT_TGS, -1>,
-		(const void*)stripSoftKernel<SOFT_PGS, WARM_CURRENT>,	(const void*)stripSoftKernel<SOFT_PGS, WARM_FIXED>,	  (const void*)stripSoftKernel<SOFT_PGS, -1>,
-		(const void*)stripSoftKernel<SOFT_FIXED, WARM_CURRENT>, (const void*)stripSoftKernel<SOFT_FIXED, WARM_FIXED>, (const void*)stripSoftKernel<SOFT_FIXED, -1>,
-	};
-	const void* steps[] = {
-		(const void*)stripStepKernel<SOFT_TGS, WARM_CURRENT, 0, S2_STRIP_ROUNDS, 1>,
-#define S2_STEP_VARIANTS(K, W)                                                                                                   \
-	(const void*)stripStepKernel<K, W, 0, S2_STRIP_ROUNDS, 0>, (const void*)stripStepKernel<K, W, 2, S2_STRIP_ROUNDS, 0>,        \
-		(const void*)stripStepKernel<K, W, 0, S2_STRIP_ROUNDS_MAX, 0>, (const void*)stripStepKernel<K, W, 2, S2_STRIP_ROUNDS_MAX, 0>
-		S2_STEP_VARIANTS(SOFT_TGS, WARM_CURRENT),	S2_STEP_VARIANTS(SOFT_TGS, WARM_FIXED),	  S2_STEP_VARIANTS(SOFT_PGS, WARM_CURRENT),
-		S2_STEP_VARIANTS(SOFT_PGS, WARM_FIXED),		S2_STEP_VARIANTS(SOFT_FIXED, WARM_CURRENT), S2_STEP_VARIANTS(SOFT_FIXED, WARM_FIXED),
-#undef S2_STEP_VARIANTS
-	};
-	const void* islands[] = {
-#define S2_ISLAND_VARIANTS(K, W)                                                                                                 \
-	(const void*)islandStepKernel<K, W, S2_STRIP_ROUNDS, S2_ISLAND_THREADS>, (const void*)islandStepKernel<K, W, S2_STRIP_ROUNDS_MAX, S2_ISLAND_THREADS>
-		S2_ISLAND_VARIANTS(SOFT_TGS, WARM_CURRENT),	 S2_ISLAND_VARIANTS(SOFT_TGS, WARM_FIXED),	 S2_ISLAND_VARIANTS(SOFT_PGS, WARM_CURRENT),
-		S2_ISLAND_VARIANTS(SOFT_PGS, WARM_FIXED),	 S2_ISLAND_VARIANTS(SOFT_FIXED, WARM_CURRENT), S2_ISLAND_VARIANTS(SOFT_FIXED, WARM_FIXED),
-#undef S2_ISLAND_VARIANTS
-	};
-	for (const void* f : islands)
-	{
-		hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		if (e != hipSuccess)
-		{
-			return (int)e;
-		}
-	}
-	for (const void* f : steps)
-	{
-		hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		if (e != hipSuccess)
-		{
-			return (int)e;
-		}
-	}
-	for (const void* f : fns)
-	{
-		hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		if (e != hipSuccess)
-		{
-			return (int)e;
-		}
-	}
-	return 0;
+	const StripVariants& v = stripVariants();
+	int e = raiseLdsLimit(v.island);
+	e = e != 0 ? e : raiseLdsLimit(v.step);
+	return e != 0 ? e : raiseLdsLimit(v.soft);
 }
 
 S2_DEFINE_WARM(strip_kernel)

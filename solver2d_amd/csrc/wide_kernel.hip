@@ -31,11 +31,6 @@
 #ifndef S2_PERSIST_INSTRUMENTED
 #define S2_PERSIST_INSTRUMENTED 0
 #endif
-// 1: strips are dealt to the workgroups so that neighbours share an XCD, and a seam inside an XCD hands its bodies over through
-// that XCD's L2 (experiment switch)
-#ifndef S2_WIDE_XCD_AFFINE
-#define S2_WIDE_XCD_AFFINE 1
-#endif
 #define S2_WIDE_THREADS 512
 #define S2_WIDE_INTERIOR 256  // a colour batch of a strip has at most 256 constraints: interior round i runs on half i & 1 of the workgroup
 #define S2_WIDE_ROUNDS_PER_HALF (S2_STRIP_ROUNDS / 2) // ... so a lane holds three interior records
@@ -93,62 +88,10 @@ template <int KIND> S2_DEV WideRegs loadWide(const ContactView& c, int k, int ia
 }
 
 S2_DEV V2 asV2(f2 v) { return v2(v.x, v.y); }
-// rotate (math.h:330-341) on 2-vectors: q = {s, c}, qn = {-s, c}: (c x + (-s) y, s x + c y) -- (-s) y == -(s y) and
-// a - b == a + (-b), so these are the reference's bits
-S2_DEV f2 rot2(f2 q, f2 qn, f2 l)
-{
-	return q.yx * l.xx + qn * l.yy;
-}
-
 // s2WarmStartContacts (solve_common.c:276-330): strip_kernel.hip warmSoftRegs
 // The warm start and the prep on 2-vectors both measured SLOWER (178 / 171 vs 131 us per launch: their even-aligned
 // register pairs push resident constraint registers into scratch on the hand-off path -- 84 spilled VGPRs instead of ~30);
-// only the chain (chainWide) is packed.  Kept for the A/B (tools/kernel_ab.sh).
-#ifndef S2_WIDE_PACKED_WARM
-#define S2_WIDE_PACKED_WARM 0
-#endif
-#ifndef S2_WIDE_PACKED_PREP
-#define S2_WIDE_PACKED_PREP 0
-#endif
-#if S2_WIDE_PACKED_WARM
-template <int KIND, int POINTS> S2_DEV void warmWide(const WideRegs& p, float4* lvel, const float4* ldq, const float2* lmass, uint32_t salt)
-{
-	const uint32_t idx = p.idx ^ salt;
-	const int ia = (int)(idx & 0x1fffu), ib = (int)((idx >> 13) & 0x1fffu);
-	const int pointCount = (int)((idx >> 26) & 3u);
-	const float4 velA = lvel[ia], velB = lvel[ib];
-	const f2 qA = hi2(ldq[ia]), qB = hi2(ldq[ib]);
-	const float2 mA = lmass[ia], mB = lmass[ib];
-	const f2 n = f2{fromBits(asBits(p.n.x) ^ salt), p.n.y};
-	const f2 t = f2{n.y, -n.x};
-	const f2 qnA = f2{-qA.x, qA.y}, qnB = f2{-qB.x, qB.y};
-	const f2 nmA2 = f2{-mA.x, -mA.x}, mB2 = f2{mB.x, mB.x};
-	f2 vA = lo2(velA), vB = lo2(velB);
-	float wA = velA.z, wB = velB.z;
-#pragma unroll
-	for (int j = 0; j < 2; ++j)
-	{
-		if (POINTS == 2 || j < pointCount)
-		{
-			const f2 rA = rot2(qA, qnA, p.lA[j]), rB = rot2(qB, qnB, p.lB[j]);
-			const f2 P = p.imp[j].xx * n + p.imp[j].yy * t; // add(mulSV(normalImpulse, normal), mulSV(tangentImpulse, tangent))
-			const f2 cA = rA * P.yx, cB = rB * P.yx;		// cross(r, P) = r.x P.y - r.y P.x
-			wA -= mA.y * (cA.x - cA.y);
-			vA = vA + nmA2 * P; // mulAdd(vA, -mA, P)
-			wB += mB.y * (cB.x - cB.y);
-			vB = vB + mB2 * P;
-		}
-	}
-	if ((idx & (1u << 28)) != 0)
-	{
-		lvel[ia] = make_float4(vA.x, vA.y, wA, 0.0f);
-	}
-	if ((idx & (1u << 29)) != 0)
-	{
-		lvel[ib] = make_float4(vB.x, vB.y, wB, 0.0f);
-	}
-}
-#else
+// only the chain (chainWide) is packed.
 // LL: the record's local anchors wait in LDS ({lA, lB} per manifold point and lane: `locals`), not in p.lA / p.lB -- the variants that hold
 // a sixth resident record, or resident records beside parked rounds (wideLocalsInLds): the registers the record gives up are what
 // those variants used to spill
@@ -210,7 +153,6 @@ S2_DEV void warmWide(const WideRegs& p, float4* lvel, const float4* ldq, const f
 		lvel[ib] = make_float4(vB.x, vB.y, wB, 0.0f);
 	}
 }
-#endif
 
 // s2SolveContacts_TGS_Soft (solve_tgs_soft.c:17-135) = constraint_ops.h solveSoftRegs<SOFT_TGS>, operation for operation, in two
 // parts (the split of constraint_ops.h prepSoft / chainSoft):
@@ -220,20 +162,13 @@ S2_DEV void warmWide(const WideRegs& p, float4* lvel, const float4* ldq, const f
 //             every lane while the seam bodies are in flight);
 //   chainWide what depends on the VELOCITIES: relative velocity -> impulse -> clamp -> apply, point after point, normal then
 //             friction.  This is what a colour round has to wait for.
-// 1: the chain on explicit 2-vectors (v_pk_mul_f32 / v_pk_add_f32: two IEEE operations per issue slot, each rounded on its own)
-#ifndef S2_WIDE_PACKED
-#define S2_WIDE_PACKED 1
-#endif
+// The chain runs on explicit 2-vectors (v_pk_mul_f32 / v_pk_add_f32: two IEEE operations per issue slot, each rounded on its own)
 struct WidePrep
 {
-#if S2_WIDE_PACKED
 	// the anchors as the chain wants them: perp(r) = (-r.y, r.x).  crossSV(w, r) = w perp(r) and cross(r, P) = perp(r).x P.x +
 	// perp(r).y P.y, term for term the reference's products ((-a) b == -(a b), x - y == x + (-y)), so the chain needs no
 	// per-component sign and its 2-vector algebra packs without moves
 	f2 pA[2], pB[2];
-#else
-	V2 rA[2], rB[2];
-#endif
 	float bias[2];
 	uint32_t soft; // bit j: point j takes the soft mass / impulse scales
 };
@@ -250,32 +185,15 @@ S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lco
 	const V2 dcA = v2(dqA.x, dqA.y), dcB = v2(dqB.x, dqB.y);
 	Rot qA, qB;
 	qA.s = dqA.z, qA.c = dqA.w, qB.s = dqB.z, qB.c = dqB.w;
-#if S2_WIDE_PACKED && S2_WIDE_PACKED_PREP
-	const f2 q2A = hi2(dqA), q2B = hi2(dqB);
-	const f2 qnA = f2{-q2A.x, q2A.y}, qnB = f2{-q2B.x, q2B.y};
-	const f2 dd2 = lo2(dqB) - lo2(dqA);
-	const f2 n2 = f2{normal.x, normal.y};
-#endif
 	WidePrep pre;
 	pre.soft = 0u;
 #pragma unroll
 	for (int j = 0; j < 2; ++j)
 	{
-#if S2_WIDE_PACKED
 		pre.pA[j] = pre.pB[j] = f2{0.0f, 0.0f};
-#else
-		pre.rA[j] = pre.rB[j] = v2(0.0f, 0.0f);
-#endif
 		pre.bias[j] = 0.0f;
 		if (POINTS == 2 || j < pointCount)
 		{
-#if S2_WIDE_PACKED && S2_WIDE_PACKED_PREP
-			const f2 rA = rot2(q2A, qnA, p.lA[j]), rB = rot2(q2B, qnB, p.lB[j]);
-			pre.pA[j] = f2{-rA.y, rA.x}, pre.pB[j] = f2{-rB.y, rB.x};
-			const f2 ds2 = dd2 + (rB - rA); // add(sub(dcB, dcA), sub(rB, rA))
-			const f2 sn = ds2 * n2;
-			const float s = (sn.x + sn.y) + p.p0[j];
-#else
 			V2 lAj, lBj;
 			if constexpr (LL)
 			{
@@ -287,7 +205,6 @@ S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lco
 				lAj = asV2(p.lA[j]), lBj = asV2(p.lB[j]);
 			}
 			const V2 rA = wideIsPgs<KIND> ? v2(0.0f, 0.0f) : rotate(qA, lAj), rB = wideIsPgs<KIND> ? v2(0.0f, 0.0f) : rotate(qB, lBj);
-#if S2_WIDE_PACKED
 			if constexpr (wideLdsArms<KIND>)
 			{
 				// s2SolveContacts_TGS_Fixed (solve_soft_step.c:66-177): the separation from the anchors as the bodies stand now (below),
@@ -299,13 +216,8 @@ S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lco
 			{
 				pre.pA[j] = KIND == SOFT_PGS ? p.lA[j] : f2{-rA.y, rA.x}, pre.pB[j] = KIND == SOFT_PGS ? p.lB[j] : f2{-rB.y, rB.x};
 			}
-#else
-			static_assert(KIND == SOFT_TGS, "SOFT_PGS / SOFT_FIXED keep the packed chain's anchors");
-			pre.rA[j] = rA, pre.rB[j] = rB;
-#endif
 			const V2 ds = add(sub(dcB, dcA), sub(rB, rA));
 			const float s = wideIsPgs<KIND> ? p.p0[j] : dot(ds, normal) + p.p0[j];
-#endif
 			// select form of: if (s > 0) bias = s * inv_h; else if (useBias) {bias = max(biasCoefficient * s, cap); ...}
 			const bool speculative = s > 0.0f;
 			const bool soft = !speculative && useBias != 0;
@@ -317,7 +229,6 @@ S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lco
 	return pre;
 }
 
-#if S2_WIDE_PACKED
 S2_DEV float dot2(f2 a, f2 b) // a.x b.x + a.y b.y
 {
 	const f2 m = a * b;
@@ -408,85 +319,6 @@ template <int POINTS> S2_DEV void chainWide(WideRegs& p, const WidePrep& pre, fl
 		lvel[ib] = make_float4(vB.x, vB.y, wB, 0.0f);
 	}
 }
-#else
-template <int POINTS> S2_DEV void chainWide(WideRegs& p, const WidePrep& pre, float4* lvel, const float2* lmass, const float4* lcoef, uint32_t salt)
-{
-	const uint32_t idx = p.idx ^ salt;
-	const int ia = (int)(idx & 0x1fffu), ib = (int)((idx >> 13) & 0x1fffu);
-	const int pointCount = (int)((idx >> 26) & 3u);
-	const float4 velA = lvel[ia], velB = lvel[ib];
-	const float2 massA = lmass[ia], massB = lmass[ib];
-	const float4 sf = lcoef[(idx >> 30) & 1u];
-	const V2 normal = v2(fromBits(asBits(p.n.x) ^ salt), p.n.y);
-	const V2 tangent = rightPerp(normal);
-	const float mA = massA.x, iA = massA.y, mB = massB.x, iB = massB.y;
-	V2 vA = v2(velA.x, velA.y), vB = v2(velB.x, velB.y);
-	float wA = velA.z, wB = velB.z;
-	float nImp[2], tImp[2];
-
-#pragma unroll
-	for (int j = 0; j < 2; ++j)
-	{
-		if (POINTS == 2 || j < pointCount)
-		{
-			const V2 rA = pre.rA[j], rB = pre.rB[j];
-			const bool soft = (pre.soft >> j) & 1u;
-			const float massScale = soft ? sf.y : 1.0f;
-			const float impulseScale = soft ? sf.z : 0.0f;
-
-			const V2 vrB = add(vB, crossSV(wB, rB));
-			const V2 vrA = add(vA, crossSV(wA, rA));
-			const float vn = dot(sub(vrB, vrA), normal);
-
-			const float normalMass = fromBits(asBits(p.p1[j]) ^ salt);
-			const float old = p.imp[j].x;
-			float impulse = -normalMass * massScale * (vn + pre.bias[j]) - impulseScale * old;
-			const float newImpulse = S2_MAXF(old + impulse, 0.0f);
-			impulse = newImpulse - old;
-			nImp[j] = newImpulse;
-			tImp[j] = p.imp[j].y;
-
-			const V2 P = mulSV(impulse, normal);
-			vA = mulSub(vA, mA, P);
-			wA -= iA * cross(rA, P);
-			vB = mulAdd(vB, mB, P);
-			wB += iB * cross(rB, P);
-		}
-	}
-
-#pragma unroll
-	for (int j = 0; j < 2; ++j)
-	{
-		if (POINTS == 2 || j < pointCount)
-		{
-			const float tangentMass = fromBits(asBits(p.p2[j]) ^ salt);
-			const V2 rA = pre.rA[j], rB = pre.rB[j];
-			const V2 vrB = add(vB, crossSV(wB, rB));
-			const V2 vrA = add(vA, crossSV(wA, rA));
-			const float vt = dot(sub(vrB, vrA), tangent);
-			float impulse = -tangentMass * vt;
-			const float maxFriction = p.friction * nImp[j];
-			const float newImpulse = S2_CLAMPF(tImp[j] + impulse, -maxFriction, maxFriction);
-			impulse = newImpulse - tImp[j];
-			const V2 P = mulSV(impulse, tangent);
-			vA = mulSub(vA, mA, P);
-			wA -= iA * cross(rA, P);
-			vB = mulAdd(vB, mB, P);
-			wB += iB * cross(rB, P);
-			p.imp[j] = f2{nImp[j], newImpulse};
-		}
-	}
-
-	if ((idx & (1u << 28)) != 0)
-	{
-		lvel[ia] = make_float4(vA.x, vA.y, wA, 0.0f);
-	}
-	if ((idx & (1u << 29)) != 0)
-	{
-		lvel[ib] = make_float4(vB.x, vB.y, wB, 0.0f);
-	}
-}
-#endif
 
 S2_DEV void storeWide(const ContactView& c, const WideRegs& p, int k)
 {
@@ -505,11 +337,8 @@ S2_DEV void storeWide(const ContactView& c, const WideRegs& p, int k)
 // colour next to seven or eight interior ones): six 16-byte records per lane and round, field-major so that a wave reads
 // consecutive addresses; the impulses are a record of their own -- the only part a sweep writes back.
 #define S2_WIDE_PARKED_RECORDS 6
-// 1: the preps of the parked seam rounds run while the hand-off is in flight, like those of the rounds in registers.  Measured slower
-// on the wreck world (0.289 against 0.271 ms per churn step: 22 more live registers, 148-168 bytes of scratch instead of ~110): off
-#ifndef S2_WIDE_PARKED_PREP_EARLY
-#define S2_WIDE_PARKED_PREP_EARLY 0
-#endif
+// (The preps of the parked seam rounds run late, right before their chains: run while the hand-off is in flight, like those of the rounds in
+// registers, they measured slower on the wreck world -- 0.289 against 0.271 ms per churn step: 22 more live registers.)
 // (`stride`: the lanes of a parked round -- as many columns as its widest instance in any strip holds constraints: PersistView::parkSeamWidth / parkInteriorWidth)
 S2_DEV void parkWide(float4* slot, int stride, const WideRegs& p)
 {
@@ -899,19 +728,8 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 	constexpr int LL0 = NRES - LA; // the first such record (interior records 0 .. RPH - 1, then the seam records)
 	static_assert(LA >= 0 && LA <= NRES, "wideLocalsInLds");
 	const int tid = (int)threadIdx.x;
-#ifndef S2_WIDE_SPREAD_HALVES
-#define S2_WIDE_SPREAD_HALVES 0
-#endif
-#if S2_WIDE_SPREAD_HALVES
-	// (experiment, r4: the halves as waves {0, 1, 4, 5} / {2, 3, 6, 7}.  A CU deals its waves round-robin onto its four SIMDs and a
-	// round of a two-level strip holds ~100 constraints = the first two waves of a half, so with waves 0-3 / 4-7 the chain (waves 0, 1)
-	// and the prep (waves 4, 5) share SIMDs 0 and 1 while SIMDs 2 and 3 idle; this mapping gives each its own pair of SIMDs.  Measured
-	// at base 200: 129.7 against 130.3 us per launch -- nothing: a round is ONE wave's dependent instruction stream, 4 cycles an
-	// instruction, and a second wave on the same SIMD fills its stalls rather than lengthening it.  Bit-exact either way.)
-	const int half = (tid >> 7) & 1, ht = (tid & 127) | ((tid >> 8) << 7);
-#else
+	// (the halves as waves {0, 1, 4, 5} / {2, 3, 6, 7}, a pair of SIMDs each, measured the same: 129.7 against 130.3 us per launch at base 200)
 	const int half = tid >> 8, ht = tid & 255; // hand-offs: waves 0-3 serve the left neighbour, waves 4-7 the right
-#endif
 	// stamps: (wall_clock64 << 4) | tag; tags: 0 start, 1 loaded, 2 body stage, 3 warm start, 4 interior rounds, 5 hand-off, 6 seam rounds, 7 end
 	// (the workgroup that stamps: persist_debug bits 8-15 + 1, default one in the middle of the island)
 	const bool stamp = S2_PERSIST_INSTRUMENTED && pv.debugTimes != nullptr && tid == 0 &&
@@ -929,11 +747,11 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 	// strips [start(x), start(x) + count(x)).
 	const int K = (int)gridDim.x - (OVERFLOW ? 1 : 0);
 	const int xcd = (int)blockIdx.x & 7, lane8 = (int)blockIdx.x >> 3;
-	const int strip = S2_WIDE_XCD_AFFINE ? xcd * (K >> 3) + (xcd < (K & 7) ? xcd : (K & 7)) + lane8 : (int)blockIdx.x;
+	const int strip = xcd * (K >> 3) + (xcd < (K & 7) ? xcd : (K & 7)) + lane8;
 	// does this strip's left / right neighbour run on my XCD (by the same map)?
 	const int firstOfXcd = xcd * (K >> 3) + (xcd < (K & 7) ? xcd : (K & 7));
 	const int countOfXcd = (K >> 3) + (xcd < (K & 7) ? 1 : 0);
-	const bool nearAllowed = S2_WIDE_XCD_AFFINE && pv.nearHandoff != 0;
+	const bool nearAllowed = pv.nearHandoff != 0;
 	const bool hopeLeft = nearAllowed && strip > firstOfXcd, hopeRight = nearAllowed && strip + 1 < firstOfXcd + countOfXcd;
 	// The census: every workgroup publishes the XCD it REALLY runs on (write-through, once per launch), and a seam takes the
 	// L2 path only when both of its workgroups have read the same id from each other -- results never depend on placement.
@@ -952,7 +770,7 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 		}
 	}
 	gu64* census = (gu64*)pv.granules + pv.censusBase;
-	if (S2_WIDE_XCD_AFFINE && tid == 0)
+	if (tid == 0)
 	{
 		putGranule(census + strip, epoch0 + 1u, __uint_as_float(myXcc + 1u));
 	}
@@ -1755,16 +1573,6 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 					}
 				}
 			}
-			// (... and of the parked seam rounds: their records come out of LDS for it, and again for the chain)
-			WidePrep preP[SL > 0 ? SL : 1];
-#pragma unroll
-			for (int i = SR; i < ST; ++i)
-			{
-				if (S2_WIDE_PARKED_PREP_EARLY && ((seamMask >> i) & 1u))
-				{
-					preP[i - SR] = prepWide<RKP, POINTS>(unparkWide(lparked + (i - SR) * S2_WIDE_PARKED_RECORDS * sw, sw), ldq, lcoef, op.inv_h, op.useBias, salt);
-				}
-			}
 			int fail = 0;
 			if (ht < nImpH)
 			{
@@ -1826,15 +1634,8 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 					{
 						float4* slot = lparked + (i - SR) * S2_WIDE_PARKED_RECORDS * sw;
 						WideRegs p = unparkWide(slot, sw);
-						if (S2_WIDE_PARKED_PREP_EARLY)
-						{
-							chainWide<POINTS>(p, preP[i - SR < SL ? i - SR : 0], lvel, lmass, lcoef, salt);
-						}
-						else
-						{
-							const WidePrep late = prepWide<RKP, POINTS>(p, ldq, lcoef, op.inv_h, op.useBias, salt);
-							chainWide<POINTS>(p, late, lvel, lmass, lcoef, salt);
-						}
+						const WidePrep late = prepWide<RKP, POINTS>(p, ldq, lcoef, op.inv_h, op.useBias, salt);
+						chainWide<POINTS>(p, late, lvel, lmass, lcoef, salt);
 						slot[5 * sw] = make_float4(p.imp[0].x, p.imp[0].y, p.imp[1].x, p.imp[1].y);
 					}
 					__syncthreads();
@@ -1906,7 +1707,7 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 				p[0] = 0ull, p[1] = 0ull, p[2] = 0ull, p[3] = 0ull;
 			}
 		}
-		if (S2_WIDE_XCD_AFFINE && tid == 0)
+		if (tid == 0)
 		{
 			census[strip] = 0ull;
 		}
@@ -2057,225 +1858,126 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 	}
 }
 
-// (experiments: compile the headline variant's four modes only -- tools/kernel_ab.sh, register counts)
-#ifndef S2_WIDE_ONLY_MAIN
-#define S2_WIDE_ONLY_MAIN 0
-#endif
-#if S2_WIDE_ONLY_MAIN
-template __global__ void wideStepKernel<2, 3, 2, 0, 0, 0>(ContactView, BodyView, StripTableView, PersistView, const Op*, int, WideSelf);
-template __global__ void wideStepKernel<2, 3, 2, 0, 0, 1>(ContactView, BodyView, StripTableView, PersistView, const Op*, int, WideSelf);
-template __global__ void wideStepKernel<2, 3, 2, 0, 0, 2>(ContactView, BodyView, StripTableView, PersistView, const Op*, int, WideSelf);
-template __global__ void wideStepKernel<2, 3, 2, 0, 0, 3>(ContactView, BodyView, StripTableView, PersistView, const Op*, int, WideSelf);
-template __global__ void wideStepKernel<2, 3, 2, 0, 0, 8>(ContactView, BodyView, StripTableView, PersistView, const Op*, int, WideSelf);
-#else
 // Eligibility (checked by the caller, solver_executor.h widePlan): TGS_Soft with the current-anchor warm start on a partition with
 // at most 6 interior colour batches per strip and 3 per seam, or 8 and 2 (pv.maxRoundsA, pv.maxSeamRounds): five or six resident
 // records per lane fit its 256 registers beside the round's working set, seven do not (measured: 160 spilled registers).
-template <int RPH, int SR, int SL, int IL, int MODE, int KIND = SOFT_TGS>
-static void launchWideMode(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops, int opCount,
-						   const WideSelf& self)
+
+// Every instantiation that exists, by {POINTS, RPH, SR, SL, IL, MODE, KIND}: the five layouts in the plain, the sliced and the overflow form
+// for s2Solve_TGS_Soft and s2Solve_PGS_Soft; the <3, 2> layout alone for s2Solve_SoftStep (its record keeps rA0 / rB0 in LDS beside the TGS
+// record in registers, and a sixth such record fits neither) and for the two optional modes of s2Solve_TGS_Soft (the self-contained form
+// and the body-centric warm start -- measured no faster --: beside a sixth record or parked rounds they spilled up to 520 bytes per lane)
+typedef KernelVariant<7> WideVariant;
+template <int MODE, int KIND, int RPH, int SR, int SL, int IL, int POINTS> static void addWide(std::vector<WideVariant>& list)
 {
-	const dim3 block(S2_WIDE_THREADS);
-	if (pv.allTwoPoints)
-	{
-		wideStepKernel<2, RPH, SR, SL, IL, MODE, KIND><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount, self);
-	}
-	else
-	{
-		wideStepKernel<0, RPH, SR, SL, IL, MODE, KIND><<<grid, block, lds, s>>>(c, g, a, pv, ops, opCount, self);
-	}
+	list.push_back({{POINTS, RPH, SR, SL, IL, MODE, KIND}, (const void*)wideStepKernel<POINTS, RPH, SR, SL, IL, MODE, KIND>});
+}
+template <int MODE, int KIND, int RPH, int SR, int SL = 0, int IL = 0> static void addWidePoints(std::vector<WideVariant>& list)
+{
+	addWide<MODE, KIND, RPH, SR, SL, IL, 0>(list);
+	addWide<MODE, KIND, RPH, SR, SL, IL, 2>(list);
+}
+template <int KIND, int RPH, int SR, int SL = 0, int IL = 0> static void addWideForms(std::vector<WideVariant>& list)
+{
+	addWidePoints<0, KIND, RPH, SR, SL, IL>(list);
+	addWidePoints<S2_WIDE_SLICED, KIND, RPH, SR, SL, IL>(list);
+	addWidePoints<S2_WIDE_OVERFLOW, KIND, RPH, SR, SL, IL>(list);
+}
+template <int KIND> static void addWideLayouts(std::vector<WideVariant>& list)
+{
+	addWideForms<KIND, 3, 2>(list);
+	addWideForms<KIND, 3, 3>(list);
+	addWideForms<KIND, 4, 2>(list);
+	addWideForms<KIND, 3, 2, 2>(list);
+	addWideForms<KIND, 3, 2, 2, 2>(list);
+}
+static const std::vector<WideVariant>& wideVariants()
+{
+	static const std::vector<WideVariant> list = [] {
+		std::vector<WideVariant> v;
+		addWideLayouts<SOFT_TGS>(v);
+		addWideLayouts<SOFT_PGS>(v);
+		addWideForms<SOFT_FIXED, 3, 2>(v);
+		addWidePoints<S2_WIDE_SELF, SOFT_TGS, 3, 2>(v);
+		addWidePoints<S2_WIDE_BODYWARM, SOFT_TGS, 3, 2>(v);
+		// (both at once for manifolds of two points only: with per-point masking the combination spilled 24 bytes per lane)
+		addWide<S2_WIDE_SELF | S2_WIDE_BODYWARM, SOFT_TGS, 3, 2, 0, 0, 2>(v);
+		return v;
+	}();
+	return list;
 }
 
-// dynamic LDS beside the bodies, the ops and the three fixed records: parked rounds, the staged positions (self-contained), the
-// round masks and the term table of the body-centric warm start
-static size_t wideExtraLds(const PersistView& pv, int RPH, int SR, int SL, int IL, bool selfContained, bool bodyWarm, bool fixedArms = false, bool tgsLocals = false)
+// which variant takes the partition with these two features, or null: none
+static const WideVariant* wideVariant(int kind, const PersistView& pv, bool selfContained, bool bodyWarm)
 {
-	size_t records = (size_t)S2_WIDE_PARKED_RECORDS * ((size_t)SL * pv.parkSeamWidth + (size_t)IL * pv.parkInteriorWidth);
-	records += fixedArms ? (size_t)2 * (RPH + SR) * S2_WIDE_THREADS : 0; // SOFT_FIXED: {perp(rA0), perp(rB0)} per record, point and lane
-	records += tgsLocals ? (size_t)2 * wideLocalsInLds(RPH, SR, SL, IL, true) * S2_WIDE_THREADS : 0; // s2Solve_TGS_Soft: {lA, lB} of the records that keep them in LDS
-	records += selfContained ? (size_t)(pv.maxStaged + 1) / 2 : 0;
-	if (bodyWarm)
+	if (pv.maxRoundsA > 8 || pv.maxSeamRounds > 4)
+	{
+		return nullptr;
+	}
+	// the layout: <3, 2> unless the partition needs more rounds
+	const bool six = pv.maxRoundsA <= 6;
+	int rph = 3, sr = 2, sl = 0, il = 0;
+	if ((pv.debugSkip & 16) != 0 || pv.maxSeamRounds > 3 || (pv.maxSeamRounds > 2 && !six))
+	{
+		// seven or eight interior colours AND three or four seam colours -- a pile after an impact: six interior and two seam rounds in registers,
+		// the rest parked (the <4, 2, 2> layout of eight interior records per lane pair spilled 41 registers); debugSkip & 16: tests, the
+		// variants with parked rounds whatever the partition needs
+		sl = 2, il = six ? 0 : 2; // <3, 2, 2>, <3, 2, 2, 2>
+	}
+	else if (pv.maxSeamRounds > 2)
+	{
+		sr = 3; // <3, 3>
+	}
+	else if (!six)
+	{
+		rph = 4; // <4, 2>
+	}
+	// the mode: the two optional ones are s2Solve_TGS_Soft's; mixed point counts with both take the self-contained form with the coloured warm start
+	int mode = kind == SOFT_TGS ? (selfContained ? S2_WIDE_SELF : 0) | (bodyWarm ? S2_WIDE_BODYWARM : 0) : 0;
+	if (mode == (S2_WIDE_SELF | S2_WIDE_BODYWARM) && !pv.allTwoPoints)
+	{
+		mode = S2_WIDE_SELF;
+	}
+	if (mode == 0)
+	{
+		mode = pv.overflowKernel != 0 ? S2_WIDE_OVERFLOW : (pv.clearOwn != 0 ? S2_WIDE_SLICED : 0);
+	}
+	return findVariant(wideVariants(), {pv.allTwoPoints ? 2 : 0, rph, sr, sl, il, mode, kind});
+}
+
+// that variant's dynamic LDS: the bodies, the ops and the three fixed records (coefficients, census flags); parked rounds; the arms rA0 / rB0
+// or the local anchors of the records that keep them in LDS; the staged positions (self-contained); the round masks and the term table of the
+// body-centric warm start
+static size_t wideVariantLds(const WideVariant& v, const PersistView& pv, int opCount)
+{
+	const int RPH = v.arg[1], SR = v.arg[2], SL = v.arg[3], IL = v.arg[4], mode = v.arg[5], kind = v.arg[6];
+	size_t records = (size_t)pv.bodyRecords + 3;
+	records += (size_t)S2_WIDE_PARKED_RECORDS * ((size_t)SL * pv.parkSeamWidth + (size_t)IL * pv.parkInteriorWidth);
+	// SOFT_FIXED, SOFT_PGS: {perp(rA0), perp(rB0)} per record, point and lane; s2Solve_TGS_Soft: {lA, lB} of the records that keep them in LDS
+	records += (size_t)2 * (kind != SOFT_TGS ? RPH + SR : wideLocalsInLds(RPH, SR, SL, IL, true)) * S2_WIDE_THREADS;
+	records += (mode & S2_WIDE_SELF) != 0 ? (size_t)(pv.maxStaged + 1) / 2 : 0;
+	if ((mode & S2_WIDE_BODYWARM) != 0)
 	{
 		const size_t tw = (size_t)pv.maxStripBodies, rounds = (size_t)(2 * RPH + SR);
 		records += (tw + 3) / 4 + (3 * rounds * tw + 1) / 2;
 	}
-	return records * sizeof(float4);
+	return records * sizeof(float4) + (size_t)opCount * sizeof(Op);
 }
 
-template <int RPH, int SR, int SL = 0, int IL = 0>
-static void launchWide(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops, int opCount,
-					   const WideSelf* self, int kind)
+size_t wideStepLds(int kind, const PersistView& pv, int opCount, bool selfContained, bool bodyWarm)
 {
-	if (kind == SOFT_FIXED)
-	{
-		// s2Solve_SoftStep: the <3, 2> layout (wideVariant) -- its record keeps rA0 / rB0 in LDS beside the TGS record in registers, and a
-		// sixth such record fits neither
-		if constexpr (RPH == 3 && SR == 2 && SL == 0 && IL == 0)
-		{
-			const WideSelf none{};
-			lds += wideExtraLds(pv, RPH, SR, SL, IL, false, false, true);
-			if (pv.overflowKernel != 0)
-			{
-				launchWideMode<RPH, SR, SL, IL, S2_WIDE_OVERFLOW, SOFT_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-			}
-			else if (pv.clearOwn != 0)
-			{
-				launchWideMode<RPH, SR, SL, IL, S2_WIDE_SLICED, SOFT_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-			}
-			else
-			{
-				launchWideMode<RPH, SR, SL, IL, 0, SOFT_FIXED>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-			}
-		}
-		return;
-	}
-	if (kind == SOFT_PGS)
-	{
-		// s2Solve_PGS_Soft: the plain form only (prologue and epilogue launches, the coloured warm start); rA0 / rB0 in LDS where no round is parked
-		const WideSelf none{};
-		lds += wideExtraLds(pv, RPH, SR, SL, IL, false, false, true);
-		if (pv.overflowKernel != 0)
-		{
-			launchWideMode<RPH, SR, SL, IL, S2_WIDE_OVERFLOW, SOFT_PGS>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-		}
-		else if (pv.clearOwn != 0)
-		{
-			launchWideMode<RPH, SR, SL, IL, S2_WIDE_SLICED, SOFT_PGS>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-		}
-		else
-		{
-			launchWideMode<RPH, SR, SL, IL, 0, SOFT_PGS>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-		}
-		return;
-	}
-	// (the self-contained form and the body-centric warm start -- options, measured no faster -- exist for the <3, 2> layout: beside a
-	// sixth record or parked rounds they spilled up to 520 bytes per lane: wideExtraRecords says so to the caller)
-	constexpr bool OPTIONAL_MODES = RPH == 3 && SR == 2 && SL == 0 && IL == 0;
-	const bool selfContained = OPTIONAL_MODES && self != nullptr;
-	const bool bodyWarm = OPTIONAL_MODES && pv.bodyWarm != 0;
-	lds += wideExtraLds(pv, RPH, SR, SL, IL, selfContained, bodyWarm, false, true);
-	const WideSelf none{};
-	if constexpr (OPTIONAL_MODES)
-	{
-		if (selfContained && bodyWarm && pv.allTwoPoints)
-		{
-			// (both at once for manifolds of two points only: with per-point masking the combination spilled 24 bytes per lane; mixed
-			// point counts take the self-contained form with the coloured warm start)
-			wideStepKernel<2, RPH, SR, SL, IL, S2_WIDE_SELF | S2_WIDE_BODYWARM><<<grid, dim3(S2_WIDE_THREADS), lds, s>>>(c, g, a, pv, ops, opCount, *self);
-			return;
-		}
-		if (bodyWarm && !selfContained)
-		{
-			launchWideMode<RPH, SR, SL, IL, S2_WIDE_BODYWARM>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-			return;
-		}
-	}
-	if constexpr (OPTIONAL_MODES)
-	{
-		if (selfContained)
-		{
-			launchWideMode<RPH, SR, SL, IL, S2_WIDE_SELF>(s, grid, lds, c, g, a, pv, ops, opCount, *self);
-			return;
-		}
-	}
-	{
-		if (pv.overflowKernel != 0)
-		{
-			launchWideMode<RPH, SR, SL, IL, S2_WIDE_OVERFLOW>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-		}
-		else if (pv.clearOwn != 0)
-		{
-			launchWideMode<RPH, SR, SL, IL, S2_WIDE_SLICED>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-		}
-		else
-		{
-			launchWideMode<RPH, SR, SL, IL, 0>(s, grid, lds, c, g, a, pv, ops, opCount, none);
-		}
-	}
-}
-
-// which variant takes the partition: RPH/SR/SL/IL as an index 0..4, -1: none
-static int wideVariant(const PersistView& pv)
-{
-	if (pv.maxRoundsA > 8 || pv.maxSeamRounds > 4)
-	{
-		return -1;
-	}
-	const bool park = (pv.debugSkip & 16) != 0; // tests: the variants with parked seam rounds whatever the partition needs
-	if (park)
-	{
-		return pv.maxRoundsA <= 6 ? 3 : 4;
-	}
-	if (pv.maxRoundsA <= 6 && pv.maxSeamRounds <= 2)
-	{
-		return 0; // <3, 2>
-	}
-	if (pv.maxRoundsA <= 6 && pv.maxSeamRounds <= 3)
-	{
-		return 1; // <3, 3>
-	}
-	if (pv.maxSeamRounds <= 2)
-	{
-		return 2; // <4, 2>
-	}
-	// (seven or eight interior colours AND three or four seam colours -- a pile after an impact: six interior and two seam rounds in
-	// registers, the rest parked -- the <4, 2, 2> layout of eight interior records per lane pair spilled 41 registers)
-	return pv.maxRoundsA <= 6 ? 3 : 4; // <3, 2, 2>, <3, 2, 2, 2>
-}
-
-// records of dynamic LDS the variant for this partition needs beside the bodies, the ops and the three fixed records; -1: no variant
-// takes that partition (Executor::widePlan)
-int wideExtraRecords(const PersistView& pv, int selfContained, int bodyWarm, int kind)
-{
-	static const int shape[5][4] = {{3, 2, 0, 0}, {3, 3, 0, 0}, {4, 2, 0, 0}, {3, 2, 2, 0}, {3, 2, 2, 2}};
-	const int v = wideVariant(pv);
-	if (v < 0 || (kind == SOFT_FIXED && v > 0) || ((selfContained != 0 || bodyWarm != 0) && v > 0))
-	{
-		return -1; // (s2Solve_SoftStep, the self-contained form and the body-centric warm start: the <3, 2> layout only)
-	}
-	if (kind == SOFT_FIXED)
-	{
-		return (int)(wideExtraLds(pv, shape[v][0], shape[v][1], 0, 0, false, false, true) / sizeof(float4));
-	}
-	if (kind == SOFT_PGS)
-	{
-		return (int)(wideExtraLds(pv, shape[v][0], shape[v][1], shape[v][2], shape[v][3], false, false, true) / sizeof(float4));
-	}
-	const bool warm = bodyWarm != 0 && shape[v][2] == 0 && shape[v][3] == 0;
-	return (int)(wideExtraLds(pv, shape[v][0], shape[v][1], shape[v][2], shape[v][3], selfContained != 0, warm, false, true) / sizeof(float4));
-}
-
-// ... and whether that variant has the body-centric warm start at all (the parked ones keep the coloured sweep)
-int wideBodyWarmVariant(const PersistView& pv)
-{
-	const int v = wideVariant(pv);
-	return v == 0 ? 1 : 0;
+	const WideVariant* v = wideVariant(kind, pv, selfContained, bodyWarm);
+	return v != nullptr ? wideVariantLds(*v, pv, opCount) : 0;
 }
 
 void launchWideStep(hipStream_t s, int kind, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops, int opCount, const WideSelf* self)
 {
-	const dim3 grid((unsigned)a.groupCount + (pv.overflowKernel != 0 ? 1u : 0u)); // (+ the overflow workgroup: wideOverflowWorker)
-	const size_t lds = (size_t)(pv.bodyRecords + 3) * sizeof(float4) + (size_t)opCount * sizeof(Op);
-	switch (wideVariant(pv))
+	const WideVariant* v = wideVariant(kind, pv, self != nullptr, pv.bodyWarm != 0);
+	if (v == nullptr)
 	{
-		case 0:
-			launchWide<3, 2>(s, grid, lds, c, g, a, pv, ops, opCount, self, kind);
-			break;
-		case 1:
-			launchWide<3, 3>(s, grid, lds, c, g, a, pv, ops, opCount, self, kind);
-			break;
-		case 2:
-			launchWide<4, 2>(s, grid, lds, c, g, a, pv, ops, opCount, self, kind);
-			break;
-		case 3:
-			launchWide<3, 2, 2>(s, grid, lds, c, g, a, pv, ops, opCount, self, kind);
-			break;
-		case 4:
-			launchWide<3, 2, 2, 2>(s, grid, lds, c, g, a, pv, ops, opCount, self, kind);
-			break;
-		default:
-			break;
+		return;
 	}
+	const dim3 grid((unsigned)a.groupCount + (pv.overflowKernel != 0 ? 1u : 0u)); // (+ the overflow workgroup: wideOverflowWorker)
+	launchVariant(*v, grid, dim3(S2_WIDE_THREADS), wideVariantLds(*v, pv, opCount), s, c, g, a, pv, ops, opCount, (v->arg[5] & S2_WIDE_SELF) != 0 ? *self : WideSelf{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2302,167 +2004,379 @@ constexpr int wideIslandLocalsInLds(int ROUNDS) { return ROUNDS > S2_STRIP_ROUND
 //              (warm start, impulses): 30 dwords.  The arms of ALL six records wait in LDS ({perp(rA0), perp(rB0)} per point and lane, as
 //              wideStepKernel's larms), the local anchors stay in the record.  There is no eight-round variant: with eight records' arms
 //              in LDS (128 KB) the local anchors of eight records in registers are the 22-dword x 8 case that spilled for TGS, and both
-//              in LDS do not fit beside the bodies -- such a world stays on islandStepKernel (wideIslandForm).
+//              in LDS do not fit beside the bodies -- such a world stays on islandStepKernel (wideIslandVariants).
 constexpr int wideIslandArmsInLds(int KIND, int ROUNDS) { return KIND == SOFT_FIXED ? ROUNDS : (KIND == SOFT_PGS && ROUNDS > S2_STRIP_ROUNDS ? 7 : 0); }
-int wideIslandForm(int kind, int maxRounds) { return (kind == SOFT_TGS || kind == SOFT_PGS || (kind == SOFT_FIXED && maxRounds <= S2_STRIP_ROUNDS)) ? 1 : 0; }
-int wideIslandLocalRecords(int maxRounds, int kind)
-{
-	const int rounds = maxRounds > S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS_MAX : S2_STRIP_ROUNDS;
-	return 2 * (kind == SOFT_TGS ? wideIslandLocalsInLds(rounds) : wideIslandArmsInLds(kind, rounds)) * S2_WIDE_THREADS;
-}
-
-template <int ROUNDS, bool SELF, int POINTS>
+template <int KIND, int ROUNDS, bool SELF, int POINTS>
 __global__ __launch_bounds__(S2_WIDE_THREADS) void wideIslandKernel(ContactView c, BodyView g, StripTableView ta, float4 softCoef0, float4 softCoef1, const Op* ops,
 																	 int opCount, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart,
 																	 StepConsts sc, float unpackH, const unsigned int* stepFailed)
 {
-	constexpr int KIND = SOFT_TGS;
-#include "wide_island_body.h"
-}
-// ... for s2Solve_SoftStep (KIND = SOFT_FIXED: six rounds) and s2Solve_PGS_Soft (SOFT_PGS: six and eight)
-template <int KIND, int ROUNDS, bool SELF, int POINTS>
-__global__ __launch_bounds__(S2_WIDE_THREADS) void wideIslandKernelOf(ContactView c, BodyView g, StripTableView ta, float4 softCoef0, float4 softCoef1, const Op* ops,
-																		 int opCount, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart,
-																		 StepConsts sc, float unpackH, const unsigned int* stepFailed)
-{
-#include "wide_island_body.h"
+	// (the body stays in the __global__ function: as a forced-inline __device__ function the kernel parameters become values with an address --
+	// the two coefficient records went through a 48-byte private frame and the eight-round TGS_Soft variants spilled one or two VGPRs)
+	static_assert(KIND == SOFT_TGS || KIND == SOFT_PGS || (KIND == SOFT_FIXED && ROUNDS <= S2_STRIP_ROUNDS), "wideIslandVariants");
+	extern __shared__ __attribute__((aligned(16))) float4 lds[];
+	if (stepFailed != nullptr && *stepFailed != 0u)
+	{
+		return; // a persistent strip kernel of this step lost a hand-off: the step will be repeated, nothing of it may reach the wire arrays
+	}
+	const int tid = (int)threadIdx.x;
+	const StripDesc* da = ta.descs + blockIdx.x;
+	const int bodyBase = da->bodyBase, nb = da->bodyCount, roundsA = da->batchCount;
+	int2 batchA[ROUNDS];
+#pragma unroll
+	for (int i = 0; i < ROUNDS; ++i)
+	{
+		batchA[i] = make_int2(da->batch[i].x, da->batch[i].y);
+	}
+	float4* lvel = lds;
+	float4* ldq = lds + nb;
+	float4* linteg = lds + 2 * nb;
+	float* langDamp = (float*)(lds + 3 * nb);
+	float2* lmass = (float2*)(lds + 3 * nb + (nb + 3) / 4);
+	float2* llc = (float2*)(lds + 3 * nb + (nb + 3) / 4 + (nb + 1) / 2); // the bodies' local centres (soft_from_wire.h: prepareSoftFromWire)
+	const int bodyRecords = 3 * nb + (nb + 3) / 4 + 2 * ((nb + 1) / 2);
+	Op* lops = (Op*)(lds + bodyRecords);
+	float4* lcoef = lds + bodyRecords + 2 * opCount; // 2 records (the launch adds them to the size)
+	constexpr int LA = KIND == SOFT_TGS ? wideIslandLocalsInLds(ROUNDS) : 0, LL0 = ROUNDS - LA;
+	float4* llocals = lcoef + 2 + tid; // [record - LL0][point][lane] {lA, lB}
+	auto localsOf = [&](int r) { return llocals + 2 * (r - LL0 > 0 ? r - LL0 : 0) * S2_WIDE_THREADS; };
+	// ... or, for the other kinds, the arms of the records from AL0 on (never both: wideIslandLds): [record - AL0][point][lane] {perp(rA0), perp(rB0)}
+	constexpr int AA = wideIslandArmsInLds(KIND, ROUNDS), AL0 = ROUNDS - AA;
+	constexpr int AK = KIND == SOFT_PGS ? S2_WIDE_PGS_ARMS : KIND; // the kind of a record whose arms are in LDS
+	auto armsOf = [&](int r) { return llocals + 2 * (r - AL0 > 0 ? r - AL0 : 0) * S2_WIDE_THREADS; };
+
+	uint32_t id[S2_STRIP_BODY_CHUNKS];
+#pragma unroll
+	for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
+	{
+		const int i = tid + ch * S2_WIDE_THREADS;
+		id[ch] = i < nb ? (uint32_t)ta.bodyIds[bodyBase + i] : 0u;
+	}
+	for (int i = tid; i < opCount * 8; i += S2_WIDE_THREADS)
+	{
+		((int*)lops)[i] = ((const int*)ops)[i];
+	}
+	if (tid < 2)
+	{
+		lcoef[tid] = tid ? softCoef1 : softCoef0;
+	}
+	auto kOfRound = [&](int i) {
+		const int k = batchA[i].x + tid;
+		return (i < roundsA && k < batchA[i].y) ? k : -1;
+	};
+	// this thread's constraints: pool slot and group-local body slots (the wire records follow once the bodies are staged)
+	int slotOf[ROUNDS];
+	int2 localOf[ROUNDS];
+#pragma unroll
+	for (int i = 0; i < ROUNDS; ++i)
+	{
+		slotOf[i] = -1;
+		localOf[i] = make_int2(0, 0);
+		if (kOfRound(i) >= 0)
+		{
+			slotOf[i] = c.contactIndex[kOfRound(i)];
+			localOf[i] = c.localBodies[kOfRound(i)];
+		}
+	}
+	uint32_t flags[S2_STRIP_BODY_CHUNKS];
+	float2 pos[S2_STRIP_BODY_CHUNKS]; // SELF: the positions of the bodies this lane stages (s2FinalizePositions adds to them)
+#pragma unroll
+	for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
+	{
+		const int i = tid + ch * S2_WIDE_THREADS;
+		flags[ch] = 0u;
+		pos[ch] = make_float2(0.0f, 0.0f);
+		if (i < nb)
+		{
+			const int gi = (int)(id[ch] & ~S2G_OWNED);
+			if constexpr (SELF)
+			{
+				// body_ops.h: unpackBodyOne, into LDS instead of the SoA arrays
+				const s2amdBody* w = wireBodies + gi;
+				const int type = w->type;
+				uint32_t f = 0x80000000u;
+				if (type != S2AMD_BODY_FREE)
+				{
+					f |= S2F_LIVE | (type == S2AMD_BODY_DYNAMIC ? S2F_DYNAMIC : 0u) | (type != S2AMD_BODY_STATIC ? S2F_MOVES : 0u);
+				}
+				flags[ch] = f;
+				lvel[i] = make_float4(w->linearVelocity[0], w->linearVelocity[1], w->angularVelocity, 0.0f);
+				ldq[i] = make_float4(w->deltaPosition[0], w->deltaPosition[1], w->rot[0], w->rot[1]);
+				pos[ch] = make_float2(w->position[0], w->position[1]);
+				lmass[i] = make_float2(w->invMass, w->invI);
+				llc[i] = make_float2(w->localCenter[0], w->localCenter[1]);
+				const V2 gravity = v2(sc.gravityX, sc.gravityY);
+				const V2 force = v2(w->force[0], w->force[1]);
+				const V2 inner = mulAdd(force, w->mass * w->gravityScale, gravity);
+				const V2 a = mulSV(unpackH * w->invMass, inner);
+				const float aw = unpackH * w->invI * w->torque;
+				const float ld = 1.0f / (1.0f + unpackH * w->linearDamping);
+				const float ad = 1.0f / (1.0f + unpackH * w->angularDamping);
+				linteg[i] = make_float4(a.x, a.y, aw, ld);
+				langDamp[i] = ad;
+			}
+			else
+			{
+				lvel[i] = g.vel[gi];
+				ldq[i] = g.dq[gi];
+				flags[ch] = g.flags[gi] | 0x80000000u;
+				linteg[i] = g.integ[gi];
+				langDamp[i] = g.angDamp[gi];
+				lmass[i] = g.massInv[gi];
+				llc[i] = make_float2(wireBodies[gi].localCenter[0], wireBodies[gi].localCenter[1]);
+			}
+		}
+	}
+	__syncthreads();
+
+	LdsBodies lb{lvel, ldq};
+	WideRegs rA[ROUNDS];
+#pragma unroll
+	for (int i = 0; i < ROUNDS; ++i)
+	{
+		if (slotOf[i] >= 0)
+		{
+			const SoftRegs<KIND> t = prepareSoftFromWire<KIND>(wire + slotOf[i], wireBodies, hostFlags, lb, lmass, localOf[i], g.capacity, warmStart, llc);
+			rA[i] = wideFromSoft<KIND>(t);
+			const bool st = lmass[localOf[i].x].x == 0.0f || lmass[localOf[i].y].x == 0.0f; // the doubled contact hertz of a static side
+			rA[i].idx |= st ? 1u << 30 : 0u;
+			if (i >= LL0)
+			{
+#pragma unroll
+				for (int j = 0; j < 2; ++j)
+				{
+					localsOf(i)[j * S2_WIDE_THREADS] = make_float4(rA[i].lA[j].x, rA[i].lA[j].y, rA[i].lB[j].x, rA[i].lB[j].y);
+				}
+			}
+			if (AA > 0 && i >= AL0)
+			{
+#pragma unroll
+				for (int j = 0; j < 2; ++j)
+				{
+					armsOf(i)[j * S2_WIDE_THREADS] = wideArmsOf(t.r0[j]);
+				}
+			}
+		}
+	}
+	for (int oi = 0; oi < opCount; ++oi)
+	{
+		const Op op = lops[oi];
+		uint32_t salt;
+		asm volatile("s_mov_b32 %0, 0" : "=s"(salt));
+		if (op.code == OP_INTEGRATE_VEL)
+		{
+#pragma unroll
+			for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
+			{
+				if ((flags[ch] & S2F_DYNAMIC) != 0)
+				{
+					const int i = tid + ch * S2_WIDE_THREADS;
+					float4 v = lvel[i], k = linteg[i];
+					V2 lv = add(v2(v.x, v.y), v2(k.x, k.y));
+					float w = v.z + k.z;
+					lv = mulSV(k.w, lv);
+					w *= langDamp[i];
+					lvel[i] = make_float4(lv.x, lv.y, w, 0.0f);
+				}
+			}
+			__syncthreads();
+		}
+		else if (op.code == OP_INTEGRATE_POS)
+		{
+#pragma unroll
+			for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
+			{
+				if ((flags[ch] & S2F_MOVES) != 0)
+				{
+					const int i = tid + ch * S2_WIDE_THREADS;
+					float4 v = lvel[i], d = ldq[i];
+					V2 dpos = mulAdd(v2(d.x, d.y), op.h, v2(v.x, v.y));
+					Rot q;
+					q.s = d.z, q.c = d.w;
+					q = integrateRot(q, op.h * v.z);
+					ldq[i] = make_float4(dpos.x, dpos.y, q.s, q.c);
+				}
+			}
+			__syncthreads();
+		}
+		else if (op.code == OP_FINALIZE)
+		{
+#pragma unroll
+			for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
+			{
+				if constexpr (SELF)
+				{
+					// s2FinalizePositions (solve_common.c:70-91; body_ops.h: finalizePositionsOne) on the lane's own copy of the position
+					if ((flags[ch] & (op.flag ? S2F_DYNAMIC : S2F_MOVES)) != 0)
+					{
+						const int i = tid + ch * S2_WIDE_THREADS;
+						const float4 d = ldq[i];
+						const V2 np = add(v2(pos[ch].x, pos[ch].y), v2(d.x, d.y));
+						pos[ch] = make_float2(np.x, np.y);
+						ldq[i] = make_float4(0.0f, 0.0f, d.z, d.w);
+					}
+				}
+				else if (flags[ch] != 0u)
+				{
+					finalizePositionsOne(lb, tid + ch * S2_WIDE_THREADS, g, (int)(id[ch] & ~S2G_OWNED), op.flag, (id[ch] & S2G_OWNED) != 0);
+				}
+			}
+			__syncthreads();
+		}
+		else if (op.code == OP_WARM)
+		{
+#pragma unroll
+			for (int i = 0; i < ROUNDS; ++i)
+			{
+				if (i < roundsA)
+				{
+					if (kOfRound(i) >= 0)
+					{
+						if (i >= LL0)
+						{
+							warmWide<KIND, POINTS, true>(rA[i], lvel, ldq, lmass, salt, nullptr, localsOf(i));
+						}
+						else if (AA > 0 && i >= AL0)
+						{
+							warmWide<AK, POINTS>(rA[i], lvel, ldq, lmass, salt, armsOf(i));
+						}
+						else
+						{
+							warmWide<KIND, POINTS>(rA[i], lvel, ldq, lmass, salt);
+						}
+					}
+					__syncthreads();
+				}
+			}
+		}
+		else if (op.code == OP_SOLVE_SOFT)
+		{
+#pragma unroll
+			for (int i = 0; i < ROUNDS; ++i)
+			{
+				if (i < roundsA)
+				{
+					if (kOfRound(i) >= 0)
+					{
+						const WidePrep pre = (i >= LL0)				? prepWide<KIND, POINTS, true>(rA[i], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(i))
+											 : (AA > 0 && i >= AL0) ? prepWide<AK, POINTS>(rA[i], ldq, lcoef, op.inv_h, op.useBias, salt, armsOf(i))
+																	: prepWide<KIND, POINTS>(rA[i], ldq, lcoef, op.inv_h, op.useBias, salt);
+						chainWide<POINTS>(rA[i], pre, lvel, lmass, lcoef, salt);
+					}
+					__syncthreads();
+				}
+			}
+		}
+	}
+#pragma unroll
+	for (int ch = 0; ch < S2_STRIP_BODY_CHUNKS; ++ch)
+	{
+		const int i = tid + ch * S2_WIDE_THREADS;
+		if (i < nb && (id[ch] & S2G_OWNED) != 0)
+		{
+			const int gi = (int)(id[ch] & ~S2G_OWNED);
+			if constexpr (SELF)
+			{
+				if ((flags[ch] & S2F_LIVE) != 0) // body_ops.h: packBodyOne
+				{
+					s2amdBody* w = wireBodies + gi;
+					const float4 v = lvel[i], d = ldq[i];
+					w->position[0] = pos[ch].x, w->position[1] = pos[ch].y;
+					w->rot[0] = d.z, w->rot[1] = d.w;
+					w->linearVelocity[0] = v.x, w->linearVelocity[1] = v.y;
+					w->angularVelocity = v.z;
+					w->deltaPosition[0] = d.x, w->deltaPosition[1] = d.y;
+				}
+			}
+			else
+			{
+				g.vel[gi] = lvel[i];
+				g.dq[gi] = ldq[i];
+			}
+		}
+	}
+	// s2StoreContactImpulses (solve_common.c:396-410): straight into the manifolds
+#pragma unroll
+	for (int i = 0; i < ROUNDS; ++i)
+	{
+		if (slotOf[i] >= 0)
+		{
+			const int pointCount = (int)((rA[i].idx >> 26) & 3u);
+			s2amdContact* contact = wire + slotOf[i];
+#pragma unroll
+			for (int j = 0; j < 2; ++j)
+			{
+				if (j < pointCount)
+				{
+					contact->points[j].normalImpulse = rA[i].imp[j].x;
+					contact->points[j].tangentImpulse = rA[i].imp[j].y;
+				}
+			}
+		}
+	}
 }
 
-// t.ldsRecords: body records of the largest group; maxRounds: colour rounds of the group with the most
-template <int KIND, int ROUNDS>
-static void launchWideIslandRounds(hipStream_t s, dim3 grid, size_t lds, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef,
-								   const Op* ops, int opCount, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const StepConsts& sc,
-								   float unpackH, int selfContained, const unsigned int* stepFailed, int allTwoPoints)
+// Every instantiation that exists, by {KIND, ROUNDS, SELF, POINTS}: six and eight rounds for s2Solve_TGS_Soft and s2Solve_PGS_Soft, six for s2Solve_SoftStep
+typedef KernelVariant<4> WideIslandVariant;
+template <int KIND, int ROUNDS> static void addWideIslands(std::vector<WideIslandVariant>& list)
 {
-#define S2_LAUNCH_ISLAND(SELF, POINTS)                                                                                                                             \
-	if constexpr (KIND == SOFT_TGS)                                                                                                                                \
-	{                                                                                                                                                              \
-		wideIslandKernel<ROUNDS, SELF, POINTS>                                                                                                                     \
-			<<<grid, dim3(S2_WIDE_THREADS), lds, s>>>(c, g, t, softCoef[0], softCoef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed); \
-	}                                                                                                                                                              \
-	else                                                                                                                                                           \
-	{                                                                                                                                                              \
-		wideIslandKernelOf<KIND, ROUNDS, SELF, POINTS>                                                                                                           \
-			<<<grid, dim3(S2_WIDE_THREADS), lds, s>>>(c, g, t, softCoef[0], softCoef[1], ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed); \
-	}
-	if (selfContained)
-	{
-		if (allTwoPoints)
-		{
-			S2_LAUNCH_ISLAND(true, 2);
-		}
-		else
-		{
-			S2_LAUNCH_ISLAND(true, 0);
-		}
-	}
-	else if (allTwoPoints)
-	{
-		S2_LAUNCH_ISLAND(false, 2);
-	}
-	else
-	{
-		S2_LAUNCH_ISLAND(false, 0);
-	}
-#undef S2_LAUNCH_ISLAND
+	list.push_back({{KIND, ROUNDS, 0, 0}, (const void*)wideIslandKernel<KIND, ROUNDS, false, 0>});
+	list.push_back({{KIND, ROUNDS, 1, 0}, (const void*)wideIslandKernel<KIND, ROUNDS, true, 0>});
+	list.push_back({{KIND, ROUNDS, 0, 2}, (const void*)wideIslandKernel<KIND, ROUNDS, false, 2>});
+	list.push_back({{KIND, ROUNDS, 1, 2}, (const void*)wideIslandKernel<KIND, ROUNDS, true, 2>});
+}
+static const std::vector<WideIslandVariant>& wideIslandVariants()
+{
+	static const std::vector<WideIslandVariant> list = [] {
+		std::vector<WideIslandVariant> v;
+		addWideIslands<SOFT_TGS, S2_STRIP_ROUNDS>(v);
+		addWideIslands<SOFT_TGS, S2_STRIP_ROUNDS_MAX>(v);
+		addWideIslands<SOFT_PGS, S2_STRIP_ROUNDS>(v);
+		addWideIslands<SOFT_PGS, S2_STRIP_ROUNDS_MAX>(v);
+		addWideIslands<SOFT_FIXED, S2_STRIP_ROUNDS>(v);
+		return v;
+	}();
+	return list;
 }
 
-// kind: SOFT_TGS, SOFT_PGS or SOFT_FIXED, in a form that exists (wideIslandForm: Executor::wideIslandPlan has asked)
+// maxRounds: colour rounds of the group with the most
+static const WideIslandVariant* wideIslandVariant(int kind, int maxRounds, bool selfContained, bool allTwoPoints)
+{
+	return findVariant(wideIslandVariants(), {kind, maxRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX, selfContained ? 1 : 0, allTwoPoints ? 2 : 0});
+}
+
+// ldsRecords: body records of the largest group (StripTableView::ldsRecords)
+size_t wideIslandLds(int kind, int maxRounds, int ldsRecords, int opCount)
+{
+	const WideIslandVariant* v = wideIslandVariant(kind, maxRounds, false, false);
+	if (v == nullptr)
+	{
+		return 0;
+	}
+	// per-lane {lA, lB} of the records whose local anchors wait in LDS (s2Solve_TGS_Soft) or {perp(rA0), perp(rB0)} of those whose arms do (never both)
+	const int perLane = kind == SOFT_TGS ? wideIslandLocalsInLds(v->arg[1]) : wideIslandArmsInLds(kind, v->arg[1]);
+	return (size_t)(ldsRecords + 2 + 2 * perLane * S2_WIDE_THREADS) * sizeof(float4) + (size_t)opCount * sizeof(Op);
+}
+
+// kind: SOFT_TGS, SOFT_PGS or SOFT_FIXED, in a form that exists (Executor::wideIslandPlan has asked wideIslandLds)
 void launchWideIsland(hipStream_t s, int kind, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops, int opCount,
 					  int maxRounds, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const StepConsts& sc, float unpackH,
 					  int selfContained, const unsigned int* stepFailed, int allTwoPoints)
 {
-	const dim3 grid((unsigned)t.groupCount);
-	const size_t lds = (size_t)(t.ldsRecords + 2 + wideIslandLocalRecords(maxRounds, kind)) * sizeof(float4) + (size_t)opCount * sizeof(Op);
-#define S2_ISLAND_ROUNDS(KIND, ROUNDS) \
-	launchWideIslandRounds<KIND, ROUNDS>(s, grid, lds, c, g, t, softCoef, ops, opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, selfContained, stepFailed, allTwoPoints)
-	if (kind == SOFT_FIXED)
+	const WideIslandVariant* v = wideIslandVariant(kind, maxRounds, selfContained != 0, allTwoPoints != 0);
+	if (v == nullptr)
 	{
-		if (maxRounds <= S2_STRIP_ROUNDS)
-		{
-			S2_ISLAND_ROUNDS(SOFT_FIXED, S2_STRIP_ROUNDS);
-		}
+		return;
 	}
-	else if (kind == SOFT_PGS)
-	{
-		if (maxRounds <= S2_STRIP_ROUNDS)
-		{
-			S2_ISLAND_ROUNDS(SOFT_PGS, S2_STRIP_ROUNDS);
-		}
-		else
-		{
-			S2_ISLAND_ROUNDS(SOFT_PGS, S2_STRIP_ROUNDS_MAX);
-		}
-	}
-	else if (maxRounds <= S2_STRIP_ROUNDS)
-	{
-		S2_ISLAND_ROUNDS(SOFT_TGS, S2_STRIP_ROUNDS);
-	}
-	else
-	{
-		S2_ISLAND_ROUNDS(SOFT_TGS, S2_STRIP_ROUNDS_MAX);
-	}
-#undef S2_ISLAND_ROUNDS
+	launchVariant(*v, dim3((unsigned)t.groupCount), dim3(S2_WIDE_THREADS), wideIslandLds(kind, maxRounds, t.ldsRecords, opCount), s, c, g, t, softCoef[0], softCoef[1], ops,
+				  opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed);
 }
 
 int wideKernelSetup()
 {
-#define S2_ISLAND_FORMS(KIND, ROUNDS)                                                                                                   \
-	(const void*)wideIslandKernelOf<KIND, ROUNDS, false, 0>, (const void*)wideIslandKernelOf<KIND, ROUNDS, true, 0>,                 \
-		(const void*)wideIslandKernelOf<KIND, ROUNDS, false, 2>, (const void*)wideIslandKernelOf<KIND, ROUNDS, true, 2>
-	for (const void* f : {(const void*)wideIslandKernel<S2_STRIP_ROUNDS, false, 0>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, false, 0>,
-						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, true, 0>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, true, 0>,
-						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, false, 2>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, false, 2>,
-						  (const void*)wideIslandKernel<S2_STRIP_ROUNDS, true, 2>, (const void*)wideIslandKernel<S2_STRIP_ROUNDS_MAX, true, 2>,
-						  // every form of the other two kinds the launch can pick (launchWideIsland)
-						  S2_ISLAND_FORMS(SOFT_FIXED, S2_STRIP_ROUNDS), S2_ISLAND_FORMS(SOFT_PGS, S2_STRIP_ROUNDS), S2_ISLAND_FORMS(SOFT_PGS, S2_STRIP_ROUNDS_MAX)})
-#undef S2_ISLAND_FORMS
-	{
-		if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-		{
-			return 1;
-		}
-	}
-	// every variant the launch can pick (launchWide): the five layouts in the plain, the sliced and the overflow form for s2Solve_TGS_Soft and
-	// s2Solve_PGS_Soft, the <3, 2> layout alone for s2Solve_SoftStep and for the two optional modes
-#define S2_WIDE_LAYOUTS(P, MODE, KIND)                                                                                            \
-	(const void*)wideStepKernel<P, 3, 2, 0, 0, MODE, KIND>, (const void*)wideStepKernel<P, 3, 3, 0, 0, MODE, KIND>, (const void*)wideStepKernel<P, 4, 2, 0, 0, MODE, KIND>, \
-		(const void*)wideStepKernel<P, 3, 2, 2, 0, MODE, KIND>, (const void*)wideStepKernel<P, 3, 2, 2, 2, MODE, KIND>
-	const void* steps[] = {S2_WIDE_LAYOUTS(0, 0, SOFT_TGS), S2_WIDE_LAYOUTS(2, 0, SOFT_TGS), S2_WIDE_LAYOUTS(0, S2_WIDE_SLICED, SOFT_TGS), S2_WIDE_LAYOUTS(2, S2_WIDE_SLICED, SOFT_TGS),
-						   S2_WIDE_LAYOUTS(0, S2_WIDE_OVERFLOW, SOFT_TGS), S2_WIDE_LAYOUTS(2, S2_WIDE_OVERFLOW, SOFT_TGS),
-						   (const void*)wideStepKernel<0, 3, 2, 0, 0, 1>, (const void*)wideStepKernel<0, 3, 2, 0, 0, 2>,
-						   (const void*)wideStepKernel<2, 3, 2, 0, 0, 1>, (const void*)wideStepKernel<2, 3, 2, 0, 0, 2>, (const void*)wideStepKernel<2, 3, 2, 0, 0, 3>};
-	const void* pgs[] = {S2_WIDE_LAYOUTS(0, 0, SOFT_PGS), S2_WIDE_LAYOUTS(2, 0, SOFT_PGS), S2_WIDE_LAYOUTS(0, S2_WIDE_SLICED, SOFT_PGS), S2_WIDE_LAYOUTS(2, S2_WIDE_SLICED, SOFT_PGS),
-						 S2_WIDE_LAYOUTS(0, S2_WIDE_OVERFLOW, SOFT_PGS), S2_WIDE_LAYOUTS(2, S2_WIDE_OVERFLOW, SOFT_PGS)};
-#undef S2_WIDE_LAYOUTS
-	const void* fixed[] = {(const void*)wideStepKernel<0, 3, 2, 0, 0, 0, SOFT_FIXED>, (const void*)wideStepKernel<2, 3, 2, 0, 0, 0, SOFT_FIXED>,
-						   (const void*)wideStepKernel<0, 3, 2, 0, 0, S2_WIDE_SLICED, SOFT_FIXED>, (const void*)wideStepKernel<2, 3, 2, 0, 0, S2_WIDE_SLICED, SOFT_FIXED>,
-						   (const void*)wideStepKernel<0, 3, 2, 0, 0, S2_WIDE_OVERFLOW, SOFT_FIXED>, (const void*)wideStepKernel<2, 3, 2, 0, 0, S2_WIDE_OVERFLOW, SOFT_FIXED>};
-	for (const void* f : fixed)
-	{
-		if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-		{
-			return 1;
-		}
-	}
-	for (const void* f : pgs)
-	{
-		if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-		{
-			return 1;
-		}
-	}
-	for (const void* f : steps)
-	{
-		hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		if (e != hipSuccess)
-		{
-			return (int)e;
-		}
-	}
-	return 0;
+	const int e = raiseLdsLimit(wideIslandVariants());
+	return e != 0 ? e : raiseLdsLimit(wideVariants());
 }
-#endif // S2_WIDE_ONLY_MAIN
 
 S2_DEFINE_WARM(wide_kernel)
 

@@ -247,14 +247,15 @@ def world_chain_async(base, steps):
     return seen
 
 
-def overflow_chain(base, steps):
+def overflow_chain(base, steps, options=(), solver_name="TGS_Soft"):
     """A contact that fits nowhere in the strips (two boxes many strips apart: a body on two seams is what the partition cannot have)
     takes an overflow position behind the strips instead of a rebuild in that step; the steps run sliced while a worker thread builds
     the structure that holds it, adopted a fixed number of steps later (solver_internal.h: IncrementalStrips; solver_async.cpp).
     Returns per step (overflowContacts, slicedStep, requested, adopted, structureBuilds, kernelLaunches)."""
     world = synthetic.pyramid_world(base)
     keys = ("bodies", "contacts", "joints", "shapes", "pairs", "origins")
-    params = wire.StepParams.make("TGS_Soft", 1.0 / 60.0, 8, 4, True)
+    vel, pos = common.DEFAULT_ITERS[solver_name]
+    params = wire.StepParams.make(solver_name, 1.0 / 60.0, vel, pos, True)
     # sixteen free pool slots behind the live ones
     spare_c = np.zeros(16, dtype=wire.contact_dtype)
     spare_c["bodyA"], spare_c["bodyB"], spare_c["constraintIndex"] = -1, -1, -1
@@ -284,7 +285,7 @@ def overflow_chain(base, steps):
         s.world_set_contacts(np.array([slot], dtype=np.int32), contacts, pairs)
 
     with hip.Solver(0) as s:
-        for k, v in (("strip_patience", 0), ("async_build_delay", 4)):
+        for k, v in (("strip_patience", 0), ("async_build_delay", 4)) + tuple(options):
             s.set_option(k, v)
         s.world_upload(*[world[k] for k in keys])
         mine = []
@@ -317,6 +318,38 @@ def overflow_chain(base, steps):
         order, offsets = s.contact_order()
         assert len(order) == len(set(order.tolist()))
     return seen
+
+
+def kernel_variants():
+    """The variants of the persistent strip kernels that the worlds above do not reach (launch.h: KernelVariant): the options that measured
+    no faster (pair_lanes, strip_body_warm, self_contained_strips, alone and together), parked rounds and option "wide" = 0 under the three soft
+    drivers, each with manifolds of two points only and of mixed point counts.  With S2_HOSTCHECK_TRACE_LAUNCHES the stand-in runtime prints
+    which kernel each launch picked and the LDS it asked for."""
+    cases = [("TGS_Soft", {"wide": 0, "pair_lanes": 1}), ("SoftStep", {"wide": 0, "pair_lanes": 1}), ("TGS_Soft", {"strip_body_warm": 1}),
+             ("TGS_Soft", {"self_contained_strips": 1}), ("TGS_Soft", {"self_contained_strips": 1, "strip_body_warm": 1}),
+             ("PGS_Soft", {}), ("PGS_Soft", {"persist_debug": 16}), ("SoftStep", {"persist_debug": 16}), ("TGS_Soft", {"persist_debug": 16, "strip_body_warm": 1}),
+             ("PGS_Soft", {"wide": 0}), ("SoftStep", {"wide": 0}), ("TGS_Soft", {"wide": 0, "pair_lanes": 0}),
+             # neither persistent kernel: one lean launch per sweep and phase (stripSoftKernel)
+             ("TGS_Soft", {"persist": 0}), ("PGS_Soft", {"persist": 0}), ("SoftStep", {"persist": 0})]
+    n = 0
+    for mixed in (False, True):
+        pre = common.copy3(synthetic.pyramid(100))
+        if mixed:
+            pre[1]["pointCount"][::37] = 1
+        for solver_name, options in cases:
+            vel, pos = common.DEFAULT_ITERS[solver_name]
+            params = wire.StepParams.make(solver_name, 1.0 / 60.0, vel, pos, True)
+            print("VARIANT CASE %s %s mixed %d" % (solver_name, sorted(options.items()), mixed), flush=True)
+            with hip.Solver(0) as s:
+                s.set_option("strip_patience", 0)
+                for k, v in options.items():
+                    s.set_option(k, v)
+                s.upload(*pre)
+                for _ in range(3):
+                    s.step_resident(params)
+                assert s.stats()["stripCount"] > 1
+                n += 1
+    return n
 
 
 def hub_rule():
@@ -428,6 +461,13 @@ def main():
     assert seen[-1][3] >= 1 and seen[-1][0] == 0 and seen[-1][1] == 0, seen  # ... until the worker's structure was adopted
     first = next(i for i, x in enumerate(seen) if x[0] > 0)
     assert seen[first][4] == seen[first - 1][4], seen  # no structure build in the step that found the contact
+    seen = overflow_chain(100, 12, (("overflow_kernel", 0),))
+    assert any(x[1] for x in seen), seen  # (option "overflow_kernel" = 0: the sliced form of the step)
+    for name in ("PGS_Soft", "SoftStep"):  # ... and both forms under the sibling soft solvers
+        for options in ((), (("overflow_kernel", 0),)):
+            seen = overflow_chain(100, 12, options, name)
+            assert max(x[0] for x in seen) >= 1, seen
+    print("kernel variants: %d cases" % kernel_variants())
     print("HOSTCHECK OK")
 
 

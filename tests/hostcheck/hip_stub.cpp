@@ -2,15 +2,23 @@
 // partition, incremental placement, the world chain's bookkeeping, the reference-side binding's pack / unpack -- can run under
 // AddressSanitizer + UndefinedBehaviorSanitizer on a box without a GPU (tests/hostcheck/Makefile, tests/test_hostcheck.py).
 // "Device" memory is heap memory (so an out-of-bounds hipMemcpy into a device table is an ASan report), copies are memcpy,
-// streams / events / graphs are inert handles, and kernels are never run: hipLaunchKernel returns success and does nothing.
+// streams / events / graphs are inert handles, and kernels are never run: hipLaunchKernel returns success and does nothing --
+// with S2_HOSTCHECK_TRACE_LAUNCHES set it prints one line per launch first: "LAUNCH <kernel symbol> grid <x> block <x> lds <bytes>"
+// (which kernel the host picked and the dynamic LDS it asked for are host decisions: tests/test_wide_island_kinds_host.py).
 // Results of a step are therefore meaningless; what is checked is that the host code touches only memory it owns.
 // The product never links this file.
 #include <hip/hip_runtime_api.h>
 
+#include <dlfcn.h>
+
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 static int s_dummy[16];
+// the configuration of the `kernel<<<...>>>` in flight (clang's host code pushes it, the kernel's stub pops it and calls hipLaunchKernel)
+static thread_local dim3 s_grid(1), s_block(1);
+static thread_local size_t s_shared = 0;
 
 extern "C" {
 
@@ -182,11 +190,28 @@ hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* numBlocks, const vo
 }
 
 // what clang's host-side code for `kernel<<<...>>>(...)` and for a translation unit with kernels calls
-hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) { return hipSuccess; }
-hipError_t __hipPushCallConfiguration(dim3, dim3, size_t, hipStream_t) { return hipSuccess; }
+hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void**, size_t shared, hipStream_t)
+{
+	static const bool trace = getenv("S2_HOSTCHECK_TRACE_LAUNCHES") != nullptr;
+	if (trace)
+	{
+		Dl_info info;
+		const bool named = dladdr(fn, &info) != 0 && info.dli_sname != nullptr && info.dli_saddr == fn;
+		// (under ASan a kernel's handle has a second symbol, <name>__sanitized_padded_global: print the kernel's own)
+		const char* alias = named ? strstr(info.dli_sname, "__sanitized_padded_global") : nullptr;
+		printf("LAUNCH %.*s grid %u block %u lds %zu\n", alias != nullptr ? (int)(alias - info.dli_sname) : 1 << 20, named ? info.dli_sname : "?", grid.x, block.x, shared);
+		fflush(stdout);
+	}
+	return hipSuccess;
+}
+hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t shared, hipStream_t)
+{
+	s_grid = grid, s_block = block, s_shared = shared;
+	return hipSuccess;
+}
 hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shared, hipStream_t* stream)
 {
-	*grid = dim3(1), *block = dim3(1), *shared = 0, *stream = nullptr;
+	*grid = s_grid, *block = s_block, *shared = s_shared, *stream = nullptr;
 	return hipSuccess;
 }
 void** __hipRegisterFatBinary(const void*) { return (void**)s_dummy; }

@@ -1,4 +1,4 @@
-"""s2Solve_SoftStep and s2Solve_PGS_Soft on the 512-thread resident-island kernel (wide_kernel.hip: wideIslandKernelOf<KIND, ROUNDS,
+"""s2Solve_SoftStep and s2Solve_PGS_Soft on the 512-thread resident-island kernel (wide_kernel.hip: wideIslandKernel<KIND, ROUNDS,
 SELF, POINTS>): worlds of many small islands, stepped resident through the C-ABI and compared BIT FOR BIT with the oracle swept in
 the order the device reports -- the gate of tests/test_gpu_fullsize.py: test_config5_512_pyramids_tgs_soft.
 
@@ -186,7 +186,7 @@ def test_fuzz_worlds_bit_exact_in_six_and_eight_rounds(seed, n_bodies, n_contact
     note(solver_name, kernels)
     assert all(r == rounds for _, r in kernels), kernels
     if solver_name == "SoftStep" and rounds == 8:
-        # no eight-round form for s2Solve_SoftStep (wide_kernel.hip: wideIslandForm): the world stays on islandStepKernel
+        # no eight-round form for s2Solve_SoftStep (wide_kernel.hip: wideIslandVariants): the world stays on islandStepKernel
         assert all(k == 2 for k, _ in kernels), kernels
     else:
         assert all(k in (3, 4) for k, _ in kernels), kernels

@@ -67,7 +67,7 @@ def test_every_layout_the_launch_can_pick_was_compiled(rows):
     for rounds in (6, 8):
         for self_contained in ("false", "true"):
             for points in (0, 2):
-                assert "wideIslandKernel<%d, %s, %d>" % (rounds, self_contained, points) in names
+                assert "wideIslandKernel<0, %d, %s, %d>" % (rounds, self_contained, points) in names  # (KIND 0: s2Solve_TGS_Soft)
 
 
 def test_the_fall_back_kernels_spill_no_more_than_they_did(rows):

@@ -1,7 +1,7 @@
 """Table of the compiler's register report (make -C solver2d_amd/csrc resources -> build/resources.txt):
 kernel, VGPRs, scratch bytes per lane, occupancy.  tests/test_kernel_resources.py reads the same file.
-The resident-island kernels appear as wideIslandKernel<ROUNDS, SELF, POINTS> (s2Solve_TGS_Soft) and wideIslandKernelOf<KIND, ROUNDS,
-SELF, POINTS> (KIND 1 = s2Solve_PGS_Soft: 6 and 8 rounds, KIND 3 = s2Solve_SoftStep: 6 rounds), 512 threads each; islandStepKernel
+The resident-island kernels appear as wideIslandKernel<KIND, ROUNDS, SELF, POINTS> (KIND 0 = s2Solve_TGS_Soft and KIND 1 =
+s2Solve_PGS_Soft: 6 and 8 rounds, KIND 3 = s2Solve_SoftStep: 6 rounds), 512 threads each; islandStepKernel
 <KIND, WARM, ROUNDS, 512> is their fall-back (option "wide" = 0; SoftStep with 7-8 rounds) and the only one of them that spills.
 Usage: python tools/kernel_resources.py [--scratch-only]"""
 import os
