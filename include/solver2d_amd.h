@@ -469,6 +469,18 @@ int s2amd_get_strip_owners(s2amdSolver* solver, int32_t* ownerStrip, int32_t* on
 #define S2AMD_RESIDENT_WIDE 3             /* the 512-thread island kernel (wide_kernel.hip) between the body prologue and epilogue */
 #define S2AMD_RESIDENT_WIDE_ONLY_LAUNCH 4 /* ... as the step's only launch (a world of resident islands only) */
 int s2amd_get_resident_kernel(s2amdSolver* solver, int32_t* kernel, int32_t* rounds);
+/* (additive, API 5) The variant census.  The register-resident soft kernels exist in many instantiations, kept in one table per kernel
+ * family; a step's launcher looks the instantiation for its input up by a key of small integers (the template arguments).  These calls
+ * enumerate the tables -- s2amd_variant_family_count() families; per family the kernel template's name, the names of the key's fields
+ * (comma separated, in the key's order), the key length and the number of entries; per entry its key -- and report per entry how often a
+ * launcher SELECTED it in this process, over all solvers.  That counts what the host enqueued or captured: a step replayed from its
+ * captured hipGraph executes the kernel again without selecting it again, and is not counted.  Counters never reset: take differences.
+ * The strings live as long as the library.  Any out pointer may be NULL.  No solver is needed, and nothing about a result depends on it:
+ * tests use it to know which code they compared.  A launcher that finds NO entry for its key fails the step with S2AMD_E_STATE and
+ * names family and key in s2amd_last_error(); it launches nothing. */
+int s2amd_variant_family_count(void);
+int s2amd_get_variant_family(int32_t family, const char** kernel, const char** keyFields, int32_t* keyLength, int32_t* entryCount);
+int s2amd_get_variant_entry(int32_t family, int32_t entry, int32_t* key, int32_t keyCapacity, uint64_t* selections);
 /* Live timing of the dominant kernel on the solver's own stream: the first contact solve sweep of
  * the step plan (all its colour-batch launches) is enqueued `repeats` times back to back in one
  * hipGraph and bracketed by a HIP event pair; *usPerLaunch = elapsed / launches, i.e. the time one

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <string>
 #include <vector>
 
 #include "solver2d_amd.h"
@@ -152,10 +153,15 @@ constexpr size_t S2_LDS_LIMIT = 160 * 1024;
 // One instantiation of a kernel family: its template arguments as plain numbers, and its address.  A family (wideStepKernel, wideIslandKernel,
 // stripStepKernel, islandStepKernel, stripSoftKernel, pairStepKernel) keeps ONE list of these beside its launcher, which looks the kernel for
 // its input up in it -- the rules are in the key it asks for, what exists is in the list -- and whose xxxKernelSetup() walks it.
+// selected: the variant census (s2amd_get_variant_entry) -- how often launchVariant picked this entry, in this process, whichever solver asked.
+// It counts the HOST's selections: a launch enqueued directly or captured into a step graph is one; the replays of that graph
+// (solver_step.cpp) are device executions the host never selects again, and are not counted.  A plain word behind a relaxed atomic
+// add: nothing on the step path allocates or locks for it.
 template <int N> struct KernelVariant
 {
 	int arg[N];
 	const void* fn;
+	mutable unsigned long long selected = 0;
 };
 template <int N> const KernelVariant<N>* findVariant(const std::vector<KernelVariant<N>>& list, const int (&key)[N])
 {
@@ -173,6 +179,20 @@ template <int N> const KernelVariant<N>* findVariant(const std::vector<KernelVar
 	}
 	return nullptr;
 }
+// A launcher found no entry for its key: the step must fail, not go on with that part of the world unswept.  Nothing is launched; the message
+// (family and key) becomes s2amd_last_error of the step that s2amdTakeVariantMiss is asked in (solver.cpp; per thread, like the error text).
+void s2amdVariantMiss(const char* family, const char* fields, const int* key, int n);
+bool s2amdTakeVariantMiss(std::string* message);
+// ... the launchers' lookup: the entry, or null with the miss recorded
+template <int N> const KernelVariant<N>* needVariant(const char* family, const char* fields, const std::vector<KernelVariant<N>>& list, const int (&key)[N])
+{
+	const KernelVariant<N>* v = findVariant(list, key);
+	if (v == nullptr)
+	{
+		s2amdVariantMiss(family, fields, key, N);
+	}
+	return v;
+}
 template <int N> int raiseLdsLimit(const std::vector<KernelVariant<N>>& list)
 {
 	for (const KernelVariant<N>& v : list)
@@ -188,9 +208,38 @@ template <int N> int raiseLdsLimit(const std::vector<KernelVariant<N>>& list)
 // (every variant of a family has the same parameter list; args: objects of exactly the kernel's parameter types, in its order)
 template <int N, typename... Args> void launchVariant(const KernelVariant<N>& v, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args)
 {
+	__atomic_fetch_add(&v.selected, 1ull, __ATOMIC_RELAXED);
 	void* ptrs[] = {(void*)&args...};
 	(void)hipLaunchKernel(v.fn, grid, block, ptrs, lds, s);
 }
+
+// A family as the census enumerates it (s2amd_get_variant_family / s2amd_get_variant_entry): the kernel template's name, the names of the key's
+// fields in the key's order (comma separated), and a reader of entry i.  xxxVariantFamilies() of the three files give their lists.
+struct VariantFamily
+{
+	const char* kernel;
+	const char* fields;
+	int keyLength;
+	int entries;
+	const void* list;
+	void (*read)(const void* list, int i, int* key, unsigned long long* selected);
+};
+template <int N> VariantFamily variantFamily(const char* kernel, const char* fields, const std::vector<KernelVariant<N>>& list)
+{
+	return VariantFamily{kernel, fields, N, (int)list.size(), &list, [](const void* l, int i, int* key, unsigned long long* selected) {
+							 const KernelVariant<N>& v = (*(const std::vector<KernelVariant<N>>*)l)[(size_t)i];
+							 for (int k = 0; k < N; ++k)
+							 {
+								 key[k] = v.arg[k];
+							 }
+							 *selected = __atomic_load_n(&v.selected, __ATOMIC_RELAXED);
+						 }};
+}
+#define S2_VARIANT_FAMILIES 6
+#define S2_VARIANT_KEY_MAX 7
+int wideVariantFamilies(VariantFamily* out);  // wide_kernel.hip: wideStepKernel, wideIslandKernel
+int stripVariantFamilies(VariantFamily* out); // strip_kernel.hip: stripStepKernel, islandStepKernel, stripSoftKernel
+int pairVariantFamilies(VariantFamily* out);  // pair_kernel.hip: pairStepKernel
 
 // strip_kernel.hip
 int stripKernelSetup();

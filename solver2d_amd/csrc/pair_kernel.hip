@@ -655,7 +655,11 @@ __global__ __launch_bounds__(S2_PAIR_THREADS) void pairStepKernel(ContactView c,
 	}
 }
 
-// pairStepKernel by {KIND, WARM, POINTS}
+// pairStepKernel by {KIND, WARM, POINTS}: the three soft drivers, each with the warm start its plan has -- s2Solve_TGS_Soft and s2Solve_PGS_Soft
+// the current-anchor one, s2Solve_SoftStep the fixed-anchor one (solver_plan.cpp: solveTgsSoft, solveJacobiOrPgsSoft; a plan without a warm
+// start is given its kind's: Executor::softPlan).  No StepParams makes another pair, so no other pair is instantiated.
+#define S2_PAIR_FAMILY "pairStepKernel"
+#define S2_PAIR_FIELDS "KIND,WARM,POINTS"
 typedef KernelVariant<3> PairVariant;
 template <int KIND, int WARM> static void addPairs(std::vector<PairVariant>& list)
 {
@@ -666,9 +670,9 @@ static const std::vector<PairVariant>& pairVariants()
 {
 	static const std::vector<PairVariant> list = [] {
 		std::vector<PairVariant> v;
-		addPairs<SOFT_TGS, WARM_CURRENT>(v), addPairs<SOFT_TGS, WARM_FIXED>(v);
-		addPairs<SOFT_PGS, WARM_CURRENT>(v), addPairs<SOFT_PGS, WARM_FIXED>(v);
-		addPairs<SOFT_FIXED, WARM_CURRENT>(v), addPairs<SOFT_FIXED, WARM_FIXED>(v);
+		addPairs<SOFT_TGS, WARM_CURRENT>(v);
+		addPairs<SOFT_PGS, WARM_CURRENT>(v);
+		addPairs<SOFT_FIXED, WARM_FIXED>(v);
 		return v;
 	}();
 	return list;
@@ -679,11 +683,17 @@ static const std::vector<PairVariant>& pairVariants()
 void launchPairStep(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops,
 					int opCount)
 {
-	const PairVariant* v = findVariant(pairVariants(), {kind, warm, pv.allTwoPoints ? 2 : 0});
-	if (v != nullptr)
+	const PairVariant* v = needVariant(S2_PAIR_FAMILY, S2_PAIR_FIELDS, pairVariants(), {kind, warm, pv.allTwoPoints ? 2 : 0});
+	if (v != nullptr) // (else the step fails: s2amdTakeVariantMiss)
 	{
 		launchVariant(*v, dim3((unsigned)a.groupCount), dim3(S2_PAIR_THREADS), stripStepLds(pv.ldsRecords, opCount), s, c, g, a, pv, ops, opCount);
 	}
+}
+
+int pairVariantFamilies(VariantFamily* out)
+{
+	out[0] = variantFamily(S2_PAIR_FAMILY, S2_PAIR_FIELDS, pairVariants());
+	return 1;
 }
 
 int pairKernelSetup() { return raiseLdsLimit(pairVariants()); }

@@ -13,8 +13,46 @@ namespace
 {
 
 thread_local std::string g_lastError;
+thread_local std::string g_variantMiss; // the first launcher of this thread's step that found no kernel for its key (launch.h: needVariant)
 
 } // namespace
+
+void s2amdVariantMiss(const char* family, const char* fields, const int* key, int n)
+{
+	if (!g_variantMiss.empty())
+	{
+		return; // (the first miss names the step's trouble)
+	}
+	std::string text = std::string("no ") + family + " variant for {" + fields + "} = {";
+	for (int i = 0; i < n; ++i)
+	{
+		text += (i != 0 ? ", " : "") + std::to_string(key[i]);
+	}
+	g_variantMiss = text + "}: nothing was launched for that part of the world";
+}
+
+bool s2amdTakeVariantMiss(std::string* message)
+{
+	if (g_variantMiss.empty())
+	{
+		return false;
+	}
+	if (message != nullptr)
+	{
+		*message = g_variantMiss;
+	}
+	g_variantMiss.clear();
+	return true;
+}
+
+// the six variant tables in the order of the census (s2amd_get_variant_family)
+static int variantFamilies(VariantFamily (&f)[S2_VARIANT_FAMILIES])
+{
+	int n = wideVariantFamilies(f);
+	n += stripVariantFamilies(f + n);
+	n += pairVariantFamilies(f + n);
+	return n;
+}
 
 // shared with the other translation units (solver_internal.h: fail) and the .hip stage files
 int s2amdFail(int code, const std::string& msg)
@@ -650,6 +688,62 @@ int s2amd_get_resident_kernel(s2amdSolver* s, int32_t* kernel, int32_t* rounds)
 	return S2AMD_OK;
 }
 
+int s2amd_variant_family_count(void)
+{
+	return S2_VARIANT_FAMILIES;
+}
+
+int s2amd_get_variant_family(int32_t family, const char** kernel, const char** keyFields, int32_t* keyLength, int32_t* entryCount)
+{
+	VariantFamily f[S2_VARIANT_FAMILIES];
+	if (family < 0 || family >= variantFamilies(f))
+	{
+		return fail(S2AMD_E_INVALID, "variant family out of range");
+	}
+	if (kernel)
+	{
+		*kernel = f[family].kernel;
+	}
+	if (keyFields)
+	{
+		*keyFields = f[family].fields;
+	}
+	if (keyLength)
+	{
+		*keyLength = f[family].keyLength;
+	}
+	if (entryCount)
+	{
+		*entryCount = f[family].entries;
+	}
+	return S2AMD_OK;
+}
+
+int s2amd_get_variant_entry(int32_t family, int32_t entry, int32_t* key, int32_t keyCapacity, uint64_t* selections)
+{
+	VariantFamily f[S2_VARIANT_FAMILIES];
+	if (family < 0 || family >= variantFamilies(f) || entry < 0 || entry >= f[family].entries)
+	{
+		return fail(S2AMD_E_INVALID, "variant family or entry out of range");
+	}
+	if (key != nullptr && keyCapacity < f[family].keyLength)
+	{
+		return fail(S2AMD_E_CAPACITY, "key buffer too small");
+	}
+	int k[S2_VARIANT_KEY_MAX];
+	unsigned long long n = 0;
+	f[family].read(f[family].list, entry, k, &n);
+	for (int i = 0; key != nullptr && i < f[family].keyLength; ++i)
+	{
+		key[i] = k[i];
+	}
+	if (selections)
+	{
+		*selections = n;
+	}
+	return S2AMD_OK;
+}
+
 int s2amd_get_strip_owners(s2amdSolver* s, int32_t* ownerStrip, int32_t* onSeam, int32_t capacity, int32_t* stripCount)
 {
 	if (!s)
@@ -895,6 +989,12 @@ int s2amd_measure_dominant(s2amdSolver* s, const s2amdStepParams* params, int32_
 	if (ce != hipSuccess)
 	{
 		return fail(S2AMD_E_DEVICE, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+	}
+	std::string miss;
+	if (s2amdTakeVariantMiss(&miss))
+	{
+		(void)hipGraphDestroy(g);
+		return fail(S2AMD_E_STATE, miss);
 	}
 	int launches = s->launchCounter;
 	if (launches == 0)

@@ -632,6 +632,10 @@ int doStep(s2amdSolver* s, const s2amdStepParams* params)
 	}
 	bool useGraph = s->optGraph != 0 && !q.profile;
 	q.fork = useGraph && s->optFork != 0;
+	// a launcher that found no kernel for its input (launch.h: needVariant) launched nothing: the step fails, it does not return a world
+	// with that part unswept
+	std::string variantMiss;
+	(void)s2amdTakeVariantMiss(nullptr); // (nothing left over from a call that failed earlier on this thread)
 	HIP_TRY(hipEventRecord(s->evBegin, s->stream));
 	if (useGraph)
 	{
@@ -659,6 +663,11 @@ int doStep(s2amdSolver* s, const s2amdStepParams* params)
 			s->graphKeySeen = key;
 			q.fork = false; // the parallel branches only exist inside a captured graph
 			enqueueAll();
+			if (s2amdTakeVariantMiss(&variantMiss))
+			{
+				(void)hipStreamSynchronize(s->stream);
+				return fail(S2AMD_E_STATE, variantMiss);
+			}
 			s->graphKeySeenLaunches = s->launchCounter;
 		}
 		else if (key != s->graphKey || s->graphExec == nullptr)
@@ -671,6 +680,11 @@ int doStep(s2amdSolver* s, const s2amdStepParams* params)
 			{
 				s->graph = nullptr;
 				return fail(S2AMD_E_DEVICE, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+			}
+			if (s2amdTakeVariantMiss(&variantMiss))
+			{
+				destroyGraph(s); // (never replayed: the captured sequence lacks a launch)
+				return fail(S2AMD_E_STATE, variantMiss);
 			}
 			HIP_TRY(hipGraphInstantiate(&s->graphExec, s->graph, nullptr, nullptr, 0));
 			s->graphKey = key;
@@ -691,6 +705,11 @@ int doStep(s2amdSolver* s, const s2amdStepParams* params)
 	else
 	{
 		enqueueAll();
+		if (s2amdTakeVariantMiss(&variantMiss))
+		{
+			(void)hipStreamSynchronize(s->stream);
+			return fail(S2AMD_E_STATE, variantMiss);
+		}
 	}
 	HIP_TRY(hipEventRecord(s->evEnd, s->stream));
 	HIP_TRY(hipGetLastError());

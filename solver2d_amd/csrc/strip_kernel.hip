@@ -1164,8 +1164,18 @@ __global__ __launch_bounds__(THREADS) void islandStepKernel(ContactView c, BodyV
 size_t stripStepLds(int ldsRecords, int opCount) { return (size_t)ldsRecords * sizeof(float4) + (size_t)opCount * sizeof(Op); }
 
 // Every instantiation of the three kernel families of this file that exists: islandStepKernel by {KIND, WARM, ROUNDS}, stripStepKernel by
-// {KIND, WARM, POINTS, ROUNDS, SEAMREG}, stripSoftKernel by {KIND, WARM} (WARM -1: no warm start in the launch)
+// {KIND, WARM, POINTS, ROUNDS, SEAMREG}, stripSoftKernel by {KIND, WARM} (WARM -1: no warm start in the launch).
+// KIND and WARM come in three pairs only: s2Solve_TGS_Soft and s2Solve_PGS_Soft warm start with the current anchors, s2Solve_SoftStep with the
+// fixed ones (solver_plan.cpp: solveTgsSoft, solveJacobiOrPgsSoft; a plan without a warm start is given its kind's: Executor::softPlan).  No
+// StepParams makes {SOFT_TGS, WARM_FIXED}, {SOFT_PGS, WARM_FIXED} or {SOFT_FIXED, WARM_CURRENT}: they are not instantiated, and a launcher
+// asked for one fails the step (launch.h: needVariant).
 #define S2_ISLAND_THREADS 512
+#define S2_STRIP_FAMILY "stripStepKernel"
+#define S2_STRIP_FIELDS "KIND,WARM,POINTS,ROUNDS,SEAMREG"
+#define S2_ISLAND_FAMILY "islandStepKernel"
+#define S2_ISLAND_FIELDS "KIND,WARM,ROUNDS"
+#define S2_SOFT_FAMILY "stripSoftKernel"
+#define S2_SOFT_FIELDS "KIND,WARM"
 struct StripVariants
 {
 	std::vector<KernelVariant<3>> island;
@@ -1184,8 +1194,7 @@ template <int KIND, int WARM> static void addStripVariants(StripVariants& v)
 }
 template <int KIND> static void addStripVariants(StripVariants& v)
 {
-	addStripVariants<KIND, WARM_CURRENT>(v);
-	addStripVariants<KIND, WARM_FIXED>(v);
+	addStripVariants<KIND, KIND == SOFT_FIXED ? WARM_FIXED : WARM_CURRENT>(v);
 	v.soft.push_back({{KIND, -1}, (const void*)stripSoftKernel<KIND, -1>});
 }
 static const StripVariants& stripVariants()
@@ -1207,10 +1216,14 @@ static const StripVariants& stripVariants()
 void launchIslandStep(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& t, const float4* softCoef, const Op* ops,
 					  int opCount, int maxRounds, s2amdContact* wire, const s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const unsigned int* stepFailed)
 {
-	const auto* v = findVariant(stripVariants().island, {kind, warm, maxRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX});
-	if (t.groupCount <= 0 || v == nullptr)
+	if (t.groupCount <= 0)
 	{
 		return;
+	}
+	const auto* v = needVariant(S2_ISLAND_FAMILY, S2_ISLAND_FIELDS, stripVariants().island, {kind, warm, maxRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX});
+	if (v == nullptr)
+	{
+		return; // (the step fails: s2amdTakeVariantMiss)
 	}
 	launchVariant(*v, dim3((unsigned)t.groupCount), dim3(S2_ISLAND_THREADS), stripStepLds(t.ldsRecords, opCount), s, c, g, t, softCoef[0], softCoef[1], ops, opCount, wire,
 				  wireBodies, hostFlags, warmStart, stepFailed);
@@ -1221,8 +1234,8 @@ void launchStripStep(hipStream_t s, int kind, int warm, const ContactView& c, co
 {
 	// (seam records in registers: TGS_Soft with the current-anchor warm start on six rounds; the other kinds keep theirs in LDS on such a partition too)
 	const bool seamRegs = !pv.wideRounds && pv.seamRegs && kind == SOFT_TGS && warm == WARM_CURRENT;
-	const auto* v = findVariant(stripVariants().step, {kind, warm, !seamRegs && pv.allTwoPoints ? 2 : 0, pv.wideRounds ? S2_STRIP_ROUNDS_MAX : S2_STRIP_ROUNDS, seamRegs ? 1 : 0});
-	if (v != nullptr)
+	const auto* v = needVariant(S2_STRIP_FAMILY, S2_STRIP_FIELDS, stripVariants().step, {kind, warm, !seamRegs && pv.allTwoPoints ? 2 : 0, pv.wideRounds ? S2_STRIP_ROUNDS_MAX : S2_STRIP_ROUNDS, seamRegs ? 1 : 0});
+	if (v != nullptr) // (else the step fails: s2amdTakeVariantMiss)
 	{
 		// pv.ldsRecords: bodies + seam constraint records
 		launchVariant(*v, dim3((unsigned)a.groupCount), dim3(S2_STRIP_THREADS), stripStepLds(pv.ldsRecords, opCount), s, c, g, a, pv, ops, opCount);
@@ -1231,12 +1244,25 @@ void launchStripStep(hipStream_t s, int kind, int warm, const ContactView& c, co
 
 void launchStripSoft(hipStream_t s, int kind, int warm, const ContactView& c, const BodyView& g, const StripTableView& t, const StripOps& ops)
 {
-	const auto* v = findVariant(stripVariants().soft, {kind, warm == WARM_CURRENT || warm == WARM_FIXED ? warm : -1});
-	if (t.groupCount <= 0 || v == nullptr)
+	if (t.groupCount <= 0)
 	{
 		return;
 	}
+	const auto* v = needVariant(S2_SOFT_FAMILY, S2_SOFT_FIELDS, stripVariants().soft, {kind, warm == WARM_CURRENT || warm == WARM_FIXED ? warm : -1});
+	if (v == nullptr)
+	{
+		return; // (the step fails: s2amdTakeVariantMiss)
+	}
 	launchVariant(*v, dim3((unsigned)t.groupCount), dim3(S2_STRIP_THREADS), stripStepLds(t.ldsRecords, 0), s, c, g, t.descs, t.bodyIds, t.slots, t.slotOffsets, ops);
+}
+
+int stripVariantFamilies(VariantFamily* out)
+{
+	const StripVariants& v = stripVariants();
+	out[0] = variantFamily(S2_STRIP_FAMILY, S2_STRIP_FIELDS, v.step);
+	out[1] = variantFamily(S2_ISLAND_FAMILY, S2_ISLAND_FIELDS, v.island);
+	out[2] = variantFamily(S2_SOFT_FAMILY, S2_SOFT_FIELDS, v.soft);
+	return 3;
 }
 
 int stripKernelSetup()

@@ -1906,16 +1906,20 @@ static const std::vector<WideVariant>& wideVariants()
 	return list;
 }
 
-// which variant takes the partition with these two features, or null: none
-static const WideVariant* wideVariant(int kind, const PersistView& pv, bool selfContained, bool bodyWarm)
+#define S2_WIDE_FAMILY "wideStepKernel"
+#define S2_WIDE_FIELDS "POINTS,RPH,SR,SL,IL,MODE,KIND"
+// the key of the variant that takes the partition with these two features; false: the partition has more rounds than any layout
+static bool wideKey(int kind, const PersistView& pv, bool selfContained, bool bodyWarm, int (&key)[7])
 {
 	if (pv.maxRoundsA > 8 || pv.maxSeamRounds > 4)
 	{
-		return nullptr;
+		return false;
 	}
 	// the layout: <3, 2> unless the partition needs more rounds
 	const bool six = pv.maxRoundsA <= 6;
 	int rph = 3, sr = 2, sl = 0, il = 0;
+	// debugSkip & 16, 64, 128 (option "persist_debug"; tests): a roomier layout than the partition needs -- the parked rounds, the third seam
+	// record, the fourth interior pair.  They change this choice and nothing else: no kernel reads them
 	if ((pv.debugSkip & 16) != 0 || pv.maxSeamRounds > 3 || (pv.maxSeamRounds > 2 && !six))
 	{
 		// seven or eight interior colours AND three or four seam colours -- a pile after an impact: six interior and two seam rounds in registers,
@@ -1923,11 +1927,11 @@ static const WideVariant* wideVariant(int kind, const PersistView& pv, bool self
 		// variants with parked rounds whatever the partition needs
 		sl = 2, il = six ? 0 : 2; // <3, 2, 2>, <3, 2, 2, 2>
 	}
-	else if (pv.maxSeamRounds > 2)
+	else if (pv.maxSeamRounds > 2 || ((pv.debugSkip & 64) != 0 && six))
 	{
 		sr = 3; // <3, 3>
 	}
-	else if (!six)
+	else if (!six || (pv.debugSkip & 128) != 0)
 	{
 		rph = 4; // <4, 2>
 	}
@@ -1941,7 +1945,18 @@ static const WideVariant* wideVariant(int kind, const PersistView& pv, bool self
 	{
 		mode = pv.overflowKernel != 0 ? S2_WIDE_OVERFLOW : (pv.clearOwn != 0 ? S2_WIDE_SLICED : 0);
 	}
-	return findVariant(wideVariants(), {pv.allTwoPoints ? 2 : 0, rph, sr, sl, il, mode, kind});
+	const int k[7] = {pv.allTwoPoints ? 2 : 0, rph, sr, sl, il, mode, kind};
+	for (int i = 0; i < 7; ++i)
+	{
+		key[i] = k[i];
+	}
+	return true;
+}
+// ... and that variant, or null: none (a plan asks before it chooses this kernel: wideStepLds)
+static const WideVariant* wideVariant(int kind, const PersistView& pv, bool selfContained, bool bodyWarm)
+{
+	int key[7];
+	return wideKey(kind, pv, selfContained, bodyWarm, key) ? findVariant(wideVariants(), key) : nullptr;
 }
 
 // that variant's dynamic LDS: the bodies, the ops and the three fixed records (coefficients, census flags); parked rounds; the arms rA0 / rB0
@@ -1971,10 +1986,19 @@ size_t wideStepLds(int kind, const PersistView& pv, int opCount, bool selfContai
 
 void launchWideStep(hipStream_t s, int kind, const ContactView& c, const BodyView& g, const StripTableView& a, const PersistView& pv, const Op* ops, int opCount, const WideSelf* self)
 {
-	const WideVariant* v = wideVariant(kind, pv, self != nullptr, pv.bodyWarm != 0);
+	int key[7] = {-1, -1, -1, -1, -1, -1, kind};
+	const WideVariant* v = nullptr;
+	if (wideKey(kind, pv, self != nullptr, pv.bodyWarm != 0, key))
+	{
+		v = needVariant(S2_WIDE_FAMILY, S2_WIDE_FIELDS, wideVariants(), key);
+	}
+	else
+	{
+		s2amdVariantMiss(S2_WIDE_FAMILY, S2_WIDE_FIELDS, key, 7); // (more rounds than any layout holds: -1 in the fields nothing could be chosen for)
+	}
 	if (v == nullptr)
 	{
-		return;
+		return; // (the step fails: s2amdTakeVariantMiss)
 	}
 	const dim3 grid((unsigned)a.groupCount + (pv.overflowKernel != 0 ? 1u : 0u)); // (+ the overflow workgroup: wideOverflowWorker)
 	launchVariant(*v, grid, dim3(S2_WIDE_THREADS), wideVariantLds(*v, pv, opCount), s, c, g, a, pv, ops, opCount, (v->arg[5] & S2_WIDE_SELF) != 0 ? *self : WideSelf{});
@@ -2339,10 +2363,13 @@ static const std::vector<WideIslandVariant>& wideIslandVariants()
 	return list;
 }
 
-// maxRounds: colour rounds of the group with the most
-static const WideIslandVariant* wideIslandVariant(int kind, int maxRounds, bool selfContained, bool allTwoPoints)
+#define S2_WIDE_ISLAND_FAMILY "wideIslandKernel"
+#define S2_WIDE_ISLAND_FIELDS "KIND,ROUNDS,SELF,POINTS"
+// maxRounds: colour rounds of the group with the most; need: a launch asks (no entry is an error), not a plan (wideIslandLds)
+static const WideIslandVariant* wideIslandVariant(int kind, int maxRounds, bool selfContained, bool allTwoPoints, bool need = false)
 {
-	return findVariant(wideIslandVariants(), {kind, maxRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX, selfContained ? 1 : 0, allTwoPoints ? 2 : 0});
+	const int key[4] = {kind, maxRounds <= S2_STRIP_ROUNDS ? S2_STRIP_ROUNDS : S2_STRIP_ROUNDS_MAX, selfContained ? 1 : 0, allTwoPoints ? 2 : 0};
+	return need ? needVariant(S2_WIDE_ISLAND_FAMILY, S2_WIDE_ISLAND_FIELDS, wideIslandVariants(), key) : findVariant(wideIslandVariants(), key);
 }
 
 // ldsRecords: body records of the largest group (StripTableView::ldsRecords)
@@ -2363,13 +2390,20 @@ void launchWideIsland(hipStream_t s, int kind, const ContactView& c, const BodyV
 					  int maxRounds, s2amdContact* wire, s2amdBody* wireBodies, const uint32_t* hostFlags, int warmStart, const StepConsts& sc, float unpackH,
 					  int selfContained, const unsigned int* stepFailed, int allTwoPoints)
 {
-	const WideIslandVariant* v = wideIslandVariant(kind, maxRounds, selfContained != 0, allTwoPoints != 0);
+	const WideIslandVariant* v = wideIslandVariant(kind, maxRounds, selfContained != 0, allTwoPoints != 0, true);
 	if (v == nullptr)
 	{
-		return;
+		return; // (the step fails: s2amdTakeVariantMiss)
 	}
 	launchVariant(*v, dim3((unsigned)t.groupCount), dim3(S2_WIDE_THREADS), wideIslandLds(kind, maxRounds, t.ldsRecords, opCount), s, c, g, t, softCoef[0], softCoef[1], ops,
 				  opCount, wire, wireBodies, hostFlags, warmStart, sc, unpackH, stepFailed);
+}
+
+int wideVariantFamilies(VariantFamily* out)
+{
+	out[0] = variantFamily(S2_WIDE_FAMILY, S2_WIDE_FIELDS, wideVariants());
+	out[1] = variantFamily(S2_WIDE_ISLAND_FAMILY, S2_WIDE_ISLAND_FIELDS, wideIslandVariants());
+	return 2;
 }
 
 int wideKernelSetup()

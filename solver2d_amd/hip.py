@@ -25,7 +25,7 @@ EXPORTS = [
     "s2amd_set_option", "s2amd_export_poses", "s2amd_export_poses_async", "s2amd_export_bodies_async", "s2amd_export_wait", "s2amd_measure_dominant", "s2amd_refit_shapes", "s2amd_find_pairs", "s2amd_synchronize", "s2amd_update_contacts", "s2amd_find_islands", "s2amd_color_constraints",
     "s2amd_world_upload", "s2amd_world_step", "s2amd_world_download", "s2amd_world_find_pairs", "s2amd_world_set_contacts",
     "s2amd_device_alloc", "s2amd_device_free", "s2amd_device_read", "s2amd_world_separated", "s2amd_world_download_boxes", "s2amd_world_set_refit_order", "s2amd_world_download_step", "s2amd_world_set_tree", "s2amd_world_get_tree",
-    "s2amd_get_strip_owners", "s2amd_get_resident_kernel",
+    "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
     "s2amd_sharded_step_async", "s2amd_sharded_wait", "s2amd_sharded_get_step_ops", "s2amd_sharded_count_ops",
@@ -68,6 +68,9 @@ def load(fast=False):
     L.s2amd_get_writable_bodies.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_get_strip_owners.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_get_resident_kernel.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.s2amd_variant_family_count.restype = ctypes.c_int
+    L.s2amd_get_variant_family.argtypes = [i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.s2amd_get_variant_entry.argtypes = [i32, i32, ctypes.POINTER(i32), i32, ctypes.POINTER(ctypes.c_uint64)]
     L.s2amd_get_stats.argtypes = [vp, ctypes.POINTER(wire.StepStats)]
     L.s2amd_set_option.argtypes = [vp, ctypes.c_char_p, i32]
     L.s2amd_export_poses.argtypes = [vp, vp, i32]
@@ -131,6 +134,34 @@ def device_bus_id(device):
 def _check(rc, L=None):
     if rc != 0:
         raise S2AmdError("s2amd error %d: %s" % (rc, (L or load()).s2amd_last_error().decode(errors="replace")))
+
+
+def variant_families(fast=False):
+    """{kernel family: tuple of its key's field names} of the variant tables (s2amd_get_variant_family)."""
+    L = load(fast)
+    out = {}
+    for f in range(L.s2amd_variant_family_count()):
+        kernel, fields = ctypes.c_char_p(), ctypes.c_char_p()
+        _check(L.s2amd_get_variant_family(f, ctypes.byref(kernel), ctypes.byref(fields), None, None), L)
+        out[kernel.value.decode()] = tuple(fields.value.decode().split(","))
+    return out
+
+
+def variant_census(fast=False):
+    """{kernel family: {key tuple: count}}: every entry of the variant tables of the register-resident soft kernels and how often a launcher
+    of this process has selected it so far (host-side selections -- an eager launch or a capture; the replays of a captured step graph are not
+    counted: s2amd_get_variant_entry).  Counters never reset: compare two calls."""
+    L = load(fast)
+    out = {}
+    for f in range(L.s2amd_variant_family_count()):
+        kernel, length, entries = ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int32()
+        _check(L.s2amd_get_variant_family(f, ctypes.byref(kernel), None, ctypes.byref(length), ctypes.byref(entries)), L)
+        family = out.setdefault(kernel.value.decode(), {})
+        key, count = (ctypes.c_int32 * length.value)(), ctypes.c_uint64()
+        for e in range(entries.value):
+            _check(L.s2amd_get_variant_entry(f, e, key, length.value, ctypes.byref(count)), L)
+            family[tuple(key)] = int(count.value)
+    return out
 
 
 _env_options_logged = False

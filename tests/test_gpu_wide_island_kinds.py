@@ -11,50 +11,14 @@ import numpy as np
 import pytest
 
 from solver2d_amd import hip, synthetic, wire
-from tests import common, fuzz_worlds, oraclebind, world_chain
+from tests import common, oraclebind, world_chain
+# (the builders the variant census shares with this file live beside its case table)
+from tests.variant_cases import fuzz_world, hub_pyramids, mixed_point_counts, mixed_pyramids, with_free_bodies
 
 pytestmark = pytest.mark.gpu
 
 SOLVERS = ["SoftStep", "PGS_Soft"]
 SEEN = {}  # solver name -> set of (kernel, rounds) over the tests of this file that ran before the census at its end
-
-
-def concat_worlds(parts):
-    """Several (bodies, contacts, joints) worlds as one, body indices shifted."""
-    bodies = np.concatenate([p[0] for p in parts])
-    contacts, joints, base = [], [], 0
-    for b, c, j in parts:
-        c, j = c.copy(), j.copy()
-        for arr in (c, j):
-            if len(arr):
-                live = arr["bodyA"] >= 0
-                arr["bodyA"][live] += base
-                arr["bodyB"][live] += base
-        contacts.append(c), joints.append(j)
-        base += len(b)
-    return bodies, np.concatenate(contacts), np.concatenate(joints)
-
-
-def mixed_pyramids(bases=(5, 8, 12, 17, 23, 31, 40, 9, 26, 40, 6, 14)):
-    """Pyramids of mixed bases, each on its own static ground (a ground contact has a static side: the doubled contact hertz)."""
-    parts = []
-    for k, base in enumerate(bases):
-        b, c, j = synthetic.pyramid(base)
-        b = b.copy()
-        b["position"][:, 0] += np.float32(64.0 * k)
-        parts.append((b, c, j))
-    return concat_worlds(parts)
-
-
-def mixed_point_counts(seed=11):
-    """... with manifolds of 0, 1 and 2 points: the kernel's POINTS == 0 form (per-point masking)."""
-    b, c, j = mixed_pyramids((5, 12, 20, 31, 7, 16))
-    rng = np.random.default_rng(seed)
-    pick = rng.random(len(c))
-    c["pointCount"][pick < 0.15] = 0
-    c["pointCount"][(pick >= 0.15) & (pick < 0.40)] = 1
-    assert {0, 1, 2} <= set(np.unique(c["pointCount"]).tolist())
-    return b, c, j
 
 
 def kinematic_world():
@@ -70,47 +34,6 @@ def kinematic_world():
         b[top]["linearVelocity"] = (0.25, 0.0)
         b[top]["angularVelocity"] = 0.1
     return b, c, j
-
-
-def hub_pyramids():
-    """Pyramids whose top brick also touches five bricks further down (copies of its own manifolds with another partner): a body
-    with seven contacts, so its group needs a seventh colour round -- the eight-round variant, in an islands-only world."""
-    b, c, j = synthetic.pyramid(12, count=4)
-    per_b, per_c = len(b) // 4, len(c) // 4
-    extra = []
-    for k in range(4):
-        top = (k + 1) * per_b - 1
-        mine = [i for i in range(k * per_c, (k + 1) * per_c) if top in (int(c[i]["bodyA"]), int(c[i]["bodyB"]))]
-        assert len(mine) == 2
-        for n in range(5):
-            e = c[mine[n % 2]].copy()
-            partner = k * per_b + (1, 12, 13, 23, 24)[n]  # bricks at the ends of the lower rows (three or four contacts of their own)
-            assert b[partner]["type"] == wire.BODY_DYNAMIC and partner != top
-            if int(e["bodyA"]) == top:
-                e["bodyB"] = partner
-            else:
-                e["bodyA"] = partner
-            e["points"][0]["separation"] = 0.004 * n - 0.01
-            extra.append(e)
-    return b, np.concatenate([c, np.array(extra, dtype=c.dtype)]), j
-
-
-def fuzz_world(seed, n_bodies, n_contacts):
-    """tests/fuzz_worlds.random_world without joints: speculative and deep points, massless and kinematic bodies, off-centre
-    centres of mass, free slots -- and, in the small dense ones, bodies with seven or eight contacts."""
-    return fuzz_worlds.random_world(seed, n_bodies=n_bodies, n_contacts=n_contacts, n_joints=0)
-
-
-def with_free_bodies(world, count=40):
-    """The same islands beside dynamic bodies that touch nothing: the world is no longer islands only, so the body prologue and
-    epilogue stay and the island kernel runs between them (its non-SELF form)."""
-    b, c, j = world
-    extra = np.zeros(count, dtype=wire.body_dtype)
-    for i in range(count):
-        synthetic._dynamic_body(extra[i], -50.0 - 2.0 * i, 30.0 + i, synthetic.BOX_MASS, synthetic.BOX_I)
-        extra[i]["linearVelocity"] = (0.5, -0.25 * i)
-        extra[i]["angularVelocity"] = 0.125 * i
-    return np.concatenate([b, extra]), c.copy(), j.copy()
 
 
 # world name -> (builder, options, {solver: (kernels allowed, rounds)})

@@ -2,13 +2,16 @@
 (-Rpass-analysis=kernel-resource-usage; `make -C solver2d_amd/csrc resources`) for every kernel of wide_kernel.hip, strip_kernel.hip,
 generic_kernel.hip and group_kernel.hip.
 
-  * NO variant of the 512-thread family -- wideStepKernel (every layout the launch can pick: <3,2>, <3,3>, <4,2>, <3,2,2>, <3,2,2,2>;
-    plain, sliced and with the overflow workgroup; s2Solve_TGS_Soft, s2Solve_PGS_Soft, s2Solve_SoftStep) and wideIslandKernel (6 and 8 rounds) -- spills a byte to
+  * NO variant of the 512-thread family -- wideStepKernel (71 entries: every layout the launch can pick: <3,2>, <3,3>, <4,2>, <3,2,2>, <3,2,2,2>;
+    plain, sliced and with the overflow workgroup; s2Solve_TGS_Soft, s2Solve_PGS_Soft, s2Solve_SoftStep) and wideIslandKernel (20 entries: 6 and 8 rounds) -- spills a byte to
     scratch, and all of them keep two waves per SIMD.  Through round 4, 37 of 56 did (24-520 bytes per lane): exactly the variants a
     churning world ends up on.  Round 5 moved the local anchors of the records beyond the fifth into LDS (wide_kernel.hip:
     wideLocalsInLds) and dropped the optional modes where they did not fit.
   * The older 256-thread kernels (stripStepKernel / islandStepKernel: the fall-back when option "wide" is off or a hand-off timed
-    out) are reported, and their scratch may only shrink: the set below is what they spill today.
+    out) are reported, and their scratch may only shrink: the set below is what they spill today.  (13 stripStepKernel, 6 islandStepKernel,
+    6 stripSoftKernel entries: one warm-start kind per soft kind, the one its driver's plan has.)
+
+What the entries COMPUTE is tests/test_gpu_variant_census.py's business: every one of them runs there, bit for bit against the oracle.
 
 No GPU: the compiler runs here (about a minute on four cores)."""
 import os
