@@ -405,6 +405,55 @@ int s2amd_world_download(s2amdSolver* solver, s2amdBody* bodies, int32_t bodyCap
 						 s2amdJoint* joints, int32_t jointCapacity, s2amdShape* shapes, int32_t shapeCapacity, s2amdPairState* pairs, float* origins,
 						 int32_t* status);
 
+/* (additive, API 5) The contact report: what touches what, and how hard, without moving the world.  s2World_Draw's contact pass
+ * (src/world.c:486-561) reads, for every valid contact, manifold.pointCount and manifold.normal and, per point, localAnchorA through
+ * S2_TRANSFORM(bodyA), separation, persisted, normalImpulse and tangentImpulse; a sensor, a foot-contact force or a "began touching"
+ * trigger reads the same.  With a report flag set, s2amd_world_step compacts that on the device behind its stage 4, in a defined order,
+ * and the three getters below hand it out; with no flag set (the default) a step enqueues what it always did.
+ *   A contact slot is TOUCHING after a step when its pair slot is live and pointCount > 0 after that step's stage 3 (src/world.c:132-168):
+ *   the contacts the solve swept.
+ *   S2AMD_REPORT_TOUCH     `began`: the slots touching now that were not touching before the step; `ended`: the reverse -- a pair stage 3
+ *                          found separated and destroyed while it was touching is in `ended`.  Both ascending.  "Before" is, after
+ *                          s2amd_world_upload, pointCount > 0 of the uploaded contacts (resting manifolds report no begin), and a slot
+ *                          written by s2amd_world_set_contacts takes pointCount > 0 of what was written: no event, the caller did that itself.
+ *                          A step the library repeats internally (a lost hand-off) reports once, as finally executed.
+ *   S2AMD_REPORT_CONTACTS  one s2amdTouchingContact per touching slot, ascending: point[j] = s2TransformPoint({origin, rot} of bodyA after
+ *                          the step, localAnchorA) in the operation order of include/solver2d/math.h:350-356 -- what a s2World_Draw called
+ *                          right after the step would draw (src/world.c:518) --, persisted from s2amdPairState, everything else from the
+ *                          resident contact; the entries of unused points are zero.
+ *   S2AMD_REPORT_BODY_SUMS per body slot, static ones included: with P = s2Add(s2MulSV(normalImpulse, normal), s2MulSV(tangentImpulse,
+ *                          s2RightPerp(normal))) of a contact point (src/solve_common.c:304-314), `impulse` is the float32 sum, from +0, left
+ *                          to right over the body's touching contacts in ascending slot order, points in index order, of -P where the body
+ *                          is bodyA and +P where it is bodyB; `normalImpulse` the same ordered sum of the points' normalImpulse; `touching`
+ *                          the number of contacts.  No floating-point atomics: the result is a pure function of the arrays.
+ * Every getter describes the last s2amd_world_step: S2AMD_E_STATE without a resident world, when its flag was not set before that step or
+ * no step has run since; S2AMD_E_CAPACITY when a buffer is too small -- the counts are set, nothing is consumed, the caller asks again
+ * (as s2amd_world_find_pairs).  s2amd_world_set_report: S2AMD_E_INVALID for unknown bits; the flags hold from the next step on, across
+ * uploads.  The step itself gains no host wait: the getters wait for what they need. */
+#define S2AMD_REPORT_TOUCH 1     /* begin / end lists */
+#define S2AMD_REPORT_CONTACTS 2  /* one record per touching contact */
+#define S2AMD_REPORT_BODY_SUMS 4 /* per body: net contact impulse, normal load, touching count */
+int s2amd_world_set_report(s2amdSolver* solver, int32_t flags);
+typedef struct s2amdTouchingContact /* 64 bytes */
+{
+	int32_t slot, bodyA, bodyB;
+	uint8_t pointCount, persisted[2], pad; /* persisted: s2amdPairState.persisted */
+	float normal[2];
+	float point[2][2]; /* world space, as src/world.c:518 computes it */
+	float separation[2], normalImpulse[2], tangentImpulse[2];
+} s2amdTouchingContact;
+typedef struct s2amdBodyContactSum /* 16 bytes */
+{
+	float impulse[2];
+	float normalImpulse;
+	int32_t touching;
+} s2amdBodyContactSum;
+int s2amd_world_touch_events(s2amdSolver* solver, int32_t* began, int32_t beganCapacity, int32_t* beganCount, int32_t* ended,
+							 int32_t endedCapacity, int32_t* endedCount);
+int s2amd_world_touching(s2amdSolver* solver, s2amdTouchingContact* out, int32_t capacity, int32_t* count);
+/* out[bodyCapacity of the upload] */
+int s2amd_world_body_sums(s2amdSolver* solver, s2amdBodyContactSum* out, int32_t bodyCapacity);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

@@ -524,6 +524,13 @@ struct SolverRest
 	std::vector<uint8_t> hSlotBytes;
 	bool slotBytesFresh = false; // hSlotBytes is of the state the device is in right now (cleared by every world call that changes it)
 	std::vector<int32_t> hSeparated;
+	// contact report (contact_report.hip; s2amd_world_set_report): compacted behind stage 4 of the step attempt that stands
+	int reportFlags = 0;	 // S2AMD_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
+	int reportStepFlags = 0; // ... and what the last one did: the getters answer for these only
+	bool reportHeadKnown = false; // hReportHead holds the last step's counts (fetched by the first getter that asks)
+	int32_t hReportHead[4] = {0, 0, 0, 0}; // {began, ended, touching, 0}
+	DevBuf dReport;			 // one block, carved by reportLayout(): was-touching bytes, tile counts, head, the three lists, sort arrays, body sums
+	size_t reportSortTmpBytes = 0;
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -763,6 +770,13 @@ int refreshConstraintIndexOnDevice(s2amdSolver* s);
 int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
+// contact_report.hip.  reportPrepare: the report's device block for the resident world, its "was touching" bytes from the resident
+// contacts (at s2amd_world_upload and when s2amd_world_set_report turns the report on: nothing is allocated inside a step);
+// reportNoteSetContacts: the slots s2amd_world_set_contacts has just staged take pointCount > 0 of what was written (device pointers);
+// reportEnqueue: the step's report passes on the solve stream, behind the attempt that stands
+int reportPrepare(s2amdSolver* s);
+int reportNoteSetContacts(s2amdSolver* s, const int32_t* dSlots, int count, const s2amdContact* dNewContacts);
+int reportEnqueue(s2amdSolver* s);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

@@ -533,6 +533,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		}
 	}
 	s->worldResident = false;
+	s->reportStepFlags = 0;
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -621,6 +622,14 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	s->shapeCapacity = shapeCapacity;
 	s->worldResident = true;
+	{
+		// (the contact report's block and its "was touching" bytes, from the contacts just uploaded: contact_report.hip)
+		int rcReport = reportPrepare(s);
+		if (rcReport)
+		{
+			return rcReport;
+		}
+	}
 	if (s->optAsyncBuild != 0)
 	{
 		// (a stream for the first worker-thread build, made now while nothing is stepping: creating one later stalls the step that asks;
@@ -977,6 +986,13 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 			return rc;
 		}
 	}
+	s->reportStepFlags = 0;
+	if (s->reportFlags != 0 && (rc = reportEnqueue(s)) != 0)
+	{
+		// (the contact report of the attempt that stands, enqueued behind its impulse store and stage 4: a repeated step reports once;
+		// nothing waits for it here -- contact_report.hip)
+		return rc;
+	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;
 	{
@@ -1263,6 +1279,10 @@ int s2amd_world_set_contacts(s2amdSolver* s, const int32_t* slots, int32_t count
 																			  (const s2amdPairState*)(base + b0 + b1), (s2amdContact*)s->dContacts.p,
 																			  (s2amdPairState*)s->dPairs.p, (uint8_t*)s->dPointBytes.p, (int32_t*)s->dStatus.p);
 	HIP_TRY(hipGetLastError());
+	if ((rc = reportNoteSetContacts(s, (const int32_t*)base, count, (const s2amdContact*)(base + b0))) != 0)
+	{
+		return rc;
+	}
 	HIP_TRY(hipStreamSynchronize(st));
 	// the pair set changed: a contact created in a slot that held no live pair goes into the pair log; anything else (a pair taken
 	// away or replaced by the caller: its old key is the device's to know) has the key set sorted again

@@ -25,6 +25,7 @@ EXPORTS = [
     "s2amd_set_option", "s2amd_export_poses", "s2amd_export_poses_async", "s2amd_export_bodies_async", "s2amd_export_wait", "s2amd_measure_dominant", "s2amd_refit_shapes", "s2amd_find_pairs", "s2amd_synchronize", "s2amd_update_contacts", "s2amd_find_islands", "s2amd_color_constraints",
     "s2amd_world_upload", "s2amd_world_step", "s2amd_world_download", "s2amd_world_find_pairs", "s2amd_world_set_contacts",
     "s2amd_device_alloc", "s2amd_device_free", "s2amd_device_read", "s2amd_world_separated", "s2amd_world_download_boxes", "s2amd_world_set_refit_order", "s2amd_world_download_step", "s2amd_world_set_tree", "s2amd_world_get_tree",
+    "s2amd_world_set_report", "s2amd_world_touch_events", "s2amd_world_touching", "s2amd_world_body_sums",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -92,6 +93,10 @@ def load(fast=False):
     L.s2amd_world_set_tree.argtypes = [vp, i32, vp, i32, i32]
     L.s2amd_world_get_tree.argtypes = [vp, i32, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_download.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp]
+    L.s2amd_world_set_report.argtypes = [vp, i32]
+    L.s2amd_world_touch_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_touching.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_body_sums.argtypes = [vp, vp, i32]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -329,6 +334,7 @@ class Solver:
         assert origins.shape == (len(bodies), 2)
         self._ck(self._L.s2amd_world_upload(self._h, *self._args(bodies, contacts, joints), wire.as_ptr(shapes), len(shapes), wire.as_ptr(pairs),
                                          wire.as_ptr(origins)))
+        self._world_bodies = len(bodies)
 
     def world_step(self, params):
         """One s2World_Step minus pair creation on the resident world; returns the step's counters as a dict."""
@@ -398,6 +404,46 @@ class Solver:
         self._ck(self._L.s2amd_world_download(self._h, *self._args(bodies, contacts, joints), wire.as_ptr(shapes), len(shapes), wire.as_ptr(pairs),
                                            wire.as_ptr(origins), wire.as_ptr(status)))
         return bodies, contacts, joints, shapes, pairs, origins, status
+
+    # ---- contact report of the resident world (s2amd_world_set_report): what touches what, and how hard ----
+    def world_set_report(self, flags):
+        """wire.REPORT_* bits: what every world_step from the next one on compacts on the device (0: nothing, the default)."""
+        self._ck(self._L.s2amd_world_set_report(self._h, int(flags)))
+
+    def world_touch_events(self, expected=64):
+        """(began, ended): the contact slots that started / stopped touching in the last world_step, each ascending."""
+        cap_b = cap_e = max(int(expected), 1)
+        while True:
+            began, ended = np.zeros(cap_b, dtype=np.int32), np.zeros(cap_e, dtype=np.int32)
+            nb, ne = ctypes.c_int32(), ctypes.c_int32()
+            rc = self._L.s2amd_world_touch_events(self._h, wire.as_ptr(began), cap_b, ctypes.byref(nb), wire.as_ptr(ended), cap_e, ctypes.byref(ne))
+            if rc == -5 and (nb.value > cap_b or ne.value > cap_e):  # S2AMD_E_CAPACITY: the counts are set, nothing was consumed
+                cap_b, cap_e = max(cap_b, nb.value), max(cap_e, ne.value)
+                continue
+            self._ck(rc)
+            return began[: nb.value].copy(), ended[: ne.value].copy()
+
+    def world_touching(self, expected=1024):
+        """wire.touching_contact_dtype records of the contacts touching after the last world_step, ascending by slot."""
+        cap = max(int(expected), 1)
+        while True:
+            out = np.zeros(cap, dtype=wire.touching_contact_dtype)
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_touching(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:
+                cap = n.value
+                continue
+            self._ck(rc)
+            return out[: n.value].copy()
+
+    def world_body_sums(self, body_capacity=None):
+        """wire.body_contact_sum_dtype per body slot: net contact impulse, normal load and touching count after the last world_step
+        (body_capacity: that of the upload, which is the default)."""
+        if body_capacity is None:
+            body_capacity = getattr(self, "_world_bodies", 0)
+        out = np.zeros(int(body_capacity), dtype=wire.body_contact_sum_dtype)
+        self._ck(self._L.s2amd_world_body_sums(self._h, wire.as_ptr(out), len(out)))
+        return out
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

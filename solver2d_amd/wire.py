@@ -151,3 +151,14 @@ tree_node_dtype = np.dtype([("aabb", np.float32, 4), ("categoryBits", np.uint32)
 assert tree_node_dtype.itemsize == 48
 shape_box_dtype = np.dtype([("aabb", np.float32, 4), ("fatAABB", np.float32, 4), ("enlarged", np.int32)])
 assert shape_box_dtype.itemsize == 36
+
+# contact report of the resident world (include/solver2d_amd.h: s2amd_world_set_report)
+REPORT_TOUCH, REPORT_CONTACTS, REPORT_BODY_SUMS = 1, 2, 4
+REPORT_ALL = REPORT_TOUCH | REPORT_CONTACTS | REPORT_BODY_SUMS
+# s2amdTouchingContact, s2amdBodyContactSum
+touching_contact_dtype = np.dtype([("slot", np.int32), ("bodyA", np.int32), ("bodyB", np.int32), ("pointCount", np.uint8), ("persisted", np.uint8, 2),
+                                   ("pad", np.uint8), ("normal", np.float32, 2), ("point", np.float32, (2, 2)), ("separation", np.float32, 2),
+                                   ("normalImpulse", np.float32, 2), ("tangentImpulse", np.float32, 2)])
+assert touching_contact_dtype.itemsize == 64
+body_contact_sum_dtype = np.dtype([("impulse", np.float32, 2), ("normalImpulse", np.float32), ("touching", np.int32)])
+assert body_contact_sum_dtype.itemsize == 16

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""What the contact report costs per step, and what it replaces.  Two resident worlds under TGS_Soft 8/4 -- the standing base-N pyramid
+(every contact touching, nothing begins or ends) and wreck_world at base N (tests/world_chain.py: balls ploughing through the pile,
+contacts created and destroyed all the time, the whole loop per step as tools/churn_bench.py runs it) -- `--steps` steps after `--warmup`:
+
+    off        no report flag: s2amd_world_step as it always was
+    touch      S2AMD_REPORT_TOUCH      + s2amd_world_touch_events every step
+    contacts   S2AMD_REPORT_CONTACTS   + s2amd_world_touching every step
+    sums       S2AMD_REPORT_BODY_SUMS  + s2amd_world_body_sums every step
+    all        all three flags and all three getters
+    download   no report flag, and every step the s2amd_world_download of contacts, pairs, bodies and origins that a caller needs
+               today for the same information
+
+One JSON object per line and mode.  All read-backs land in buffers allocated once, through the raw C calls.
+
+    python tools/contact_report_bench.py --tree . --label this [--rep N] [--modes off,all,download] [--base 200]
+
+--tree: a directory that holds a built `solver2d_amd` package and `tests/world_chain.py` (this checkout: `.`; another commit: an export
+of it, built; a tree without the report API can run `off` and `download`).  Run two trees alternately, several repeats each, in ONE
+session, so that the run-to-run spread is known before a difference is read (profiles/contact_report.jsonl)."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--tree", default=".")
+ap.add_argument("--label", default="this")
+ap.add_argument("--rep", type=int, default=0)
+ap.add_argument("--modes", default="off,touch,contacts,sums,all,download")
+ap.add_argument("--worlds", default="pyramid,wreck")
+ap.add_argument("--base", type=int, default=200)
+ap.add_argument("--seed", type=int, default=3)
+ap.add_argument("--steps", type=int, default=200)
+ap.add_argument("--warmup", type=int, default=60)
+a = ap.parse_args()
+sys.path.insert(0, os.path.abspath(a.tree))
+from solver2d_amd import hip, synthetic, wire  # noqa: E402
+from tests import world_chain  # noqa: E402
+
+assert os.path.abspath(hip.__file__).startswith(os.path.abspath(a.tree)), hip.__file__
+FLAGS = {"off": 0, "download": 0, "touch": 1, "contacts": 2, "sums": 4, "all": 7}
+SOLVER = "TGS_Soft"
+
+
+def create_contacts(world, free, new_pairs):
+    """The caller's s2CreateContact on its own copy of the pool (tools/churn_bench.py)."""
+    n = len(new_pairs)
+    slots = np.array([free.pop() for _ in range(n)], dtype=np.int32)
+    contacts = np.zeros(n, dtype=wire.contact_dtype)
+    pairs = np.zeros(n, dtype=wire.pair_state_dtype)
+    contacts["bodyA"] = world["shapes"]["body"][new_pairs[:, 0]]
+    contacts["bodyB"] = world["shapes"]["body"][new_pairs[:, 1]]
+    contacts["friction"] = 0.6
+    contacts["constraintIndex"] = -1
+    pairs["shapeA"], pairs["shapeB"] = new_pairs[:, 0], new_pairs[:, 1]
+    return slots, contacts, pairs
+
+
+def run(world, mode, loop):
+    params = wire.StepParams.make(SOLVER, 1.0 / 60.0, 8, 4, True)
+    nb, nc = len(world["bodies"]), len(world["contacts"])
+    free = sorted(np.flatnonzero(world["pairs"]["shapeA"] < 0).tolist(), reverse=True)
+    flags = FLAGS[mode]
+    ms, touching, began, ended = [], 0, 0, 0
+    with hip.Solver(0) as s:
+        L, h = s._L, s._h
+        s.set_option("prebuild_solver", wire.SOLVER_ID[SOLVER])
+        if flags:
+            s.world_set_report(flags)
+        s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
+        if flags:
+            b_buf, e_buf = np.zeros(nc, dtype=np.int32), np.zeros(nc, dtype=np.int32)
+            t_buf = np.zeros(nc, dtype=wire.touching_contact_dtype)
+            s_buf = np.zeros(nb, dtype=wire.body_contact_sum_dtype)
+        if mode == "download":
+            d_bodies, d_contacts, d_pairs = np.zeros(nb, dtype=wire.body_dtype), np.zeros(nc, dtype=wire.contact_dtype), np.zeros(nc, dtype=wire.pair_state_dtype)
+            d_origins = np.zeros((nb, 2), dtype=np.float32)
+        n1, n2 = ctypes.c_int32(), ctypes.c_int32()
+        moved = 1 if loop else 0
+        for step in range(a.warmup + a.steps):
+            t0 = time.perf_counter()
+            if loop and moved > 0:
+                new = s.world_find_pairs()
+                if len(new):
+                    s.world_set_contacts(*create_contacts(world, free, new))
+            info = s.world_step(params)
+            if loop and info["separatedCount"] > 0:
+                free.extend(s.world_separated(info["separatedCount"]).tolist())
+            moved = info["movedCount"]
+            if flags & 1:
+                s._ck(L.s2amd_world_touch_events(h, wire.as_ptr(b_buf), nc, ctypes.byref(n1), wire.as_ptr(e_buf), nc, ctypes.byref(n2)))
+                began, ended = began + n1.value, ended + n2.value
+            if flags & 2:
+                s._ck(L.s2amd_world_touching(h, wire.as_ptr(t_buf), nc, ctypes.byref(n1)))
+                touching = n1.value
+            if flags & 4:
+                s._ck(L.s2amd_world_body_sums(h, wire.as_ptr(s_buf), nb))
+            if mode == "download":
+                s._ck(L.s2amd_world_download(h, wire.as_ptr(d_bodies), nb, wire.as_ptr(d_contacts), nc, None, 0, None, 0, wire.as_ptr(d_pairs), wire.as_ptr(d_origins), None))
+                touching = int(((d_contacts["pointCount"] > 0) & (d_pairs["shapeA"] >= 0)).sum()) if step == a.warmup + a.steps - 1 else touching
+            if step >= a.warmup:
+                ms.append(1e3 * (time.perf_counter() - t0))
+        active = info["activeContacts"]
+    ms.sort()
+    return {"step_ms_mean": round(sum(ms) / len(ms), 4), "step_ms_median": round(ms[len(ms) // 2], 4), "step_ms_p90": round(ms[(9 * len(ms)) // 10], 4),
+            "active_contacts_last": active, "touching_last": touching, "began_total": began, "ended_total": ended, "bodies": nb, "contact_slots": nc}
+
+
+for name in a.worlds.split(","):
+    world = synthetic.pyramid_world(a.base) if name == "pyramid" else world_chain.wreck_world(a.seed, a.base)
+    for mode in a.modes.split(","):
+        r = run(world_chain.copy_world(world), mode, name == "wreck")
+        r.update({"tree": a.label, "rep": a.rep, "world": "%s base %d" % (name, a.base), "solver": SOLVER, "mode": mode, "steps": a.steps, "warmup": a.warmup})
+        print(json.dumps(r), flush=True)
