@@ -454,6 +454,78 @@ int s2amd_world_touching(s2amdSolver* solver, s2amdTouchingContact* out, int32_t
 /* out[bodyCapacity of the upload] */
 int s2amd_world_body_sums(s2amdSolver* solver, s2amdBodyContactSum* out, int32_t bodyCapacity);
 
+/* (additive, API 5) The joint report: the joint half of what s2World_Draw, a ragdoll controller or a "what breaks" test reads -- anchors,
+ * angles, speeds, limit contacts, motor torque, reactions -- without moving the world.  s2World_Draw's joint pass (src/world.c:423,
+ * s2DrawJoint src/joint.c:469-505, s2DrawRevolute src/revolute_joint.c:942-984) and s2RevoluteJoint_GetMotorTorque
+ * (src/revolute_joint.c:929-940) read the same.  It has a setter and a flag space of its own (the contact report's flags above are
+ * unchanged); with a flag set, s2amd_world_step compacts the report on the device behind its stage 4 and behind the contact report,
+ * and the four getters below hand it out; with no flag set (the default) a step enqueues nothing for it.
+ * Everything is float32, one rounding per operation in the order stated, read from the resident arrays AFTER the step's stage 4:
+ * origins, bodies.rot, bodies.angularVelocity and the joints.  A joint slot is LIVE when type != S2AMD_JOINT_FREE.
+ *   anchorB (every type)  s2TransformPoint({origin, rot} of bodyB, localOriginAnchorB), include/solver2d/math.h:350-356 (src/joint.c:474-477).
+ *   revolute record       anchorA the same transform of bodyA's localOriginAnchorA; angle = s2RelativeAngle(rotB, rotA) - referenceAngle
+ *                         (math.h:320-327 with glibc's atan2f, src/revolute_joint.c:190); angularSpeed = wB - wA;
+ *                         axialImpulse = (motorImpulse + lowerImpulse) - upperImpulse (src/revolute_joint.c:137); impulse, motorImpulse,
+ *                         lowerImpulse and upperImpulse as stored.
+ *   mouse record          anchorA = targetA verbatim (what src/joint.c:485-492 draws); angle, lowerImpulse, upperImpulse = +0 whatever the
+ *                         wire record holds; angularSpeed = wB; axialImpulse = motorImpulse (src/mouse_joint.c:102-103).
+ *   S2AMD_JOINT_REPORT_STATES     one s2amdJointState per live slot, ascending by slot.
+ *   S2AMD_JOINT_REPORT_LIMITS     a revolute joint with enableLimit != 0 is AT ITS LOWER LIMIT when the stored lowerImpulse > 0 and AT ITS
+ *                         UPPER LIMIT when upperImpulse > 0.  `began`: the codes 2 * slot + side (side 0 lower, 1 upper) at the limit now
+ *                         that were not before the step; `ended`: the reverse.  Both ascending.  "Before" is, after s2amd_world_upload,
+ *                         the same rule on the uploaded joints.  A step the library repeats internally reports once, as finally
+ *                         executed (the report owns its state bytes).  The report states what the solver STORES: a solver that stores
+ *                         no limit impulses reports no events -- s2Solve_XPBD leaves lowerImpulse and upperImpulse at zero.
+ *   S2AMD_JOINT_REPORT_BODY_SUMS  per body slot, static and free ones included: sums from +0, left to right over the body's live joints in
+ *                         ascending slot order, within one joint the bodyA term before the bodyB term.  A revolute joint adds -impulse
+ *                         and -axialImpulse where the body is its bodyA, +impulse and +axialImpulse where it is its bodyB
+ *                         (src/revolute_joint.c:140-144); a mouse joint adds +impulse and +motorImpulse to its bodyB only and adds and
+ *                         counts nothing for its bodyA.  `joints` is the number of terms.  No floating-point atomics: the result is a
+ *                         pure function of the arrays.  (The body -> joint adjacency is built at s2amd_world_upload and when the report
+ *                         is turned on: no resident-world call changes a joint's type, bodyA or bodyB in between.)
+ *   s2amd_world_joint_summary   answers whenever ANY joint-report flag was set before the last step: the live and revolute joint counts,
+ *                         atLower / atUpper by the rule above, and the largest anchor gap: over the live revolute joints,
+ *                         g = dx * dx + dy * dy with d = anchorB - anchorA; the largest g wins, ties go to the lowest slot
+ *                         (maxGapSlot), a NaN g never wins; with no revolute joint (or none whose g is a number) maxGapSquared = -1.0f
+ *                         and maxGapSlot = -1.
+ * Errors as the contact report's: S2AMD_E_STATE without a resident world, when the getter's flag was not set before the last
+ * s2amd_world_step or no step has run since; S2AMD_E_CAPACITY when a buffer is too small -- the counts are set, nothing is consumed;
+ * s2amd_world_set_joint_report: S2AMD_E_INVALID for unknown bits; the flags hold from the next step on, across uploads.  The step gains
+ * no host wait: the getters wait. */
+#define S2AMD_JOINT_REPORT_STATES 1    /* one s2amdJointState per live joint slot */
+#define S2AMD_JOINT_REPORT_LIMITS 2    /* limit began / ended lists */
+#define S2AMD_JOINT_REPORT_BODY_SUMS 4 /* per body: net joint impulse, axial impulse, joint count */
+int s2amd_world_set_joint_report(s2amdSolver* solver, int32_t flags);
+typedef struct s2amdJointState /* 64 bytes */
+{
+	int32_t slot, type, bodyA, bodyB;
+	float anchorA[2], anchorB[2]; /* world space */
+	float impulse[2];
+	float axialImpulse, motorImpulse;
+	float angle, angularSpeed;
+	float lowerImpulse, upperImpulse;
+} s2amdJointState;
+typedef struct s2amdBodyJointSum /* 16 bytes */
+{
+	float impulse[2];
+	float axialImpulse;
+	int32_t joints;
+} s2amdBodyJointSum;
+typedef struct s2amdJointSummary /* 32 bytes */
+{
+	int32_t liveJoints, revoluteJoints, atLower, atUpper;
+	int32_t maxGapSlot;
+	float maxGapSquared;
+	int32_t pad[2];
+} s2amdJointSummary;
+int s2amd_world_joint_states(s2amdSolver* solver, s2amdJointState* out, int32_t capacity, int32_t* count);
+/* began / ended hold up to 2 * jointCapacity codes each */
+int s2amd_world_joint_limit_events(s2amdSolver* solver, int32_t* began, int32_t beganCapacity, int32_t* beganCount, int32_t* ended,
+								   int32_t endedCapacity, int32_t* endedCount);
+/* out[bodyCapacity of the upload] */
+int s2amd_world_body_joint_sums(s2amdSolver* solver, s2amdBodyJointSum* out, int32_t bodyCapacity);
+int s2amd_world_joint_summary(s2amdSolver* solver, s2amdJointSummary* out);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

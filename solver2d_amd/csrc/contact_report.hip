@@ -7,7 +7,7 @@
 //                                           flags; per-tile counts by wave ballots, then every tile adds up the counts before it and
 //                                           writes its entries at their ranks (the shape of movedCountKernel / movedWriteKernel in
 //                                           world.hip): three lists in ascending slot order without a sort, and the byte advances.
-//   reportBodyKeysKernel -> rocPRIM radix sort -> reportBodyRangesKernel -> reportBodySumKernel
+//   reportBodyKeysKernel -> rocPRIM radix sort -> reportBodyRangesKernel (report_common.h) -> reportBodySumKernel
 //                                           the per-body sums: two (body, entry) keys per contact slot (a slot that does not touch sorts
 //                                           behind every body), sorted STABLY by body so that a body's entries stay in slot order, then
 //                                           one wave per body gathers 64 entries at a time and adds their terms in list order.
@@ -15,11 +15,10 @@
 // The byte array is the report's own (not world.hip's pointBytes, which advance inside the retry loop of s2amd_world_step): the passes
 // are enqueued once per step, behind the attempt that stands, so a repeated step reports once.  All device memory is one block sized
 // by reportPrepare (at upload / set_report); a step allocates nothing and waits for nothing -- the getters do.
-#include "solver_internal.h"
+#include "report_common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#define S2_BLOCK 256
 #define S2_REPORT_STAGE 128 // terms one wave stages per batch of a body's list: 64 entries, two points each
 
 namespace
@@ -56,17 +55,6 @@ ReportLayout reportLayout(int nc, int nb, size_t sortTmpBytes)
 	l.sortTmp = take(sortTmpBytes);
 	l.total = at;
 	return l;
-}
-
-// bits of a body key: every body slot and the value `nb` itself (the key of an entry that does not touch)
-unsigned int bodyKeyBits(int nb)
-{
-	unsigned int bits = 1;
-	while (bits < 32 && (1u << bits) <= (unsigned int)nb)
-	{
-		bits += 1;
-	}
-	return bits;
 }
 
 __global__ __launch_bounds__(S2_BLOCK) void reportInitKernel(const s2amdContact* contacts, int n, uint8_t* was)
@@ -123,14 +111,6 @@ __global__ __launch_bounds__(S2_BLOCK) void reportCountKernel(const s2amdContact
 	}
 }
 
-// s2TransformPoint (include/solver2d/math.h:350-356), rot = {s, c}
-S2_DEV float2 transformPoint(float2 origin, float2 rot, float2 p)
-{
-	const float x = (rot.y * p.x - rot.x * p.y) + origin.x;
-	const float y = (rot.x * p.x + rot.y * p.y) + origin.y;
-	return make_float2(x, y);
-}
-
 // head[0..2] = {began, ended, touching} counts of the step; `flags`: which lists are wanted (the byte advances in any case)
 __global__ __launch_bounds__(S2_BLOCK) void reportWriteKernel(const s2amdContact* contacts, const s2amdPairState* pairs, uint8_t* was, int n, int tiles,
 															  const int* counts, const s2amdBody* bodies, const float2* origins, int nb, int flags, int32_t* head,
@@ -152,11 +132,7 @@ __global__ __launch_bounds__(S2_BLOCK) void reportWriteKernel(const s2amdContact
 	if (wave < 3)
 	{
 		// the tiles before this one: wave w adds up list w's counts
-		int partial = 0;
-		for (int b = lane; b < (int)blockIdx.x; b += 64)
-		{
-			partial += counts[wave * tiles + b];
-		}
+		int partial = tileCountsBefore(counts, tiles, wave, (int)blockIdx.x, lane);
 		for (int d = 32; d > 0; d >>= 1)
 		{
 			partial += __shfl_xor(partial, d);
@@ -244,56 +220,6 @@ __global__ __launch_bounds__(S2_BLOCK) void reportBodyKeysKernel(const s2amdCont
 	vals[e] = e;
 }
 
-// ranges[2 * body] .. ranges[2 * body + 1]: the body's run in the sorted entries (both zero, from the memset, for a body without any)
-__global__ __launch_bounds__(S2_BLOCK) void reportBodyRangesKernel(const uint32_t* keys, int n, int nb, int* ranges)
-{
-	const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-	if (e >= n)
-	{
-		return;
-	}
-	const uint32_t key = keys[e];
-	if (key >= (uint32_t)nb)
-	{
-		return;
-	}
-	if (e == 0 || keys[e - 1] != key)
-	{
-		ranges[2 * key] = e;
-	}
-	if (e == n - 1 || keys[e + 1] != key)
-	{
-		ranges[2 * key + 1] = e + 1;
-	}
-}
-
-S2_DEV float laneOf(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-
-S2_DEV void waveLdsOrder()
-{
-	// LDS operations of one wave execute in order: this only keeps the compiler from moving them across
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// acc += comp[0], += comp[1], ... in that order: one dependent add per term (jacobi_kernel.hip: addInOrder)
-S2_DEV float addInOrder(float acc, const float* comp, int n)
-{
-	int k = 0;
-	for (; k + 8 <= n; k += 8)
-	{
-		const float4 a = *(const float4*)(comp + k), b = *(const float4*)(comp + k + 4);
-		acc = acc + a.x, acc = acc + a.y, acc = acc + a.z, acc = acc + a.w;
-		acc = acc + b.x, acc = acc + b.y, acc = acc + b.z, acc = acc + b.w;
-	}
-	for (; k < n; ++k)
-	{
-		acc = acc + comp[k];
-	}
-	return acc;
-}
-
 // One wave per body slot.  64 entries of the body's run are gathered at once, their points' terms -- {P.x, P.y, normalImpulse}, P negated
 // where the body is the contact's bodyA -- compacted into the wave's staging rows in list order (point 0 before point 1), then lanes 0, 1
 // and 2 add one row each in that order.  A body with thousands of entries (a drum, the ground) costs one dependent add per term instead
@@ -359,11 +285,6 @@ __global__ __launch_bounds__(S2_BLOCK) void reportBodySumKernel(const s2amdConta
 		out.touching = count;
 		sums[body] = out;
 	}
-}
-
-dim3 gridFor(size_t n)
-{
-	return dim3((unsigned)((n + S2_BLOCK - 1) / S2_BLOCK));
 }
 
 ReportLayout layoutOf(const s2amdSolver* s)

@@ -531,6 +531,17 @@ struct SolverRest
 	int32_t hReportHead[4] = {0, 0, 0, 0}; // {began, ended, touching, 0}
 	DevBuf dReport;			 // one block, carved by reportLayout(): was-touching bytes, tile counts, head, the three lists, sort arrays, body sums
 	size_t reportSortTmpBytes = 0;
+	// joint report (joint_report.hip; s2amd_world_set_joint_report): the same shape, behind the contact report
+	int jointReportFlags = 0;	  // S2AMD_JOINT_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
+	int jointReportStepFlags = 0; // ... and what the last one did
+	bool jointReportHeadKnown = false; // hJointReportHead holds the last step's counts and summary
+	struct
+	{
+		int32_t counts[4]; // {live, began, ended, 0}
+		s2amdJointSummary summary;
+	} hJointReportHead = {};
+	DevBuf dJointReport;		  // one block, carved by jointReportLayout(): limit-state bytes, tile counts and partials, head, lists, records, adjacency, body sums
+	size_t jointReportSortTmpBytes = 0;
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -777,6 +788,11 @@ int syncDeadSlots(s2amdSolver* s);
 int reportPrepare(s2amdSolver* s);
 int reportNoteSetContacts(s2amdSolver* s, const int32_t* dSlots, int count, const s2amdContact* dNewContacts);
 int reportEnqueue(s2amdSolver* s);
+// joint_report.hip.  jointReportPrepare: the joint report's device block, its limit-state bytes from the resident joints and the
+// body -> joint adjacency (at s2amd_world_upload and when s2amd_world_set_joint_report turns the report on);
+// jointReportEnqueue: the step's passes on the solve stream, behind the attempt that stands
+int jointReportPrepare(s2amdSolver* s);
+int jointReportEnqueue(s2amdSolver* s);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

@@ -534,6 +534,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	}
 	s->worldResident = false;
 	s->reportStepFlags = 0;
+	s->jointReportStepFlags = 0;
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -626,6 +627,11 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		// (the contact report's block and its "was touching" bytes, from the contacts just uploaded: contact_report.hip)
 		int rcReport = reportPrepare(s);
 		if (rcReport)
+		{
+			return rcReport;
+		}
+		// (... and the joint report's: limit-state bytes and the body -> joint adjacency from the joints just uploaded: joint_report.hip)
+		if ((rcReport = jointReportPrepare(s)) != 0)
 		{
 			return rcReport;
 		}
@@ -992,6 +998,11 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 		// (the contact report of the attempt that stands, enqueued behind its impulse store and stage 4: a repeated step reports once;
 		// nothing waits for it here -- contact_report.hip)
 		return rc;
+	}
+	s->jointReportStepFlags = 0;
+	if (s->jointReportFlags != 0 && (rc = jointReportEnqueue(s)) != 0)
+	{
+		return rc; // (the joint report, the same way: joint_report.hip)
 	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;

@@ -26,6 +26,7 @@ EXPORTS = [
     "s2amd_world_upload", "s2amd_world_step", "s2amd_world_download", "s2amd_world_find_pairs", "s2amd_world_set_contacts",
     "s2amd_device_alloc", "s2amd_device_free", "s2amd_device_read", "s2amd_world_separated", "s2amd_world_download_boxes", "s2amd_world_set_refit_order", "s2amd_world_download_step", "s2amd_world_set_tree", "s2amd_world_get_tree",
     "s2amd_world_set_report", "s2amd_world_touch_events", "s2amd_world_touching", "s2amd_world_body_sums",
+    "s2amd_world_set_joint_report", "s2amd_world_joint_states", "s2amd_world_joint_limit_events", "s2amd_world_body_joint_sums", "s2amd_world_joint_summary",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -97,6 +98,11 @@ def load(fast=False):
     L.s2amd_world_touch_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_touching.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_body_sums.argtypes = [vp, vp, i32]
+    L.s2amd_world_set_joint_report.argtypes = [vp, i32]
+    L.s2amd_world_joint_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_joint_limit_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_body_joint_sums.argtypes = [vp, vp, i32]
+    L.s2amd_world_joint_summary.argtypes = [vp, vp]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -444,6 +450,53 @@ class Solver:
         out = np.zeros(int(body_capacity), dtype=wire.body_contact_sum_dtype)
         self._ck(self._L.s2amd_world_body_sums(self._h, wire.as_ptr(out), len(out)))
         return out
+
+    # ---- joint report of the resident world (s2amd_world_set_joint_report): joint states, limit events, reactions ----
+    def world_set_joint_report(self, flags):
+        """wire.JOINT_REPORT_* bits: what every world_step from the next one on compacts on the device (0: nothing, the default)."""
+        self._ck(self._L.s2amd_world_set_joint_report(self._h, int(flags)))
+
+    def world_joint_states(self, expected=256):
+        """wire.joint_state_dtype records of the live joint slots after the last world_step, ascending by slot."""
+        cap = max(int(expected), 1)
+        while True:
+            out = np.zeros(cap, dtype=wire.joint_state_dtype)
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_joint_states(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY: the count is set, nothing was consumed
+                cap = n.value
+                continue
+            self._ck(rc)
+            return out[: n.value].copy()
+
+    def world_joint_limit_events(self, expected=64):
+        """(began, ended): the codes 2 * slot + side (0 lower, 1 upper) of the joint limits that became / stopped being active in the
+        last world_step, each ascending."""
+        cap_b = cap_e = max(int(expected), 1)
+        while True:
+            began, ended = np.zeros(cap_b, dtype=np.int32), np.zeros(cap_e, dtype=np.int32)
+            nb, ne = ctypes.c_int32(), ctypes.c_int32()
+            rc = self._L.s2amd_world_joint_limit_events(self._h, wire.as_ptr(began), cap_b, ctypes.byref(nb), wire.as_ptr(ended), cap_e, ctypes.byref(ne))
+            if rc == -5 and (nb.value > cap_b or ne.value > cap_e):
+                cap_b, cap_e = max(cap_b, nb.value), max(cap_e, ne.value)
+                continue
+            self._ck(rc)
+            return began[: nb.value].copy(), ended[: ne.value].copy()
+
+    def world_body_joint_sums(self, body_capacity=None):
+        """wire.body_joint_sum_dtype per body slot: net joint impulse, axial impulse and joint count after the last world_step
+        (body_capacity: that of the upload, which is the default)."""
+        if body_capacity is None:
+            body_capacity = getattr(self, "_world_bodies", 0)
+        out = np.zeros(int(body_capacity), dtype=wire.body_joint_sum_dtype)
+        self._ck(self._L.s2amd_world_body_joint_sums(self._h, wire.as_ptr(out), len(out)))
+        return out
+
+    def world_joint_summary(self):
+        """One wire.joint_summary_dtype record: joint counts, limits active, the largest anchor gap after the last world_step."""
+        out = np.zeros(1, dtype=wire.joint_summary_dtype)
+        self._ck(self._L.s2amd_world_joint_summary(self._h, wire.as_ptr(out)))
+        return out[0]
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

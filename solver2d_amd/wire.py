@@ -162,3 +162,17 @@ touching_contact_dtype = np.dtype([("slot", np.int32), ("bodyA", np.int32), ("bo
 assert touching_contact_dtype.itemsize == 64
 body_contact_sum_dtype = np.dtype([("impulse", np.float32, 2), ("normalImpulse", np.float32), ("touching", np.int32)])
 assert body_contact_sum_dtype.itemsize == 16
+
+# joint report of the resident world (include/solver2d_amd.h: s2amd_world_set_joint_report)
+JOINT_REPORT_STATES, JOINT_REPORT_LIMITS, JOINT_REPORT_BODY_SUMS = 1, 2, 4
+JOINT_REPORT_ALL = JOINT_REPORT_STATES | JOINT_REPORT_LIMITS | JOINT_REPORT_BODY_SUMS
+# s2amdJointState, s2amdBodyJointSum, s2amdJointSummary
+joint_state_dtype = np.dtype([("slot", np.int32), ("type", np.int32), ("bodyA", np.int32), ("bodyB", np.int32), ("anchorA", np.float32, 2),
+                              ("anchorB", np.float32, 2), ("impulse", np.float32, 2), ("axialImpulse", np.float32), ("motorImpulse", np.float32),
+                              ("angle", np.float32), ("angularSpeed", np.float32), ("lowerImpulse", np.float32), ("upperImpulse", np.float32)])
+assert joint_state_dtype.itemsize == 64
+body_joint_sum_dtype = np.dtype([("impulse", np.float32, 2), ("axialImpulse", np.float32), ("joints", np.int32)])
+assert body_joint_sum_dtype.itemsize == 16
+joint_summary_dtype = np.dtype([("liveJoints", np.int32), ("revoluteJoints", np.int32), ("atLower", np.int32), ("atUpper", np.int32),
+                                ("maxGapSlot", np.int32), ("maxGapSquared", np.float32), ("pad", np.int32, 2)])
+assert joint_summary_dtype.itemsize == 32

@@ -11,9 +11,21 @@ contacts created and destroyed all the time, the whole loop per step as tools/ch
     download   no report flag, and every step the s2amd_world_download of contacts, pairs, bodies and origins that a caller needs
                today for the same information
 
+The joint report (s2amd_world_set_joint_report) is measured the same way on a jointed world with shapes -- world `jointed`: the
+--grid x --grid lattice of synthetic.joint_grid (every third joint limited to +-0.1 rad so that limits come and go), one small box
+per body that collides with nothing -- in the modes of --joint-modes:
+
+    off        no joint-report flag
+    states     S2AMD_JOINT_REPORT_STATES    + s2amd_world_joint_states every step
+    limits     S2AMD_JOINT_REPORT_LIMITS    + s2amd_world_joint_limit_events every step
+    sums       S2AMD_JOINT_REPORT_BODY_SUMS + s2amd_world_body_joint_sums every step
+    all        all three flags, their getters and s2amd_world_joint_summary
+    download   no flag, and every step the s2amd_world_download of joints, bodies and origins the report replaces
+
 One JSON object per line and mode.  All read-backs land in buffers allocated once, through the raw C calls.
 
     python tools/contact_report_bench.py --tree . --label this [--rep N] [--modes off,all,download] [--base 200]
+                                         [--worlds pyramid,wreck,jointed] [--joint-modes off,all,download] [--grid 64]
 
 --tree: a directory that holds a built `solver2d_amd` package and `tests/world_chain.py` (this checkout: `.`; another commit: an export
 of it, built; a tree without the report API can run `off` and `download`).  Run two trees alternately, several repeats each, in ONE
@@ -32,7 +44,9 @@ ap.add_argument("--tree", default=".")
 ap.add_argument("--label", default="this")
 ap.add_argument("--rep", type=int, default=0)
 ap.add_argument("--modes", default="off,touch,contacts,sums,all,download")
-ap.add_argument("--worlds", default="pyramid,wreck")
+ap.add_argument("--worlds", default="pyramid,wreck,jointed")
+ap.add_argument("--joint-modes", default="off,states,limits,sums,all,download")
+ap.add_argument("--grid", type=int, default=64)
 ap.add_argument("--base", type=int, default=200)
 ap.add_argument("--seed", type=int, default=3)
 ap.add_argument("--steps", type=int, default=200)
@@ -44,6 +58,7 @@ from tests import world_chain  # noqa: E402
 
 assert os.path.abspath(hip.__file__).startswith(os.path.abspath(a.tree)), hip.__file__
 FLAGS = {"off": 0, "download": 0, "touch": 1, "contacts": 2, "sums": 4, "all": 7}
+JOINT_FLAGS = {"off": 0, "download": 0, "states": 1, "limits": 2, "sums": 4, "all": 7}
 SOLVER = "TGS_Soft"
 
 
@@ -111,7 +126,73 @@ def run(world, mode, loop):
             "active_contacts_last": active, "touching_last": touching, "began_total": began, "ended_total": ended, "bodies": nb, "contact_slots": nc}
 
 
+def jointed_world(grid):
+    bodies, _, joints = synthetic.joint_grid(grid)
+    limited = np.arange(len(joints)) % 3 == 0
+    joints["enableLimit"][limited], joints["lowerAngle"][limited], joints["upperAngle"][limited] = 1, -0.1, 0.1
+    shapes = np.zeros(len(bodies), dtype=wire.shape_dtype)
+    for i, b in enumerate(bodies):
+        synthetic._box_shape(shapes[i], i, b["type"], 0.125, 0.125, b["position"][0], b["position"][1], i)
+    shapes["maskBits"] = 0
+    contacts = np.zeros(4, dtype=wire.contact_dtype)
+    contacts["constraintIndex"] = -1
+    pairs = np.zeros(4, dtype=wire.pair_state_dtype)
+    pairs["shapeA"] = pairs["shapeB"] = -1
+    return {"bodies": bodies, "contacts": contacts, "joints": joints, "shapes": shapes, "pairs": pairs,
+            "origins": np.ascontiguousarray(bodies["position"], dtype=np.float32).copy()}
+
+
+def run_joints(world, mode):
+    params = wire.StepParams.make(SOLVER, 1.0 / 60.0, 8, 4, True)
+    nb, nj = len(world["bodies"]), len(world["joints"])
+    flags = JOINT_FLAGS[mode]
+    ms, live, began, ended = [], 0, 0, 0
+    with hip.Solver(0) as s:
+        L, h = s._L, s._h
+        s.set_option("prebuild_solver", wire.SOLVER_ID[SOLVER])
+        if flags:
+            s.world_set_joint_report(flags)
+        s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
+        if flags:
+            b_buf, e_buf = np.zeros(2 * nj, dtype=np.int32), np.zeros(2 * nj, dtype=np.int32)
+            j_buf = np.zeros(nj, dtype=wire.joint_state_dtype)
+            s_buf = np.zeros(nb, dtype=wire.body_joint_sum_dtype)
+            m_buf = np.zeros(1, dtype=wire.joint_summary_dtype)
+        if mode == "download":
+            d_bodies, d_joints, d_origins = np.zeros(nb, dtype=wire.body_dtype), np.zeros(nj, dtype=wire.joint_dtype), np.zeros((nb, 2), dtype=np.float32)
+        n1, n2 = ctypes.c_int32(), ctypes.c_int32()
+        for step in range(a.warmup + a.steps):
+            t0 = time.perf_counter()
+            s.world_step(params)
+            if flags & 1:
+                s._ck(L.s2amd_world_joint_states(h, wire.as_ptr(j_buf), nj, ctypes.byref(n1)))
+                live = n1.value
+            if flags & 2:
+                s._ck(L.s2amd_world_joint_limit_events(h, wire.as_ptr(b_buf), 2 * nj, ctypes.byref(n1), wire.as_ptr(e_buf), 2 * nj, ctypes.byref(n2)))
+                began, ended = began + n1.value, ended + n2.value
+            if flags & 4:
+                s._ck(L.s2amd_world_body_joint_sums(h, wire.as_ptr(s_buf), nb))
+            if flags == 7:
+                s._ck(L.s2amd_world_joint_summary(h, wire.as_ptr(m_buf)))
+            if mode == "download":
+                s._ck(L.s2amd_world_download(h, wire.as_ptr(d_bodies), nb, None, 0, wire.as_ptr(d_joints), nj, None, 0, None, wire.as_ptr(d_origins), None))
+                live = int((d_joints["type"] != wire.JOINT_FREE).sum()) if step == a.warmup + a.steps - 1 else live
+            if step >= a.warmup:
+                ms.append(1e3 * (time.perf_counter() - t0))
+    ms.sort()
+    return {"step_ms_mean": round(sum(ms) / len(ms), 4), "step_ms_median": round(ms[len(ms) // 2], 4), "step_ms_p90": round(ms[(9 * len(ms)) // 10], 4),
+            "live_joints_last": live, "limits_began_total": began, "limits_ended_total": ended, "bodies": nb, "joint_slots": nj}
+
+
 for name in a.worlds.split(","):
+    if name == "jointed":
+        world = jointed_world(a.grid)
+        for mode in a.joint_modes.split(","):
+            r = run_joints(world_chain.copy_world(world), mode)
+            r.update({"tree": a.label, "rep": a.rep, "world": "joint grid %d x %d" % (a.grid, a.grid), "solver": SOLVER, "report": "joint", "mode": mode,
+                      "steps": a.steps, "warmup": a.warmup})
+            print(json.dumps(r), flush=True)
+        continue
     world = synthetic.pyramid_world(a.base) if name == "pyramid" else world_chain.wreck_world(a.seed, a.base)
     for mode in a.modes.split(","):
         r = run(world_chain.copy_world(world), mode, name == "wreck")

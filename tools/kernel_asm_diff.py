@@ -38,8 +38,10 @@ def kernels(path, renames=()):
     mangled = sorted(bodies)
     names = subprocess.run(["c++filt"] + mangled, capture_output=True, text=True, check=True).stdout.splitlines()
     out = {}
-    for m, n in zip(mangled, names):
-        n = re.sub(r"\(.*", "", n.replace("void ", ""))
+    short = [re.sub(r"\(.*", "", n.replace("void ", "")) for n in names]
+    for m, n, s in zip(mangled, names, short):
+        # (library kernels whose template arguments hold a parenthesis -- rocPRIM's sort kernels -- keep their whole name)
+        n = s if short.count(s) == 1 else n
         for pattern, to in renames:
             n = pattern.sub(to, n)
         assert n not in out, n
