@@ -466,6 +466,9 @@ struct SolverRest
 	hipStream_t side[2] = {nullptr, nullptr};
 	hipEvent_t evFork[2] = {nullptr, nullptr}, evJoin[4] = {nullptr, nullptr, nullptr, nullptr};
 	int optAsync = 0; // s2amd_step_resident returns after enqueueing; s2amd_synchronize collects errors
+	// an enqueued step records evBegin / evEnd only for a reader: a synchronous step (stats.deviceMs), a profiled one, or the world
+	// step, which enqueues its solve under "async" and reads the pair itself once it has waited (world.hip)
+	bool timeEnqueuedStep = false;
 	bool constraintIndexInPrologue = false;
 	int optFork = 0; // measured slower on MI355X (multi-branch graph replay costs more than the serial kernels): off
 

@@ -636,7 +636,13 @@ int doStep(s2amdSolver* s, const s2amdStepParams* params)
 	// with that part unswept
 	std::string variantMiss;
 	(void)s2amdTakeVariantMiss(nullptr); // (nothing left over from a call that failed earlier on this thread)
-	HIP_TRY(hipEventRecord(s->evBegin, s->stream));
+	// (the two markers cost stream time: a step that is only enqueued, with nobody to read them, goes without)
+	const bool async = s->optAsync != 0 && !q.profile;
+	const bool timed = !async || s->timeEnqueuedStep;
+	if (timed)
+	{
+		HIP_TRY(hipEventRecord(s->evBegin, s->stream));
+	}
 	if (useGraph)
 	{
 		uint64_t key = 1469598103934665603ull;
@@ -711,10 +717,12 @@ int doStep(s2amdSolver* s, const s2amdStepParams* params)
 			return fail(S2AMD_E_STATE, variantMiss);
 		}
 	}
-	HIP_TRY(hipEventRecord(s->evEnd, s->stream));
+	if (timed)
+	{
+		HIP_TRY(hipEventRecord(s->evEnd, s->stream));
+	}
 	HIP_TRY(hipGetLastError());
 	s->indexInWire = s->indexInWire || indexNow;
-	const bool async = s->optAsync != 0 && !q.profile;
 	if (!async)
 	{
 		HIP_TRY(hipStreamSynchronize(s->stream));

@@ -31,6 +31,11 @@
 #ifndef S2_PERSIST_INSTRUMENTED
 #define S2_PERSIST_INSTRUMENTED 0
 #endif
+// 1: the plain warm start prepares round 0 of the solve sweep behind it in its idle half (wideStepKernel: HOIST); 0 to measure
+// without -- `make variant NAME=nohoist EXTRA=-DS2_WIDE_HOIST_PREP=0`
+#ifndef S2_WIDE_HOIST_PREP
+#define S2_WIDE_HOIST_PREP 1
+#endif
 #define S2_WIDE_THREADS 512
 #define S2_WIDE_INTERIOR 256  // a colour batch of a strip has at most 256 constraints: interior round i runs on half i & 1 of the workgroup
 #define S2_WIDE_ROUNDS_PER_HALF (S2_STRIP_ROUNDS / 2) // ... so a lane holds three interior records
@@ -1232,6 +1237,13 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 	}
 	stampAt(1);
 
+	// Round 0 of a solve sweep that follows the plain warm start directly is prepared THERE, in the half that idles (OP_WARM below):
+	// prepWide reads the poses and the step's coefficients only, and nothing between the two ops changes either.  Every other way
+	// into a solve sweep -- a relax sweep behind s2IntegratePositions, a cold start, a sliced step's launches -- prepares it in place.
+	// (Not beside the overflow workgroup: eleven more live registers across its exchange cost those variants 36 bytes of scratch.)
+	constexpr bool HOIST = S2_WIDE_HOIST_PREP != 0 && !BODYWARM && !SLICED && !OVERFLOW;
+	WidePrep pre;
+	bool prepared = false; // `pre` holds round 0 of the next op
 	unsigned epoch = epoch0; // tags are the exchange number: the buffers are zero at launch (cleared by the previous step's epilogue), or (SELF) hold older tags only
 	int bad = 0;
 	for (int oi = 0; oi < opCount && !bad; ++oi)
@@ -1402,6 +1414,22 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 			// s2WarmStartContacts as a coloured sweep WITHOUT an exchange: a side's warm-start term depends on the impulses,
 			// the anchors and that body's own pose only, so every body this workgroup owns ends up with the right bits; the
 			// copies of the neighbours' bodies are refreshed by the next sweep's exchange before anything reads them
+			const bool hoist = HOIST && oi + 1 < opCount && lops[oi + 1].code == OP_SOLVE_SOFT;
+			// (half 0 has nothing to do in round 1: round 0 of the coming sweep, with that op's step constants)
+			auto prepNext = [&]() {
+				if (half == 0 && kOfSlot(0) >= 0)
+				{
+					const Op next = lops[oi + 1];
+					if (0 >= LL0)
+					{
+						pre = prepWide<RK, POINTS, true>(rA[0], ldq, lcoef, next.inv_h, next.useBias, salt, nullptr, localsOf(0));
+					}
+					else
+					{
+						pre = prepWide<RK, POINTS>(rA[0], ldq, lcoef, next.inv_h, next.useBias, salt, larms);
+					}
+				}
+			};
 #pragma unroll
 			for (int i = 0; i < ROUNDS; ++i)
 			{
@@ -1416,6 +1444,13 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 						else
 						{
 							warmWide<RK, POINTS>(rA[i >> 1], lvel, ldq, lmass, salt, larms + 2 * (i >> 1) * S2_WIDE_THREADS);
+						}
+					}
+					if constexpr (HOIST)
+					{
+						if (i == 1 && hoist)
+						{
+							prepNext();
 						}
 					}
 					__syncthreads();
@@ -1464,6 +1499,17 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 					__syncthreads();
 				}
 			}
+			if constexpr (HOIST)
+			{
+				if (hoist)
+				{
+					if (roundsA <= 1)
+					{
+						prepNext(); // (no idle round to hide it in: behind the last one)
+					}
+					prepared = true;
+				}
+			}
 			if constexpr (OVERFLOW)
 			{
 				bad = wideOverflowExchange(pv, lovf, lvel, ovCount, ++ovSweep);
@@ -1474,8 +1520,9 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 		{
 			// ---- interiors: round i's chain on half i & 1, while the other half prepares its round i + 1 (measured: 150 us per
 			// launch against 159 us with prep and chain back to back in the same lanes) ----
-			WidePrep pre;
-			if (half == 0 && kOfSlot(0) >= 0)
+			const bool fresh = !prepared; // (the warm start in front of this sweep has prepared round 0: above)
+			prepared = false;
+			if (fresh && half == 0 && kOfSlot(0) >= 0)
 			{
 				if (0 >= LL0)
 				{

@@ -851,6 +851,7 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	{
 		const int savedAsync = s->optAsync;
 		s->optAsync = 1;
+		s->timeEnqueuedStep = true; // (solveMs below)
 		const double td0 = debugAsync ? nowMs() : 0.0;
 		// (stage 4 rides in the solve's epilogue launch where that launch writes the bodies back -- contact_kernels.hip: storeImpulsesKernel --;
 		// a step without such a launch (a world of self-contained resident islands; a store that finalizes positions itself) gets the
@@ -861,6 +862,7 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 		s->stage4 = Stage4Args{};
 		tStep += debugAsync ? nowMs() - td0 : 0.0;
 		s->optAsync = savedAsync;
+		s->timeEnqueuedStep = false;
 		if (rc)
 		{
 			return rc;
