@@ -526,6 +526,67 @@ int s2amd_world_joint_limit_events(s2amdSolver* solver, int32_t* began, int32_t 
 int s2amd_world_body_joint_sums(s2amdSolver* solver, s2amdBodyJointSum* out, int32_t bodyCapacity);
 int s2amd_world_joint_summary(s2amdSolver* solver, s2amdJointSummary* out);
 
+/* (additive, API 5) The shape report: the shape half of what s2World_Draw, a culling pass, a camera fit or a "left the arena" trigger reads
+ * -- world-space vertices, the body's class, the boxes, what is on screen -- without moving the world.  s2World_Draw's shape pass
+ * (src/world.c:373-410, s2DrawShape :308-367) and its AABB pass (:427-460) read the same.  It has a setter and a flag space of its own
+ * (the flags of the two reports above are unchanged); with a flag set, s2amd_world_step compacts the report on the device behind its
+ * stage 4 and behind the joint report, and the three getters below hand it out; with no flag set (the default) a step enqueues nothing
+ * for it.  Everything is float32, one rounding per operation in the order stated, read from the resident arrays AFTER the step's stage 4:
+ * shapes, origins, bodies.rot, bodies.type and bodies.mass.
+ *   A shape slot is LIVE when type != S2AMD_SHAPE_FREE.  A live shape is IN VIEW when no view is set, or when
+ *   s2AABB_Overlaps(view, shape.aabb) holds as include/solver2d/aabb.h:111-123 writes it: false only when one of the four differences
+ *   aabb.lower - view.upper, view.lower - aabb.upper is > 0 -- a box that touches the view's edge is in view, and so is one with a NaN.
+ *   s2amd_world_set_shape_view   box = {lower.x, lower.y, upper.x, upper.y}, NULL: no view, every live shape is in view (the default).
+ *                         S2AMD_E_INVALID for lower > upper or a NaN.  Holds from the next step on, across uploads.
+ *   S2AMD_SHAPE_REPORT_DRAW    one s2amdShapeDraw per live shape in view, ascending by shape slot.  With the transform {origins[body],
+ *                         bodies[body].rot}: vertices[i] = s2TransformPoint(transform, shape.vertices[i]) in the operation order of
+ *                         include/solver2d/math.h:350-356 for i < vertexCount -- a polygon's count (taken as 0 below 0 and 8 above 8),
+ *                         2 for a capsule and a segment, 1 for a circle -- and +0 beyond; axis = s2RotateVector(rot, {1, 0})
+ *                         (math.h:330-341: {c * 1 - s * 0, s * 1 + c * 0}) for every type; bodyClass by the precedence of
+ *                         src/world.c:389-405: 3 for a dynamic body with mass == 0.0f before anything else, then 0 static, 1 kinematic,
+ *                         2 otherwise; radius, aabb and fatAABB verbatim.  The record names no colours: the class is what the
+ *                         reference picks them by.
+ *   S2AMD_SHAPE_REPORT_VIEW    `entered`: the shape slots in view now that were not in view before the step; `left`: the reverse.  Both
+ *                         ascending.  "Before" is the same rule on the resident shapes, evaluated at s2amd_world_upload, when the report
+ *                         is turned on and when s2amd_world_set_shape_view changes the view: the caller's own acts raise no events, and
+ *                         the step after a change of view reports against the new view.  A step the library repeats internally reports
+ *                         once, as finally executed (the report owns its state bytes).
+ *   S2AMD_SHAPE_REPORT_BOUNDS / s2amd_world_shape_summary   answers whenever ANY shape-report flag was set before the last step: liveShapes;
+ *                         inView; byType[t] the live shapes of type t = S2AMD_SHAPE_CAPSULE .. S2AMD_SHAPE_SEGMENT; badBodyShapes the
+ *                         live shapes on bodies of class 3; movableBounds over shape.aabb of the live shapes whose body is neither
+ *                         static nor free; viewBounds over shape.aabb of the shapes in view, static ones included.  A box starts as
+ *                         {+INF, +INF, -INF, -INF} -- also the answer when no shape qualifies -- and takes the shapes in ascending slot
+ *                         order: lower = x < cur ? x : cur, upper = x > cur ? x : cur.  A NaN never wins.
+ * Errors as the other reports': S2AMD_E_STATE without a resident world, when the getter's flag was not set before the last
+ * s2amd_world_step or no step has run since; S2AMD_E_CAPACITY when a buffer is too small -- the counts are set, nothing is consumed;
+ * s2amd_world_set_shape_report: S2AMD_E_INVALID for unknown bits; the flags hold from the next step on, across uploads.  The step gains
+ * no host wait: the getters wait. */
+#define S2AMD_SHAPE_REPORT_DRAW 1   /* one s2amdShapeDraw per live shape in view */
+#define S2AMD_SHAPE_REPORT_VIEW 2   /* entered / left lists */
+#define S2AMD_SHAPE_REPORT_BOUNDS 4 /* summary incl. world bounds */
+int s2amd_world_set_shape_report(s2amdSolver* solver, int32_t flags);
+int s2amd_world_set_shape_view(s2amdSolver* solver, const float* box /* {lx,ly,ux,uy}; NULL = everything */);
+typedef struct s2amdShapeDraw /* 128 bytes = two 64-byte lines */
+{
+	int32_t shape, body, type, vertexCount; /* valid entries of vertices[]: polygon count; capsule, segment 2; circle 1 */
+	int32_t bodyClass;                      /* 0 static, 1 kinematic, 2 dynamic, 3 dynamic with mass == 0 */
+	float radius;
+	float axis[2];                          /* s2RotateVector(rot, {1, 0}) */
+	float vertices[8][2];                   /* world space; unused entries +0 */
+	float aabb[4], fatAABB[4];              /* as resident after stage 4 */
+} s2amdShapeDraw;
+typedef struct s2amdShapeSummary /* 64 bytes */
+{
+	int32_t liveShapes, inView, byType[4], badBodyShapes, pad;
+	float movableBounds[4];                 /* over live shapes of non-static bodies */
+	float viewBounds[4];                    /* over the shapes in view, static ones included */
+} s2amdShapeSummary;
+int s2amd_world_shape_draws(s2amdSolver* solver, s2amdShapeDraw* out, int32_t capacity, int32_t* count);
+/* entered / left hold up to shapeCapacity slots each */
+int s2amd_world_shape_view_events(s2amdSolver* solver, int32_t* entered, int32_t enteredCapacity, int32_t* enteredCount, int32_t* left,
+								  int32_t leftCapacity, int32_t* leftCount);
+int s2amd_world_shape_summary(s2amdSolver* solver, s2amdShapeSummary* out);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

@@ -1,6 +1,6 @@
-// What the two reports of the resident world share (contact_report.hip, joint_report.hip): the ordered compaction's tile-prefix step,
-// the body-range kernel behind the stable radix sort by body, and the one-wave ordered sum's pieces.  Everything is in an unnamed
-// namespace: each of the two files holds its own copy of the kernel below under the same name.
+// What the reports of the resident world share (contact_report.hip, joint_report.hip, shape_report.hip): the ordered compaction's
+// tile-prefix step, the body-range kernel behind the stable radix sort by body, and the one-wave ordered sum's pieces.  Everything is in
+// an unnamed namespace: each of the files holds its own copy of the kernel below under the same name.
 #pragma once
 
 #include "solver_internal.h"

@@ -545,6 +545,18 @@ struct SolverRest
 	} hJointReportHead = {};
 	DevBuf dJointReport;		  // one block, carved by jointReportLayout(): limit-state bytes, tile counts and partials, head, lists, records, adjacency, body sums
 	size_t jointReportSortTmpBytes = 0;
+	// shape report (shape_report.hip; s2amd_world_set_shape_report, s2amd_world_set_shape_view): the same shape, behind the joint report
+	int shapeReportFlags = 0;	  // S2AMD_SHAPE_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
+	int shapeReportStepFlags = 0; // ... and what the last one did
+	bool shapeReportHeadKnown = false; // hShapeReportHead holds the last step's counts and summary
+	bool shapeViewSet = false;	  // false: every live shape is in view
+	float shapeView[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // {lower.x, lower.y, upper.x, upper.y}
+	struct
+	{
+		int32_t counts[4]; // {in view, entered, left, 0}
+		s2amdShapeSummary summary;
+	} hShapeReportHead = {};
+	DevBuf dShapeReport;		  // one block, carved by shapeReportLayout(): in-view state bytes, tile counts and partials, head, lists, records
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -796,6 +808,14 @@ int reportEnqueue(s2amdSolver* s);
 // jointReportEnqueue: the step's passes on the solve stream, behind the attempt that stands
 int jointReportPrepare(s2amdSolver* s);
 int jointReportEnqueue(s2amdSolver* s);
+// shape_report.hip.  shapeReportPrepare: the shape report's device block and its in-view state bytes from the resident shapes under the
+// view as set (at s2amd_world_upload and when s2amd_world_set_shape_report turns the report on); shapeReportEnqueue: the step's passes on
+// the solve stream, behind the joint report
+int shapeReportPrepare(s2amdSolver* s);
+int shapeReportEnqueue(s2amdSolver* s);
+// where the report's head -- int32 counts[4] = {in view, entered, left, 0}, then s2amdShapeSummary -- lies in dShapeReport (the host-side
+// check of tests/hostcheck writes one there, in place of the kernels it cannot run)
+size_t shapeReportHeadOffset(const s2amdSolver* s);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

@@ -535,6 +535,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	s->worldResident = false;
 	s->reportStepFlags = 0;
 	s->jointReportStepFlags = 0;
+	s->shapeReportStepFlags = 0;
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -632,6 +633,11 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		}
 		// (... and the joint report's: limit-state bytes and the body -> joint adjacency from the joints just uploaded: joint_report.hip)
 		if ((rcReport = jointReportPrepare(s)) != 0)
+		{
+			return rcReport;
+		}
+		// (... and the shape report's: in-view state bytes from the shapes just uploaded, under the view as set: shape_report.hip)
+		if ((rcReport = shapeReportPrepare(s)) != 0)
 		{
 			return rcReport;
 		}
@@ -1005,6 +1011,11 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	if (s->jointReportFlags != 0 && (rc = jointReportEnqueue(s)) != 0)
 	{
 		return rc; // (the joint report, the same way: joint_report.hip)
+	}
+	s->shapeReportStepFlags = 0;
+	if (s->shapeReportFlags != 0 && (rc = shapeReportEnqueue(s)) != 0)
+	{
+		return rc; // (the shape report, the same way: shape_report.hip)
 	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;

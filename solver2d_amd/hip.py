@@ -27,6 +27,7 @@ EXPORTS = [
     "s2amd_device_alloc", "s2amd_device_free", "s2amd_device_read", "s2amd_world_separated", "s2amd_world_download_boxes", "s2amd_world_set_refit_order", "s2amd_world_download_step", "s2amd_world_set_tree", "s2amd_world_get_tree",
     "s2amd_world_set_report", "s2amd_world_touch_events", "s2amd_world_touching", "s2amd_world_body_sums",
     "s2amd_world_set_joint_report", "s2amd_world_joint_states", "s2amd_world_joint_limit_events", "s2amd_world_body_joint_sums", "s2amd_world_joint_summary",
+    "s2amd_world_set_shape_report", "s2amd_world_set_shape_view", "s2amd_world_shape_draws", "s2amd_world_shape_view_events", "s2amd_world_shape_summary",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -103,6 +104,11 @@ def load(fast=False):
     L.s2amd_world_joint_limit_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_body_joint_sums.argtypes = [vp, vp, i32]
     L.s2amd_world_joint_summary.argtypes = [vp, vp]
+    L.s2amd_world_set_shape_report.argtypes = [vp, i32]
+    L.s2amd_world_set_shape_view.argtypes = [vp, vp]
+    L.s2amd_world_shape_draws.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_shape_view_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_shape_summary.argtypes = [vp, vp]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -496,6 +502,52 @@ class Solver:
         """One wire.joint_summary_dtype record: joint counts, limits active, the largest anchor gap after the last world_step."""
         out = np.zeros(1, dtype=wire.joint_summary_dtype)
         self._ck(self._L.s2amd_world_joint_summary(self._h, wire.as_ptr(out)))
+        return out[0]
+
+    # ---- shape report of the resident world (s2amd_world_set_shape_report): draw records, view events, bounds ----
+    def world_set_shape_report(self, flags):
+        """wire.SHAPE_REPORT_* bits: what every world_step from the next one on compacts on the device (0: nothing, the default)."""
+        self._ck(self._L.s2amd_world_set_shape_report(self._h, int(flags)))
+
+    def world_set_shape_view(self, box):
+        """The view box (lower.x, lower.y, upper.x, upper.y) the report culls to from the next world_step on; None: every live shape."""
+        if box is None:
+            self._ck(self._L.s2amd_world_set_shape_view(self._h, None))
+            return
+        box = np.ascontiguousarray(box, dtype=np.float32)
+        assert box.shape == (4,)
+        self._ck(self._L.s2amd_world_set_shape_view(self._h, wire.as_ptr(box)))
+
+    def world_shape_draws(self, expected=1024):
+        """wire.shape_draw_dtype records of the live shapes in view after the last world_step, ascending by shape slot."""
+        cap = max(int(expected), 1)
+        while True:
+            out = np.zeros(cap, dtype=wire.shape_draw_dtype)
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_shape_draws(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY: the count is set, nothing was consumed
+                cap = n.value
+                continue
+            self._ck(rc)
+            return out[: n.value].copy()
+
+    def world_shape_view_events(self, expected=64):
+        """(entered, left): the shape slots that came into / went out of view in the last world_step, each ascending."""
+        cap_e = cap_l = max(int(expected), 1)
+        while True:
+            entered, left = np.zeros(cap_e, dtype=np.int32), np.zeros(cap_l, dtype=np.int32)
+            ne, nl = ctypes.c_int32(), ctypes.c_int32()
+            rc = self._L.s2amd_world_shape_view_events(self._h, wire.as_ptr(entered), cap_e, ctypes.byref(ne), wire.as_ptr(left), cap_l, ctypes.byref(nl))
+            if rc == -5 and (ne.value > cap_e or nl.value > cap_l):
+                cap_e, cap_l = max(cap_e, ne.value), max(cap_l, nl.value)
+                continue
+            self._ck(rc)
+            return entered[: ne.value].copy(), left[: nl.value].copy()
+
+    def world_shape_summary(self):
+        """One wire.shape_summary_dtype record: shape counts, shapes in view, the movable and the in-view bounds after the last world_step."""
+        out = np.zeros(1, dtype=wire.shape_summary_dtype)
+        self._ck(self._L.s2amd_world_shape_summary(self._h, wire.as_ptr(out)))
         return out[0]
 
     def find_islands(self, bodies, contacts, joints):

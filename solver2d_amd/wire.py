@@ -176,3 +176,15 @@ assert body_joint_sum_dtype.itemsize == 16
 joint_summary_dtype = np.dtype([("liveJoints", np.int32), ("revoluteJoints", np.int32), ("atLower", np.int32), ("atUpper", np.int32),
                                 ("maxGapSlot", np.int32), ("maxGapSquared", np.float32), ("pad", np.int32, 2)])
 assert joint_summary_dtype.itemsize == 32
+
+# shape report of the resident world (include/solver2d_amd.h: s2amd_world_set_shape_report, s2amd_world_set_shape_view)
+SHAPE_REPORT_DRAW, SHAPE_REPORT_VIEW, SHAPE_REPORT_BOUNDS = 1, 2, 4
+SHAPE_REPORT_ALL = SHAPE_REPORT_DRAW | SHAPE_REPORT_VIEW | SHAPE_REPORT_BOUNDS
+# s2amdShapeDraw, s2amdShapeSummary
+shape_draw_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("type", np.int32), ("vertexCount", np.int32), ("bodyClass", np.int32),
+                             ("radius", np.float32), ("axis", np.float32, 2), ("vertices", np.float32, (8, 2)), ("aabb", np.float32, 4),
+                             ("fatAABB", np.float32, 4)])
+assert shape_draw_dtype.itemsize == 128
+shape_summary_dtype = np.dtype([("liveShapes", np.int32), ("inView", np.int32), ("byType", np.int32, 4), ("badBodyShapes", np.int32), ("pad", np.int32),
+                                ("movableBounds", np.float32, 4), ("viewBounds", np.float32, 4)])
+assert shape_summary_dtype.itemsize == 64

@@ -22,10 +22,23 @@ per body that collides with nothing -- in the modes of --joint-modes:
     all        all three flags, their getters and s2amd_world_joint_summary
     download   no flag, and every step the s2amd_world_download of joints, bodies and origins the report replaces
 
+The shape report (s2amd_world_set_shape_report, s2amd_world_set_shape_view) is measured the same way on the standing base-N pyramid --
+world `shaped`: 20,101 shapes at base 200 -- once with a view that holds about a tenth of the shapes (the middle tenth of their centres
+along x, every y) and once with none, in the modes of --shape-modes:
+
+    off            no shape-report flag
+    draw           S2AMD_SHAPE_REPORT_DRAW   + s2amd_world_shape_draws every step
+    view           S2AMD_SHAPE_REPORT_VIEW   + s2amd_world_shape_view_events every step
+    bounds         S2AMD_SHAPE_REPORT_BOUNDS + s2amd_world_shape_summary every step
+    all            all three flags and all three getters
+    download       no flag, and every step the s2amd_world_download of shapes, bodies and origins the report replaces
+    download_step  no flag, and every step s2amd_world_download_step: poses only, transforms and culling left to the host
+
 One JSON object per line and mode.  All read-backs land in buffers allocated once, through the raw C calls.
 
     python tools/contact_report_bench.py --tree . --label this [--rep N] [--modes off,all,download] [--base 200]
-                                         [--worlds pyramid,wreck,jointed] [--joint-modes off,all,download] [--grid 64]
+                                         [--worlds pyramid,wreck,jointed,shaped] [--joint-modes off,all,download] [--grid 64]
+                                         [--shape-modes off,all,download,download_step]
 
 --tree: a directory that holds a built `solver2d_amd` package and `tests/world_chain.py` (this checkout: `.`; another commit: an export
 of it, built; a tree without the report API can run `off` and `download`).  Run two trees alternately, several repeats each, in ONE
@@ -46,6 +59,7 @@ ap.add_argument("--rep", type=int, default=0)
 ap.add_argument("--modes", default="off,touch,contacts,sums,all,download")
 ap.add_argument("--worlds", default="pyramid,wreck,jointed")
 ap.add_argument("--joint-modes", default="off,states,limits,sums,all,download")
+ap.add_argument("--shape-modes", default="off,draw,view,bounds,all,download,download_step")
 ap.add_argument("--grid", type=int, default=64)
 ap.add_argument("--base", type=int, default=200)
 ap.add_argument("--seed", type=int, default=3)
@@ -59,6 +73,7 @@ from tests import world_chain  # noqa: E402
 assert os.path.abspath(hip.__file__).startswith(os.path.abspath(a.tree)), hip.__file__
 FLAGS = {"off": 0, "download": 0, "touch": 1, "contacts": 2, "sums": 4, "all": 7}
 JOINT_FLAGS = {"off": 0, "download": 0, "states": 1, "limits": 2, "sums": 4, "all": 7}
+SHAPE_FLAGS = {"off": 0, "download": 0, "download_step": 0, "draw": 1, "view": 2, "bounds": 4, "all": 7}
 SOLVER = "TGS_Soft"
 
 
@@ -184,7 +199,71 @@ def run_joints(world, mode):
             "live_joints_last": live, "limits_began_total": began, "limits_ended_total": ended, "bodies": nb, "joint_slots": nj}
 
 
+def tenth_view(world):
+    """A box that holds about a tenth of the live shapes: the middle tenth of their box centres along x, every y."""
+    shapes = world["shapes"]
+    box = shapes["aabb"][shapes["type"] != wire.SHAPE_FREE]
+    cx = 0.5 * (box[:, 0] + box[:, 2])
+    lo, hi = np.quantile(cx, [0.45, 0.55])
+    return np.array([lo, box[:, 1].min() - 1.0, hi, box[:, 3].max() + 1.0], dtype=np.float32)
+
+
+def run_shapes(world, mode, view):
+    params = wire.StepParams.make(SOLVER, 1.0 / 60.0, 8, 4, True)
+    nb, ns = len(world["bodies"]), len(world["shapes"])
+    flags = SHAPE_FLAGS[mode]
+    ms, in_view, entered, left = [], 0, 0, 0
+    with hip.Solver(0) as s:
+        L, h = s._L, s._h
+        s.set_option("prebuild_solver", wire.SOLVER_ID[SOLVER])
+        if flags:
+            s.world_set_shape_report(flags)
+            s.world_set_shape_view(view)
+        s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
+        if flags:
+            e_buf, l_buf = np.zeros(ns, dtype=np.int32), np.zeros(ns, dtype=np.int32)
+            d_buf = np.zeros(ns, dtype=wire.shape_draw_dtype)
+            m_buf = np.zeros(1, dtype=wire.shape_summary_dtype)
+        if mode == "download":
+            d_bodies, d_shapes, d_origins = np.zeros(nb, dtype=wire.body_dtype), np.zeros(ns, dtype=wire.shape_dtype), np.zeros((nb, 2), dtype=np.float32)
+        if mode == "download_step":
+            d_poses, d_moved = np.zeros((nb, 4), dtype=np.float32), np.zeros(ns, dtype=np.dtype([("shape", np.int32), ("fatAABB", np.float32, 4)]))
+        n1, n2 = ctypes.c_int32(), ctypes.c_int32()
+        for step in range(a.warmup + a.steps):
+            t0 = time.perf_counter()
+            s.world_step(params)
+            if flags & 1:
+                s._ck(L.s2amd_world_shape_draws(h, wire.as_ptr(d_buf), ns, ctypes.byref(n1)))
+                in_view = n1.value
+            if flags & 2:
+                s._ck(L.s2amd_world_shape_view_events(h, wire.as_ptr(e_buf), ns, ctypes.byref(n1), wire.as_ptr(l_buf), ns, ctypes.byref(n2)))
+                entered, left = entered + n1.value, left + n2.value
+            if flags & 4:
+                s._ck(L.s2amd_world_shape_summary(h, wire.as_ptr(m_buf)))
+                in_view = int(m_buf[0]["inView"])
+            if mode == "download":
+                s._ck(L.s2amd_world_download(h, wire.as_ptr(d_bodies), nb, None, 0, None, 0, wire.as_ptr(d_shapes), ns, None, wire.as_ptr(d_origins), None))
+            if mode == "download_step":
+                s._ck(L.s2amd_world_download_step(h, wire.as_ptr(d_poses), nb, wire.as_ptr(d_moved), ns, ctypes.byref(n1)))
+            if step >= a.warmup:
+                ms.append(1e3 * (time.perf_counter() - t0))
+    ms.sort()
+    return {"step_ms_mean": round(sum(ms) / len(ms), 4), "step_ms_median": round(ms[len(ms) // 2], 4), "step_ms_p90": round(ms[(9 * len(ms)) // 10], 4),
+            "in_view_last": in_view, "entered_total": entered, "left_total": left, "bodies": nb, "shape_slots": ns}
+
+
 for name in a.worlds.split(","):
+    if name == "shaped":
+        world = synthetic.pyramid_world(a.base)
+        for view_name, view in (("tenth", tenth_view(world)), ("none", None)):
+            for mode in a.shape_modes.split(","):
+                if view_name == "none" and SHAPE_FLAGS[mode] == 0:
+                    continue  # (without a flag the view is not looked at: these rows are the ones above)
+                r = run_shapes(world_chain.copy_world(world), mode, view)
+                r.update({"tree": a.label, "rep": a.rep, "world": "pyramid base %d" % a.base, "solver": SOLVER, "report": "shape", "view": view_name,
+                          "mode": mode, "steps": a.steps, "warmup": a.warmup})
+                print(json.dumps(r), flush=True)
+        continue
     if name == "jointed":
         world = jointed_world(a.grid)
         for mode in a.joint_modes.split(","):
