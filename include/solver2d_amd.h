@@ -587,6 +587,88 @@ int s2amd_world_shape_view_events(s2amdSolver* solver, int32_t* entered, int32_t
 								  int32_t leftCapacity, int32_t* leftCount);
 int s2amd_world_shape_summary(s2amdSolver* solver, s2amdShapeSummary* out);
 
+/* (additive, API 5) The body report: what a HUD, a trail, a sound trigger, a recorder or a "may I stop stepping" test asks of the bodies
+ * -- velocities, which poses changed, which bodies came to rest or woke up, which islands exist and whether a whole pile is at rest --
+ * without moving the world.  The fourth setter and flag space (the flags of the three reports above are unchanged); with a flag set,
+ * s2amd_world_step compacts the report on the device behind its stage 4 and behind the shape report, and the getters below hand it out;
+ * with no flag set (the default) a step enqueues nothing for it.  The reference has no sleeping and the solve skips nobody: "at rest" is
+ * something the report says, never something the step acts on.  Everything is float32, one rounding per operation in the order stated,
+ * read from the resident arrays AFTER the step's stage 4: bodies, origins, contacts, joints.
+ *   A body slot is REPORTED when its type is neither S2AMD_BODY_FREE nor S2AMD_BODY_STATIC.
+ *   S2AMD_BODY_REPORT_STATES   one s2amdBodyState per reported body, ascending by slot: origin = origins[slot]; position, rot and the
+ *                         velocities verbatim; angle = s2Rot_GetAngle(rot) = atan2f(rot.s, rot.c) (include/solver2d/math.h:267-270, what
+ *                         s2Body_GetAngle returns; glibc's atan2f); speedSquared = vx * vx + vy * vy; restTime the body's timer (below);
+ *                         island the index into the island list, -1 without ISLANDS; flags bit 0 MOVED, bit 1 AT REST, bit 2 the body's
+ *                         island is at rest (0 without ISLANDS).
+ *   MOVED                 the 16 bytes {origin.x, origin.y, rot.s, rot.c}, compared as four uint32, differ from the copy the report keeps
+ *                         from before the step.  The copy is taken at s2amd_world_upload and when the report is turned on (flags from 0 to
+ *                         non-zero), and refreshed by every reporting step.
+ *   S2AMD_BODY_REPORT_MOVED_ONLY   modifies STATES: only the reported bodies that moved are listed.
+ *   S2AMD_BODY_REPORT_REST     The report owns one float timer per body slot: +0 after an upload and whenever the flags go from 0 to non-zero.
+ *                         A step with ANY flag set advances the timer of every reported body: the body is a candidate when
+ *                         speedSquared <= lin2 && w * w <= ang2 (a NaN on either side fails), lin2 = linearSpeed * linearSpeed and
+ *                         ang2 = angularSpeed * angularSpeed rounded once on the host; timer = candidate ? timer + dt : +0 with that
+ *                         step's params->dt.  AT REST: timer >= seconds.  `rested`: the slots at rest now that were not at rest before
+ *                         the step; `woke`: the reverse; both ascending.  "At rest before" is the same rule on the timer as it stood
+ *                         before the step under the thresholds as they are now, so s2amd_world_set_rest_thresholds -- the caller's own
+ *                         act -- raises no event.  A step with every flag at 0 advances nothing.
+ *   s2amd_world_set_rest_thresholds   defaults 0.01f, 0.0349065850f (2 degrees / s), 0.5f; S2AMD_E_INVALID for a negative value or a NaN
+ *                         (the thresholds that hold stay); holds from the next step on, across uploads.
+ *   S2AMD_BODY_REPORT_ISLANDS  the islands of the world as it stands after the step, by the rule of s2amd_find_islands below on the
+ *                         resident arrays: MOVABLE bodies (reported, invMass != 0 || invI != 0) are joined by contacts with
+ *                         pointCount > 0 and by revolute joints between two of them; every other reported body is an island of its own;
+ *                         an edge that names a body outside [0, bodyCapacity) joins nothing.  Islands are numbered by their lowest body
+ *                         slot, which is firstBody.  A touching contact / a live joint counts (contactCount, jointCount) for the island
+ *                         of bodyA when bodyA is movable, else for that of bodyB when it is movable, else for none; a mouse joint looks at
+ *                         bodyB only.  restingBodies: the island's bodies at rest -- the island is AT REST when that equals bodyCount;
+ *                         minRestTime the minimum of their timers; fastestBody / maxSpeedSquared the largest speedSquared, of equal ones
+ *                         the lowest slot, a NaN never wins, -1 and -1.0f when every speed is a NaN.
+ *   s2amd_world_body_summary   answers whenever ANY body-report flag was set before the last step: bodies (reported), dynamicBodies,
+ *                         kinematicBodies, movedBodies, restingBodies; islands, restingIslands, largestIsland (most bodies, of equal ones
+ *                         the lowest index), largestIslandBodies -- 0, 0, -1, 0 without ISLANDS; fastestBody / maxSpeedSquared by the
+ *                         per-island rule over all reported bodies; pad is 0.
+ * Errors as the other reports': S2AMD_E_STATE without a resident world, when the getter's flag was not set before the last
+ * s2amd_world_step or no step has run since; S2AMD_E_CAPACITY when a buffer is too small -- the counts are set, nothing is consumed;
+ * s2amd_world_set_body_report: S2AMD_E_INVALID for unknown bits; the flags hold from the next step on, across uploads.  The step gains
+ * no host wait: the getters wait.  A step the library repeats internally reports once, as finally executed.
+ * Byte for byte this is what libs2amd.so returns; libs2amd_fast.so builds the same code under its own contraction rule
+ * (speedSquared and w * w may be fused there). */
+#define S2AMD_BODY_REPORT_STATES 1     /* one s2amdBodyState per reported body */
+#define S2AMD_BODY_REPORT_REST 2       /* rested / woke lists */
+#define S2AMD_BODY_REPORT_ISLANDS 4    /* islands of the world as it stands after the step */
+#define S2AMD_BODY_REPORT_MOVED_ONLY 8 /* modifies STATES: only bodies whose pose changed in the step */
+#define S2AMD_BODY_STATE_MOVED 1
+#define S2AMD_BODY_STATE_AT_REST 2
+#define S2AMD_BODY_STATE_ISLAND_AT_REST 4
+int s2amd_world_set_body_report(s2amdSolver* solver, int32_t flags);
+int s2amd_world_set_rest_thresholds(s2amdSolver* solver, float linearSpeed, float angularSpeed, float seconds);
+typedef struct s2amdBodyState /* 64 bytes = one line */
+{
+	int32_t slot, type, island, flags; /* flags: S2AMD_BODY_STATE_* */
+	float origin[2], position[2], rot[2]; /* rot = {s, c} */
+	float angle, angularVelocity;
+	float linearVelocity[2];
+	float restTime, speedSquared;
+} s2amdBodyState;
+typedef struct s2amdIslandState /* 32 bytes */
+{
+	int32_t firstBody, bodyCount, contactCount, jointCount, restingBodies, fastestBody;
+	float maxSpeedSquared, minRestTime;
+} s2amdIslandState;
+typedef struct s2amdBodySummary /* 64 bytes */
+{
+	int32_t bodies, dynamicBodies, kinematicBodies, movedBodies, restingBodies;
+	int32_t islands, restingIslands, largestIsland, largestIslandBodies, fastestBody;
+	float maxSpeedSquared;
+	int32_t pad[5];
+} s2amdBodySummary;
+int s2amd_world_body_states(s2amdSolver* solver, s2amdBodyState* out, int32_t capacity, int32_t* count);
+/* rested / woke hold up to bodyCapacity slots each */
+int s2amd_world_body_rest_events(s2amdSolver* solver, int32_t* rested, int32_t restedCapacity, int32_t* restedCount, int32_t* woke,
+								 int32_t wokeCapacity, int32_t* wokeCount);
+int s2amd_world_islands(s2amdSolver* solver, s2amdIslandState* out, int32_t capacity, int32_t* count);
+int s2amd_world_body_summary(s2amdSolver* solver, s2amdBodySummary* out);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

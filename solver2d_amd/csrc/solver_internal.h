@@ -557,6 +557,17 @@ struct SolverRest
 		s2amdShapeSummary summary;
 	} hShapeReportHead = {};
 	DevBuf dShapeReport;		  // one block, carved by shapeReportLayout(): in-view state bytes, tile counts and partials, head, lists, records
+	// body report (body_report.hip; s2amd_world_set_body_report, s2amd_world_set_rest_thresholds): the same shape, behind the shape report
+	int bodyReportFlags = 0;	 // S2AMD_BODY_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
+	int bodyReportStepFlags = 0; // ... and what the last one did
+	bool bodyReportHeadKnown = false; // hBodyReportHead holds the last step's counts and summary
+	float restLinearSpeed = 0.01f, restAngularSpeed = 0.0349065850f, restSeconds = 0.5f; // s2amd_world_set_rest_thresholds
+	struct
+	{
+		int32_t counts[4]; // {records, rested, woke, islands}
+		s2amdBodySummary summary;
+	} hBodyReportHead = {};
+	DevBuf dBodyReport;			 // one block, carved by bodyReportLayout(): pose copies, timers, state bytes, union-find, island sums, tile counts, head, lists, records
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -816,6 +827,14 @@ int shapeReportEnqueue(s2amdSolver* s);
 // where the report's head -- int32 counts[4] = {in view, entered, left, 0}, then s2amdShapeSummary -- lies in dShapeReport (the host-side
 // check of tests/hostcheck writes one there, in place of the kernels it cannot run)
 size_t shapeReportHeadOffset(const s2amdSolver* s);
+// body_report.hip.  bodyReportPrepare: the body report's device block, its pose copies from the resident bodies and its timers at +0 (at
+// s2amd_world_upload and when s2amd_world_set_body_report turns the report on); bodyReportEnqueue: the step's passes on the step's stream
+// behind stage 4 (never part of the captured graph); `dt` is the step's params->dt.
+int bodyReportPrepare(s2amdSolver* s);
+int bodyReportEnqueue(s2amdSolver* s, float dt);
+// where the report's head -- int32 counts[4] = {records, rested, woke, islands}, then s2amdBodySummary -- lies in dBodyReport (the
+// host-side sanitizer program writes it in place of the kernels)
+size_t bodyReportHeadOffset(const s2amdSolver* s);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

@@ -536,6 +536,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	s->reportStepFlags = 0;
 	s->jointReportStepFlags = 0;
 	s->shapeReportStepFlags = 0;
+	s->bodyReportStepFlags = 0;
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -638,6 +639,11 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		}
 		// (... and the shape report's: in-view state bytes from the shapes just uploaded, under the view as set: shape_report.hip)
 		if ((rcReport = shapeReportPrepare(s)) != 0)
+		{
+			return rcReport;
+		}
+		// (... and the body report's: pose copies from the bodies just uploaded, timers at +0: body_report.hip)
+		if ((rcReport = bodyReportPrepare(s)) != 0)
 		{
 			return rcReport;
 		}
@@ -1016,6 +1022,11 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	if (s->shapeReportFlags != 0 && (rc = shapeReportEnqueue(s)) != 0)
 	{
 		return rc; // (the shape report, the same way: shape_report.hip)
+	}
+	s->bodyReportStepFlags = 0;
+	if (s->bodyReportFlags != 0 && (rc = bodyReportEnqueue(s, params->dt)) != 0)
+	{
+		return rc; // (the body report, the same way: body_report.hip)
 	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;

@@ -28,6 +28,8 @@ EXPORTS = [
     "s2amd_world_set_report", "s2amd_world_touch_events", "s2amd_world_touching", "s2amd_world_body_sums",
     "s2amd_world_set_joint_report", "s2amd_world_joint_states", "s2amd_world_joint_limit_events", "s2amd_world_body_joint_sums", "s2amd_world_joint_summary",
     "s2amd_world_set_shape_report", "s2amd_world_set_shape_view", "s2amd_world_shape_draws", "s2amd_world_shape_view_events", "s2amd_world_shape_summary",
+    "s2amd_world_set_body_report", "s2amd_world_set_rest_thresholds", "s2amd_world_body_states", "s2amd_world_body_rest_events", "s2amd_world_islands",
+    "s2amd_world_body_summary",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -109,6 +111,12 @@ def load(fast=False):
     L.s2amd_world_shape_draws.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_shape_view_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_shape_summary.argtypes = [vp, vp]
+    L.s2amd_world_set_body_report.argtypes = [vp, i32]
+    L.s2amd_world_set_rest_thresholds.argtypes = [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    L.s2amd_world_body_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_body_rest_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_islands.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_body_summary.argtypes = [vp, vp]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -548,6 +556,54 @@ class Solver:
         """One wire.shape_summary_dtype record: shape counts, shapes in view, the movable and the in-view bounds after the last world_step."""
         out = np.zeros(1, dtype=wire.shape_summary_dtype)
         self._ck(self._L.s2amd_world_shape_summary(self._h, wire.as_ptr(out)))
+        return out[0]
+
+    # ---- body report of the resident world (s2amd_world_set_body_report): states, rest events, islands ----
+    def world_set_body_report(self, flags):
+        """wire.BODY_REPORT_* bits: what every world_step from the next one on compacts on the device (0: nothing, the default)."""
+        self._ck(self._L.s2amd_world_set_body_report(self._h, int(flags)))
+
+    def world_set_rest_thresholds(self, linear_speed, angular_speed, seconds):
+        """At rest: speed <= linear_speed and |w| <= angular_speed for `seconds`; holds from the next world_step on."""
+        self._ck(self._L.s2amd_world_set_rest_thresholds(self._h, float(np.float32(linear_speed)), float(np.float32(angular_speed)), float(np.float32(seconds))))
+
+    def _world_body_list(self, fn, dtype, expected):
+        cap = max(int(expected), 1)
+        while True:
+            out = np.zeros(cap, dtype=dtype)
+            n = ctypes.c_int32()
+            rc = fn(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY: the count is set, nothing was consumed
+                cap = n.value
+                continue
+            self._ck(rc)
+            return out[: n.value].copy()
+
+    def world_body_states(self, expected=1024):
+        """wire.body_state_dtype records of the reported bodies (under MOVED_ONLY: the moved ones) after the last world_step, ascending by slot."""
+        return self._world_body_list(self._L.s2amd_world_body_states, wire.body_state_dtype, expected)
+
+    def world_body_rest_events(self, expected=64):
+        """(rested, woke): the body slots that came to rest / woke up in the last world_step, each ascending."""
+        cap_r = cap_w = max(int(expected), 1)
+        while True:
+            rested, woke = np.zeros(cap_r, dtype=np.int32), np.zeros(cap_w, dtype=np.int32)
+            nr, nw = ctypes.c_int32(), ctypes.c_int32()
+            rc = self._L.s2amd_world_body_rest_events(self._h, wire.as_ptr(rested), cap_r, ctypes.byref(nr), wire.as_ptr(woke), cap_w, ctypes.byref(nw))
+            if rc == -5 and (nr.value > cap_r or nw.value > cap_w):
+                cap_r, cap_w = max(cap_r, nr.value), max(cap_w, nw.value)
+                continue
+            self._ck(rc)
+            return rested[: nr.value].copy(), woke[: nw.value].copy()
+
+    def world_islands(self, expected=256):
+        """wire.island_state_dtype records of the islands of the world as it stands after the last world_step, by lowest body slot."""
+        return self._world_body_list(self._L.s2amd_world_islands, wire.island_state_dtype, expected)
+
+    def world_body_summary(self):
+        """One wire.body_summary_dtype record: body, rest and island counts, the largest island, the fastest body after the last world_step."""
+        out = np.zeros(1, dtype=wire.body_summary_dtype)
+        self._ck(self._L.s2amd_world_body_summary(self._h, wire.as_ptr(out)))
         return out[0]
 
     def find_islands(self, bodies, contacts, joints):

@@ -188,3 +188,20 @@ assert shape_draw_dtype.itemsize == 128
 shape_summary_dtype = np.dtype([("liveShapes", np.int32), ("inView", np.int32), ("byType", np.int32, 4), ("badBodyShapes", np.int32), ("pad", np.int32),
                                 ("movableBounds", np.float32, 4), ("viewBounds", np.float32, 4)])
 assert shape_summary_dtype.itemsize == 64
+
+# body report of the resident world (include/solver2d_amd.h: s2amd_world_set_body_report, s2amd_world_set_rest_thresholds)
+BODY_REPORT_STATES, BODY_REPORT_REST, BODY_REPORT_ISLANDS, BODY_REPORT_MOVED_ONLY = 1, 2, 4, 8
+BODY_REPORT_ALL = BODY_REPORT_STATES | BODY_REPORT_REST | BODY_REPORT_ISLANDS | BODY_REPORT_MOVED_ONLY
+BODY_STATE_MOVED, BODY_STATE_AT_REST, BODY_STATE_ISLAND_AT_REST = 1, 2, 4
+# s2amdBodyState, s2amdIslandState, s2amdBodySummary
+body_state_dtype = np.dtype([("slot", np.int32), ("type", np.int32), ("island", np.int32), ("flags", np.int32), ("origin", np.float32, 2),
+                             ("position", np.float32, 2), ("rot", np.float32, 2), ("angle", np.float32), ("angularVelocity", np.float32),
+                             ("linearVelocity", np.float32, 2), ("restTime", np.float32), ("speedSquared", np.float32)])
+assert body_state_dtype.itemsize == 64
+island_state_dtype = np.dtype([("firstBody", np.int32), ("bodyCount", np.int32), ("contactCount", np.int32), ("jointCount", np.int32),
+                               ("restingBodies", np.int32), ("fastestBody", np.int32), ("maxSpeedSquared", np.float32), ("minRestTime", np.float32)])
+assert island_state_dtype.itemsize == 32
+body_summary_dtype = np.dtype([("bodies", np.int32), ("dynamicBodies", np.int32), ("kinematicBodies", np.int32), ("movedBodies", np.int32),
+                               ("restingBodies", np.int32), ("islands", np.int32), ("restingIslands", np.int32), ("largestIsland", np.int32),
+                               ("largestIslandBodies", np.int32), ("fastestBody", np.int32), ("maxSpeedSquared", np.float32), ("pad", np.int32, 5)])
+assert body_summary_dtype.itemsize == 64

@@ -34,11 +34,23 @@ along x, every y) and once with none, in the modes of --shape-modes:
     download       no flag, and every step the s2amd_world_download of shapes, bodies and origins the report replaces
     download_step  no flag, and every step s2amd_world_download_step: poses only, transforms and culling left to the host
 
+The body report (s2amd_world_set_body_report) is measured the same way -- world `bodies`: the standing base-N pyramid (20,100 bodies at
+base 200, all of them one island) and 512 pyramids of base 40 (420,352 bodies, 512 islands) -- in the modes of --body-modes:
+
+    off        no body-report flag
+    states     S2AMD_BODY_REPORT_STATES  + s2amd_world_body_states every step
+    moved      ... with S2AMD_BODY_REPORT_MOVED_ONLY
+    rest       S2AMD_BODY_REPORT_REST    + s2amd_world_body_rest_events every step
+    islands    S2AMD_BODY_REPORT_ISLANDS + s2amd_world_islands every step
+    all        STATES, REST and ISLANDS, their getters and s2amd_world_body_summary
+    download   no flag, and every step what the report replaces: the s2amd_world_download of bodies, origins, contacts and joints, then
+               islands.find_islands on the host
+
 One JSON object per line and mode.  All read-backs land in buffers allocated once, through the raw C calls.
 
     python tools/contact_report_bench.py --tree . --label this [--rep N] [--modes off,all,download] [--base 200]
-                                         [--worlds pyramid,wreck,jointed,shaped] [--joint-modes off,all,download] [--grid 64]
-                                         [--shape-modes off,all,download,download_step]
+                                         [--worlds pyramid,wreck,jointed,shaped,bodies] [--joint-modes off,all,download] [--grid 64]
+                                         [--shape-modes off,all,download,download_step] [--body-modes off,all,download]
 
 --tree: a directory that holds a built `solver2d_amd` package and `tests/world_chain.py` (this checkout: `.`; another commit: an export
 of it, built; a tree without the report API can run `off` and `download`).  Run two trees alternately, several repeats each, in ONE
@@ -60,6 +72,7 @@ ap.add_argument("--modes", default="off,touch,contacts,sums,all,download")
 ap.add_argument("--worlds", default="pyramid,wreck,jointed")
 ap.add_argument("--joint-modes", default="off,states,limits,sums,all,download")
 ap.add_argument("--shape-modes", default="off,draw,view,bounds,all,download,download_step")
+ap.add_argument("--body-modes", default="off,states,moved,rest,islands,all,download")
 ap.add_argument("--grid", type=int, default=64)
 ap.add_argument("--base", type=int, default=200)
 ap.add_argument("--seed", type=int, default=3)
@@ -74,6 +87,7 @@ assert os.path.abspath(hip.__file__).startswith(os.path.abspath(a.tree)), hip.__
 FLAGS = {"off": 0, "download": 0, "touch": 1, "contacts": 2, "sums": 4, "all": 7}
 JOINT_FLAGS = {"off": 0, "download": 0, "states": 1, "limits": 2, "sums": 4, "all": 7}
 SHAPE_FLAGS = {"off": 0, "download": 0, "download_step": 0, "draw": 1, "view": 2, "bounds": 4, "all": 7}
+BODY_FLAGS = {"off": 0, "download": 0, "states": 1, "moved": 9, "rest": 2, "islands": 4, "all": 7}
 SOLVER = "TGS_Soft"
 
 
@@ -252,7 +266,60 @@ def run_shapes(world, mode, view):
             "in_view_last": in_view, "entered_total": entered, "left_total": left, "bodies": nb, "shape_slots": ns}
 
 
+def run_bodies(world, mode):
+    params = wire.StepParams.make(SOLVER, 1.0 / 60.0, 8, 4, True)
+    nb, nc, nj = len(world["bodies"]), len(world["contacts"]), len(world["joints"])
+    flags = BODY_FLAGS[mode]
+    ms, records, rested, woke, n_islands = [], 0, 0, 0, 0
+    with hip.Solver(0) as s:
+        L, h = s._L, s._h
+        s.set_option("prebuild_solver", wire.SOLVER_ID[SOLVER])
+        if flags:
+            s.world_set_body_report(flags)
+        s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
+        if flags:
+            r_buf, w_buf = np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int32)
+            b_buf = np.zeros(nb, dtype=wire.body_state_dtype)
+            i_buf = np.zeros(nb, dtype=wire.island_state_dtype)
+            m_buf = np.zeros(1, dtype=wire.body_summary_dtype)
+        if mode == "download":
+            from solver2d_amd import islands
+            d_bodies, d_contacts, d_joints = np.zeros(nb, dtype=wire.body_dtype), np.zeros(nc, dtype=wire.contact_dtype), np.zeros(nj, dtype=wire.joint_dtype)
+            d_origins = np.zeros((nb, 2), dtype=np.float32)
+        n1, n2 = ctypes.c_int32(), ctypes.c_int32()
+        for step in range(a.warmup + a.steps):
+            t0 = time.perf_counter()
+            s.world_step(params)
+            if flags & 1:
+                s._ck(L.s2amd_world_body_states(h, wire.as_ptr(b_buf), nb, ctypes.byref(n1)))
+                records = n1.value
+            if flags & 2:
+                s._ck(L.s2amd_world_body_rest_events(h, wire.as_ptr(r_buf), nb, ctypes.byref(n1), wire.as_ptr(w_buf), nb, ctypes.byref(n2)))
+                rested, woke = rested + n1.value, woke + n2.value
+            if flags & 4:
+                s._ck(L.s2amd_world_islands(h, wire.as_ptr(i_buf), nb, ctypes.byref(n1)))
+                n_islands = n1.value
+            if flags == 7:
+                s._ck(L.s2amd_world_body_summary(h, wire.as_ptr(m_buf)))
+            if mode == "download":
+                s._ck(L.s2amd_world_download(h, wire.as_ptr(d_bodies), nb, wire.as_ptr(d_contacts), nc, wire.as_ptr(d_joints), nj, None, 0, None, wire.as_ptr(d_origins), None))
+                _, n_islands = islands.find_islands(d_bodies, d_contacts, d_joints)
+            if step >= a.warmup:
+                ms.append(1e3 * (time.perf_counter() - t0))
+    ms.sort()
+    return {"step_ms_mean": round(sum(ms) / len(ms), 4), "step_ms_median": round(ms[len(ms) // 2], 4), "step_ms_p90": round(ms[(9 * len(ms)) // 10], 4),
+            "records_last": records, "rested_total": rested, "woke_total": woke, "islands_last": n_islands, "bodies": nb, "contact_slots": nc}
+
+
 for name in a.worlds.split(","):
+    if name == "bodies":
+        for world_name, world in (("pyramid base %d" % a.base, synthetic.pyramid_world(a.base)), ("512 x pyramid base 40", synthetic.pyramid_world(40, 512))):
+            for mode in a.body_modes.split(","):
+                r = run_bodies(world_chain.copy_world(world), mode)
+                r.update({"tree": a.label, "rep": a.rep, "world": world_name, "solver": SOLVER, "report": "body", "mode": mode, "steps": a.steps,
+                          "warmup": a.warmup})
+                print(json.dumps(r), flush=True)
+        continue
     if name == "shaped":
         world = synthetic.pyramid_world(a.base)
         for view_name, view in (("tenth", tenth_view(world)), ("none", None)):
