@@ -669,6 +669,85 @@ int s2amd_world_body_rest_events(s2amdSolver* solver, int32_t* rested, int32_t r
 int s2amd_world_islands(s2amdSolver* solver, s2amdIslandState* out, int32_t capacity, int32_t* count);
 int s2amd_world_body_summary(s2amdSolver* solver, s2amdBodySummary* out);
 
+/* (additive, API 5) The step metrics: how well the solver did in a step -- how deep the contacts still sit, how fast bodies still
+ * approach, whether the energy drifts, whether the joints pull apart -- without moving the world, and with a history: what the samples of
+ * the reference are watched for.  A fifth, independent facility behind the four reports (their flags are unchanged); with a flag set,
+ * every s2amd_world_step reduces the world as it stands after its stage 4 -- what s2amd_world_download would return -- to ONE 128-byte
+ * s2amdStepMetrics on the device and stores it in a ring in device memory; s2amd_world_metrics hands out the last record,
+ * s2amd_world_metrics_history the whole history in one read.  With no flag set (the default) a step enqueues nothing for it.
+ * Everything is float32, one rounding per operation in the order stated, read from the resident arrays AFTER the step's stage 4:
+ * bodies, origins, contacts, pairs, joints.
+ *   o_X = origins[X]; q_X = bodies[X].rot = {s, c}; T(X, p) = s2TransformPoint({o_X, q_X}, p) (include/solver2d/math.h:350-356):
+ *   ((c * p.x - s * p.y) + o.x, (s * p.x + c * p.y) + o.y).
+ *   PSUM                  the one shape of every float sum.  The terms are indexed by slot over the array's whole capacity; a slot that
+ *                         contributes nothing has the term +0.0f.  The slots are cut into tiles of 256 consecutive slots, the last tile
+ *                         padded with +0.0f.  Inside a tile, eight levels: at level k = 0..7, t[i] = t[i] + t[i + 2^k] for every i that is
+ *                         a multiple of 2^(k+1) (in numpy, eight rounds of x = x[:, 0::2] + x[:, 1::2]).  The tile sums are then added left
+ *                         to right from +0.0f.  No floating-point atomics: the result is a pure function of the arrays.  Of a sum that is
+ *                         a NaN only "is a NaN" is specified, not its bits.
+ *   S2AMD_METRICS_CONTACTS   A contact slot is TOUCHING as the contact report defines it (pair slot live, pointCount > 0), and not
+ *                         touching when it names a body outside [0, bodyCapacity); pointCount above 2 counts as 2.  For point j of a
+ *                         touching slot with bodies A, B and n = normal: d = T(B, localAnchorB) - T(A, localAnchorA) componentwise;
+ *                         gap = (d.x * n.x + d.y * n.y) + separation.  For X in {A, B}: a = localAnchorX - localCenter_X;
+ *                         r = (c * a.x - s * a.y, s * a.x + c * a.y); u_X = (v.x - w * r.y, v.y + w * r.x) with X's velocities;
+ *                         e = u_B - u_A; vn = e.x * n.x + e.y * n.y.
+ *                         touchingContacts, touchingPoints: the counts.  penetratingPoints: the points with gap < -0.005f
+ *                         (s2_linearSlop); approachingPoints: those with vn < 0.  minGap / minGapSlot: the smallest gap; of equal gaps
+ *                         the lowest slot (inside a slot the lower point) wins, a NaN never wins; +0.0f and -1 without a point whose gap
+ *                         is a number.  maxApproachSpeed / maxApproachSlot: the largest -vn over the points with vn < 0 under the same
+ *                         rules; +0.0f and -1 with none.  sumPenetration: PSUM over the contact slots, a touching slot's term p0 for one
+ *                         point and p0 + p1 for two, p = gap < 0 ? -gap : +0.0f.  sumNormalImpulse: the same PSUM with the points'
+ *                         normalImpulse.
+ *   S2AMD_METRICS_BODIES  over the body slots whose type is neither S2AMD_BODY_FREE nor S2AMD_BODY_STATIC; energyBodies their count.
+ *                         Each a PSUM over the body slots: kineticEnergy of ((0.5f * mass) * (vx * vx + vy * vy)) + ((0.5f * I) * (w * w));
+ *                         potentialEnergy of -((mass * gravityScale) * (gx * position.x + gy * position.y)) with that step's
+ *                         params->gravity; momentum of mass * vx and mass * vy; spin of I * w.
+ *   S2AMD_METRICS_JOINTS  over the live revolute joints: g = dx * dx + dy * dy, d = T(bodyB, localOriginAnchorB) - T(bodyA,
+ *                         localOriginAnchorA) (a body outside the array stands at the origin, unrotated, as in the joint report).
+ *                         revoluteJoints the count; maxJointGapSquared / maxJointGapSlot exactly by the rule of
+ *                         s2amd_world_joint_summary: the largest g, ties to the lowest slot, a NaN never wins, -1.0f and -1 with none;
+ *                         sumJointGapSquared: PSUM of g over the joint slots.
+ *   Every record          step: the number of records written since the recorder was restarted; flags: as set; solverType, dt: that
+ *                         step's params.  The fields of a section whose flag is off are zero bytes; pad is 0.
+ *   The recorder          s2amd_world_set_metrics: S2AMD_E_INVALID for unknown bits, and for a historyLength outside 1..4096 while
+ *                         flags != 0 (the length is ignored when flags is 0; what was set before stays).  Every accepted call restarts
+ *                         the recorder -- the ring is empty, the next record has step 0 --, and so does every s2amd_world_upload.  Flags
+ *                         and length hold from the next step on, across uploads.  A step with flags != 0 writes one record into ring
+ *                         position step % historyLength; a step with flags 0 writes nothing and advances nothing.  A step the library
+ *                         repeats internally records once, as finally executed.
+ *   s2amd_world_metrics   the last step's record; S2AMD_E_STATE without a resident world, when no step has run since the restart, or
+ *                         when the flags were 0 before the last step.
+ *   s2amd_world_metrics_history   the last min(records written, historyLength) records, oldest first: their `step` values are
+ *                         consecutive.  *count is always set (it may be 0); S2AMD_E_CAPACITY when capacity < *count -- nothing is
+ *                         consumed; S2AMD_E_STATE without a resident world or with the recorder off.  Reading never clears the ring.
+ * The step gains no host wait: the getters wait.
+ * Byte for byte this is what libs2amd.so returns; libs2amd_fast.so builds the same code under its own contraction rule (the products
+ * that feed an addition may be fused there). */
+#define S2AMD_METRICS_CONTACTS 1 /* gaps, approach speeds, penetration and impulse sums of the touching contacts */
+#define S2AMD_METRICS_BODIES 2   /* energy, momentum and spin of the non-static bodies */
+#define S2AMD_METRICS_JOINTS 4   /* anchor gaps of the revolute joints */
+#define S2AMD_METRICS_MAX_HISTORY 4096
+int s2amd_world_set_metrics(s2amdSolver* solver, int32_t flags, int32_t historyLength);
+typedef struct s2amdStepMetrics /* 128 bytes */
+{
+	int32_t step, flags, solverType;
+	float dt;
+	int32_t touchingContacts, touchingPoints, penetratingPoints, approachingPoints;
+	float minGap;
+	int32_t minGapSlot;
+	float maxApproachSpeed;
+	int32_t maxApproachSlot;
+	float sumPenetration, sumNormalImpulse;
+	int32_t energyBodies;
+	float kineticEnergy;
+	float potentialEnergy, momentum[2], spin;
+	int32_t revoluteJoints, maxJointGapSlot;
+	float maxJointGapSquared, sumJointGapSquared;
+	int32_t pad[8];
+} s2amdStepMetrics;
+int s2amd_world_metrics(s2amdSolver* solver, s2amdStepMetrics* out);
+int s2amd_world_metrics_history(s2amdSolver* solver, s2amdStepMetrics* out, int32_t capacity, int32_t* count);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

@@ -568,6 +568,13 @@ struct SolverRest
 		s2amdBodySummary summary;
 	} hBodyReportHead = {};
 	DevBuf dBodyReport;			 // one block, carved by bodyReportLayout(): pose copies, timers, state bytes, union-find, island sums, tile counts, head, lists, records
+	// step metrics (step_metrics.hip; s2amd_world_set_metrics): one 128-byte record per step into a ring in device memory, behind the body report
+	int metricsFlags = 0;	  // S2AMD_METRICS_*: what the next s2amd_world_step reduces (0: a step enqueues nothing for it)
+	int metricsLength = 0;	  // records the ring holds (1..S2AMD_METRICS_MAX_HISTORY while metricsFlags != 0)
+	int metricsStepFlags = 0; // the flags the last step recorded with (0: it recorded nothing, or the recorder was restarted since)
+	long long metricsWritten = 0; // records written since the recorder was restarted: the next record's `step`
+	DevBuf dMetricsRing;	  // metricsLength records (allocated by the setter)
+	DevBuf dMetricsPartials;  // the tiles' partials between the two kernels, carved by metricsLayout() (sized at upload and by the setter)
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -835,6 +842,11 @@ int bodyReportEnqueue(s2amdSolver* s, float dt);
 // where the report's head -- int32 counts[4] = {records, rested, woke, islands}, then s2amdBodySummary -- lies in dBodyReport (the
 // host-side sanitizer program writes it in place of the kernels)
 size_t bodyReportHeadOffset(const s2amdSolver* s);
+// step_metrics.hip.  metricsPrepare: restarts the recorder and sizes the partials for the resident world (at s2amd_world_upload and in
+// s2amd_world_set_metrics); metricsEnqueue: the step's two kernels on the step's stream behind stage 4 and the body report (never part
+// of the captured graph); `params` is the step's.
+int metricsPrepare(s2amdSolver* s);
+int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

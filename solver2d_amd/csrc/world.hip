@@ -537,6 +537,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	s->jointReportStepFlags = 0;
 	s->shapeReportStepFlags = 0;
 	s->bodyReportStepFlags = 0;
+	s->metricsStepFlags = 0;
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -644,6 +645,11 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		}
 		// (... and the body report's: pose copies from the bodies just uploaded, timers at +0: body_report.hip)
 		if ((rcReport = bodyReportPrepare(s)) != 0)
+		{
+			return rcReport;
+		}
+		// (... and the step metrics': the recorder restarts, the tiles' partials fit the capacities just uploaded: step_metrics.hip)
+		if ((rcReport = metricsPrepare(s)) != 0)
 		{
 			return rcReport;
 		}
@@ -1027,6 +1033,11 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	if (s->bodyReportFlags != 0 && (rc = bodyReportEnqueue(s, params->dt)) != 0)
 	{
 		return rc; // (the body report, the same way: body_report.hip)
+	}
+	s->metricsStepFlags = 0;
+	if (s->metricsFlags != 0 && (rc = metricsEnqueue(s, params)) != 0)
+	{
+		return rc; // (the step metrics, the same way: step_metrics.hip)
 	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;

@@ -30,6 +30,7 @@ EXPORTS = [
     "s2amd_world_set_shape_report", "s2amd_world_set_shape_view", "s2amd_world_shape_draws", "s2amd_world_shape_view_events", "s2amd_world_shape_summary",
     "s2amd_world_set_body_report", "s2amd_world_set_rest_thresholds", "s2amd_world_body_states", "s2amd_world_body_rest_events", "s2amd_world_islands",
     "s2amd_world_body_summary",
+    "s2amd_world_set_metrics", "s2amd_world_metrics", "s2amd_world_metrics_history",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -117,6 +118,9 @@ def load(fast=False):
     L.s2amd_world_body_rest_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_islands.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_body_summary.argtypes = [vp, vp]
+    L.s2amd_world_set_metrics.argtypes = [vp, i32, i32]
+    L.s2amd_world_metrics.argtypes = [vp, vp]
+    L.s2amd_world_metrics_history.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -605,6 +609,22 @@ class Solver:
         out = np.zeros(1, dtype=wire.body_summary_dtype)
         self._ck(self._L.s2amd_world_body_summary(self._h, wire.as_ptr(out)))
         return out[0]
+
+    # ---- step metrics of the resident world (s2amd_world_set_metrics): one record per step, kept in a ring on the device ----
+    def world_set_metrics(self, flags, history_length=1):
+        """wire.METRICS_* bits: what every world_step from the next one on reduces to one record (0: nothing, the default); the ring keeps
+        the last `history_length` records (1..wire.METRICS_MAX_HISTORY).  Every call restarts the recorder."""
+        self._ck(self._L.s2amd_world_set_metrics(self._h, int(flags), int(history_length)))
+
+    def world_metrics(self):
+        """One wire.step_metrics_dtype record: the last world_step's."""
+        out = np.zeros(1, dtype=wire.step_metrics_dtype)
+        self._ck(self._L.s2amd_world_metrics(self._h, wire.as_ptr(out)))
+        return out[0]
+
+    def world_metrics_history(self, expected=wire.METRICS_MAX_HISTORY):
+        """wire.step_metrics_dtype records of the steps the ring still holds, oldest first, in one read."""
+        return self._world_body_list(self._L.s2amd_world_metrics_history, wire.step_metrics_dtype, expected)
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

@@ -205,3 +205,17 @@ body_summary_dtype = np.dtype([("bodies", np.int32), ("dynamicBodies", np.int32)
                                ("restingBodies", np.int32), ("islands", np.int32), ("restingIslands", np.int32), ("largestIsland", np.int32),
                                ("largestIslandBodies", np.int32), ("fastestBody", np.int32), ("maxSpeedSquared", np.float32), ("pad", np.int32, 5)])
 assert body_summary_dtype.itemsize == 64
+
+# step metrics of the resident world (include/solver2d_amd.h: s2amd_world_set_metrics)
+METRICS_CONTACTS, METRICS_BODIES, METRICS_JOINTS = 1, 2, 4
+METRICS_ALL = METRICS_CONTACTS | METRICS_BODIES | METRICS_JOINTS
+METRICS_MAX_HISTORY = 4096
+# s2amdStepMetrics
+step_metrics_dtype = np.dtype([("step", np.int32), ("flags", np.int32), ("solverType", np.int32), ("dt", np.float32),
+                               ("touchingContacts", np.int32), ("touchingPoints", np.int32), ("penetratingPoints", np.int32), ("approachingPoints", np.int32),
+                               ("minGap", np.float32), ("minGapSlot", np.int32), ("maxApproachSpeed", np.float32), ("maxApproachSlot", np.int32),
+                               ("sumPenetration", np.float32), ("sumNormalImpulse", np.float32), ("energyBodies", np.int32), ("kineticEnergy", np.float32),
+                               ("potentialEnergy", np.float32), ("momentum", np.float32, 2), ("spin", np.float32),
+                               ("revoluteJoints", np.int32), ("maxJointGapSlot", np.int32), ("maxJointGapSquared", np.float32), ("sumJointGapSquared", np.float32),
+                               ("pad", np.int32, 8)])
+assert step_metrics_dtype.itemsize == 128

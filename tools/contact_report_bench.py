@@ -46,11 +46,25 @@ base 200, all of them one island) and 512 pyramids of base 40 (420,352 bodies, 5
     download   no flag, and every step what the report replaces: the s2amd_world_download of bodies, origins, contacts and joints, then
                islands.find_islands on the host
 
+The step metrics (s2amd_world_set_metrics) are measured the same way on the standing base-N pyramid -- world `metrics` -- in the modes of
+--metrics-modes:
+
+    off        no metrics flag
+    contacts   S2AMD_METRICS_CONTACTS + s2amd_world_metrics every step
+    bodies     S2AMD_METRICS_BODIES   + s2amd_world_metrics every step
+    joints     S2AMD_METRICS_JOINTS   + s2amd_world_metrics every step
+    all        all three flags + s2amd_world_metrics every step
+    history    all three flags, a ring of --steps records, no getter in the loop and ONE s2amd_world_metrics_history behind the last step
+               (its time is `history_fetch_ms` and part of `total_ms`; `all` is the same run with one getter per step)
+    download   no flag, and every step what the record replaces: the s2amd_world_download of bodies, origins, contacts, pairs and
+               joints, then the numpy statement tests/step_metrics_ref.py on the host
+
 One JSON object per line and mode.  All read-backs land in buffers allocated once, through the raw C calls.
 
     python tools/contact_report_bench.py --tree . --label this [--rep N] [--modes off,all,download] [--base 200]
                                          [--worlds pyramid,wreck,jointed,shaped,bodies] [--joint-modes off,all,download] [--grid 64]
                                          [--shape-modes off,all,download,download_step] [--body-modes off,all,download]
+                                         [--worlds metrics --metrics-modes off,all,history,download]
 
 --tree: a directory that holds a built `solver2d_amd` package and `tests/world_chain.py` (this checkout: `.`; another commit: an export
 of it, built; a tree without the report API can run `off` and `download`).  Run two trees alternately, several repeats each, in ONE
@@ -73,6 +87,7 @@ ap.add_argument("--worlds", default="pyramid,wreck,jointed")
 ap.add_argument("--joint-modes", default="off,states,limits,sums,all,download")
 ap.add_argument("--shape-modes", default="off,draw,view,bounds,all,download,download_step")
 ap.add_argument("--body-modes", default="off,states,moved,rest,islands,all,download")
+ap.add_argument("--metrics-modes", default="off,contacts,bodies,joints,all,history,download")
 ap.add_argument("--grid", type=int, default=64)
 ap.add_argument("--base", type=int, default=200)
 ap.add_argument("--seed", type=int, default=3)
@@ -88,6 +103,7 @@ FLAGS = {"off": 0, "download": 0, "touch": 1, "contacts": 2, "sums": 4, "all": 7
 JOINT_FLAGS = {"off": 0, "download": 0, "states": 1, "limits": 2, "sums": 4, "all": 7}
 SHAPE_FLAGS = {"off": 0, "download": 0, "download_step": 0, "draw": 1, "view": 2, "bounds": 4, "all": 7}
 BODY_FLAGS = {"off": 0, "download": 0, "states": 1, "moved": 9, "rest": 2, "islands": 4, "all": 7}
+METRICS_FLAGS = {"off": 0, "download": 0, "contacts": 1, "bodies": 2, "joints": 4, "all": 7, "history": 7}
 SOLVER = "TGS_Soft"
 
 
@@ -311,7 +327,61 @@ def run_bodies(world, mode):
             "records_last": records, "rested_total": rested, "woke_total": woke, "islands_last": n_islands, "bodies": nb, "contact_slots": nc}
 
 
+def run_metrics(world, mode):
+    params = wire.StepParams.make(SOLVER, 1.0 / 60.0, 8, 4, True)
+    nb, nc, nj = len(world["bodies"]), len(world["contacts"]), len(world["joints"])
+    flags = METRICS_FLAGS[mode]
+    ms, last, fetch_ms, fetched = [], None, 0.0, 0
+    with hip.Solver(0) as s:
+        L, h = s._L, s._h
+        s.set_option("prebuild_solver", wire.SOLVER_ID[SOLVER])
+        if flags:
+            s.world_set_metrics(flags, a.steps if mode == "history" else 1)
+            m_buf = np.zeros(a.steps if mode == "history" else 1, dtype=wire.step_metrics_dtype)
+        s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
+        if mode == "download":
+            from tests import step_metrics_ref
+            d = {"bodies": np.zeros(nb, dtype=wire.body_dtype), "contacts": np.zeros(nc, dtype=wire.contact_dtype), "joints": np.zeros(nj, dtype=wire.joint_dtype),
+                 "pairs": np.zeros(nc, dtype=wire.pair_state_dtype), "origins": np.zeros((nb, 2), dtype=np.float32)}
+        n1 = ctypes.c_int32()
+        for step in range(a.warmup + a.steps):
+            if mode == "history" and step == a.warmup:
+                s.world_set_metrics(flags, a.steps)  # (restarts the recorder: the ring holds exactly the timed steps)
+            t0 = time.perf_counter()
+            s.world_step(params)
+            if flags and mode != "history":
+                s._ck(L.s2amd_world_metrics(h, wire.as_ptr(m_buf)))
+                last = m_buf[0]
+            if mode == "download":
+                s._ck(L.s2amd_world_download(h, wire.as_ptr(d["bodies"]), nb, wire.as_ptr(d["contacts"]), nc, wire.as_ptr(d["joints"]), nj, None, 0,
+                                             wire.as_ptr(d["pairs"]), wire.as_ptr(d["origins"]), None))
+                last = step_metrics_ref.record(d, params, 7, step)
+            if step >= a.warmup:
+                ms.append(1e3 * (time.perf_counter() - t0))
+        if mode == "history":
+            t0 = time.perf_counter()
+            s._ck(L.s2amd_world_metrics_history(h, wire.as_ptr(m_buf), len(m_buf), ctypes.byref(n1)))
+            fetch_ms = 1e3 * (time.perf_counter() - t0)
+            fetched, last = n1.value, m_buf[n1.value - 1]
+    total = sum(ms) + fetch_ms
+    ms.sort()
+    out = {"step_ms_mean": round(sum(ms) / len(ms), 4), "step_ms_median": round(ms[len(ms) // 2], 4), "step_ms_p90": round(ms[(9 * len(ms)) // 10], 4),
+           "total_ms": round(total, 3), "history_fetch_ms": round(fetch_ms, 4), "history_records": fetched, "bodies": nb, "contact_slots": nc}
+    if last is not None:
+        out.update({"touching_last": int(last["touchingContacts"]), "min_gap_last": float(last["minGap"]), "kinetic_energy_last": float(last["kineticEnergy"]),
+                    "record_step_last": int(last["step"])})
+    return out
+
+
 for name in a.worlds.split(","):
+    if name == "metrics":
+        world = synthetic.pyramid_world(a.base)
+        for mode in a.metrics_modes.split(","):
+            r = run_metrics(world_chain.copy_world(world), mode)
+            r.update({"tree": a.label, "rep": a.rep, "world": "pyramid base %d" % a.base, "solver": SOLVER, "report": "metrics", "mode": mode, "steps": a.steps,
+                      "warmup": a.warmup})
+            print(json.dumps(r), flush=True)
+        continue
     if name == "bodies":
         for world_name, world in (("pyramid base %d" % a.base, synthetic.pyramid_world(a.base)), ("512 x pyramid base 40", synthetic.pyramid_world(40, 512))):
             for mode in a.body_modes.split(","):
