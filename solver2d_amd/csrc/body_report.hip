@@ -95,27 +95,22 @@ BodyReportLayout bodyReportLayout(int nb)
 {
 	BodyReportLayout l{};
 	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t here = at;
-		at += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-		return here;
-	};
 	l.tiles = (nb + S2_BLOCK - 1) / S2_BLOCK;
-	l.pose = take((size_t)nb * sizeof(uint4));
-	l.timer = take((size_t)nb * sizeof(float));
-	l.state = take((size_t)nb);
-	l.parent = take((size_t)nb * sizeof(int));
-	l.label = take((size_t)nb * sizeof(int));
-	l.islandIndex = take((size_t)nb * sizeof(int));
-	l.sums = take((size_t)nb * sizeof(IslandSums));
-	l.counts = take((size_t)4 * l.tiles * sizeof(int));
-	l.partials = take((size_t)l.tiles * sizeof(BodyTilePartial));
-	l.islandPartials = take((size_t)l.tiles * sizeof(IslandTilePartial));
-	l.head = take(sizeof(BodyReportHead));
-	l.rested = take((size_t)nb * sizeof(int32_t));
-	l.woke = take((size_t)nb * sizeof(int32_t));
-	l.records = take((size_t)nb * sizeof(s2amdBodyState));
-	l.islands = take((size_t)nb * sizeof(s2amdIslandState));
+	l.pose = reportTake(at, (size_t)nb * sizeof(uint4));
+	l.timer = reportTake(at, (size_t)nb * sizeof(float));
+	l.state = reportTake(at, (size_t)nb);
+	l.parent = reportTake(at, (size_t)nb * sizeof(int));
+	l.label = reportTake(at, (size_t)nb * sizeof(int));
+	l.islandIndex = reportTake(at, (size_t)nb * sizeof(int));
+	l.sums = reportTake(at, (size_t)nb * sizeof(IslandSums));
+	l.counts = reportTake(at, (size_t)4 * l.tiles * sizeof(int));
+	l.partials = reportTake(at, (size_t)l.tiles * sizeof(BodyTilePartial));
+	l.islandPartials = reportTake(at, (size_t)l.tiles * sizeof(IslandTilePartial));
+	l.head = reportTake(at, sizeof(BodyReportHead));
+	l.rested = reportTake(at, (size_t)nb * sizeof(int32_t));
+	l.woke = reportTake(at, (size_t)nb * sizeof(int32_t));
+	l.records = reportTake(at, (size_t)nb * sizeof(s2amdBodyState));
+	l.islands = reportTake(at, (size_t)nb * sizeof(s2amdIslandState));
 	l.total = at;
 	return l;
 }
@@ -721,65 +716,30 @@ BodyReportLayout layoutOf(const s2amdSolver* s)
 	return bodyReportLayout(s->bodyCapacity);
 }
 
-// the counts and the summary of the last step's report, once per step
-int bodyReportFetchHead(s2amdSolver* s)
+ReportRef ref(s2amdSolver* s)
 {
-	if (s->bodyReportHeadKnown)
-	{
-		return S2AMD_OK;
-	}
 	static_assert(sizeof(s->hBodyReportHead) == sizeof(BodyReportHead), "the host copy of the report's head");
-	HIP_TRY(hipSetDevice(s->device));
-	const BodyReportLayout l = layoutOf(s);
-	HIP_TRY(hipMemcpyAsync(&s->hBodyReportHead, (const char*)s->dBodyReport.p + l.head, sizeof(BodyReportHead), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	s->bodyReportHeadKnown = true;
-	return S2AMD_OK;
+	return s ? ReportRef{s, &s->bodyReport, &s->hBodyReportHead, sizeof(s->hBodyReportHead), "body-report", "s2amd_world_set_body_report"} : ReportRef{};
 }
 
-// flag 0: any flag will do (s2amd_world_body_summary)
-int bodyReportGetterState(const s2amdSolver* s, int flag, const char* what)
+// where a piece of the block lies, for a getter (0 for the null solver it will refuse)
+size_t at(const s2amdSolver* s, size_t BodyReportLayout::*piece)
 {
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	if (flag != 0 ? (s->bodyReportStepFlags & flag) == 0 : s->bodyReportStepFlags == 0)
-	{
-		return fail(S2AMD_E_STATE, std::string(what) + ": the last s2amd_world_step did not run with this body-report flag set (s2amd_world_set_body_report, then a step)");
-	}
-	return S2AMD_OK;
-}
-
-// one list of the report: `count` entries of `size` bytes at `offset` of the block
-int bodyReportFetch(s2amdSolver* s, void* out, size_t offset, int count, size_t size)
-{
-	if (count > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->dBodyReport.p + offset, (size_t)count * size, hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	return s ? layoutOf(s).*piece : 0;
 }
 
 } // namespace
 
-size_t bodyReportHeadOffset(const s2amdSolver* s)
-{
-	return layoutOf(s).head;
-}
-
 int bodyReportPrepare(s2amdSolver* s)
 {
-	s->bodyReportStepFlags = 0;
-	s->bodyReportHeadKnown = false;
-	if (s->bodyReportFlags == 0 || !s->worldResident)
+	ReportState& r = s->bodyReport;
+	if (!reportPrepareBegin(s, r))
 	{
 		return S2AMD_OK;
 	}
 	const int nb = s->bodyCapacity;
 	const BodyReportLayout l = layoutOf(s);
-	int rc = s->dBodyReport.ensure(l.total);
+	int rc = reportPrepareBlock(r, l.total, l.head);
 	if (rc)
 	{
 		return rc;
@@ -787,7 +747,7 @@ int bodyReportPrepare(s2amdSolver* s)
 	if (nb > 0)
 	{
 		HIP_TRY(hipSetDevice(s->device));
-		char* base = (char*)s->dBodyReport.p;
+		char* base = (char*)r.block.p;
 		bodyInitKernel<<<gridFor((size_t)nb), dim3(S2_BLOCK), 0, s->stream>>>((const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, nb, (uint4*)(base + l.pose),
 																			  (float*)(base + l.timer), (uint8_t*)(base + l.state));
 		HIP_TRY(hipGetLastError());
@@ -795,19 +755,24 @@ int bodyReportPrepare(s2amdSolver* s)
 	return S2AMD_OK;
 }
 
-int bodyReportEnqueue(s2amdSolver* s, float dt)
+int bodyReportEnqueue(s2amdSolver* s, const s2amdStepParams* params)
 {
-	const int flags = s->bodyReportFlags;
+	ReportState& r = s->bodyReport;
+	const int flags = r.flags;
 	const int nb = s->bodyCapacity;
 	const BodyReportLayout l = layoutOf(s);
-	if (flags == 0 || s->dBodyReport.p == nullptr || s->dBodyReport.bytes < l.total)
+	if (flags == 0)
 	{
-		return flags == 0 ? S2AMD_OK : fail(S2AMD_E_STATE, "internal: the body report's device block was not prepared");
+		return S2AMD_OK;
+	}
+	if (int rc = reportEnqueueGuard(r, l.total, "body"))
+	{
+		return rc;
 	}
 	if (nb > 0)
 	{
 		hipStream_t st = s->stream;
-		char* base = (char*)s->dBodyReport.p;
+		char* base = (char*)r.block.p;
 		const s2amdBody* bodies = (const s2amdBody*)s->dBodies.p;
 		const float2* origins = (const float2*)s->dOrigins.p;
 		const s2amdContact* contacts = (const s2amdContact*)s->dContacts.p;
@@ -815,7 +780,7 @@ int bodyReportEnqueue(s2amdSolver* s, float dt)
 		const int nc = s->contactCapacity, nj = s->jointCapacity;
 		RestRule rule;
 		rule.lin2 = s->restLinearSpeed * s->restLinearSpeed, rule.ang2 = s->restAngularSpeed * s->restAngularSpeed;
-		rule.seconds = s->restSeconds, rule.dt = dt;
+		rule.seconds = s->restSeconds, rule.dt = params->dt;
 		uint8_t* state = (uint8_t*)(base + l.state);
 		float* timer = (float*)(base + l.timer);
 		int* counts = (int*)(base + l.counts);
@@ -850,8 +815,8 @@ int bodyReportEnqueue(s2amdSolver* s, float dt)
 		s->hBodyReportHead.summary.largestIsland = -1, s->hBodyReportHead.summary.fastestBody = -1;
 		s->hBodyReportHead.summary.maxSpeedSquared = -1.0f;
 	}
-	s->bodyReportStepFlags = flags;
-	s->bodyReportHeadKnown = nb <= 0;
+	r.stepFlags = flags;
+	r.headKnown = nb <= 0;
 	return S2AMD_OK;
 }
 
@@ -861,22 +826,8 @@ extern "C"
 
 int s2amd_world_set_body_report(s2amdSolver* s, int32_t flags)
 {
-	if (!s)
-	{
-		return fail(S2AMD_E_INVALID, "null solver");
-	}
-	if ((flags & ~(S2AMD_BODY_REPORT_STATES | S2AMD_BODY_REPORT_REST | S2AMD_BODY_REPORT_ISLANDS | S2AMD_BODY_REPORT_MOVED_ONLY)) != 0)
-	{
-		return fail(S2AMD_E_INVALID, "unknown body-report flag bits");
-	}
-	const bool turnedOn = s->bodyReportFlags == 0 && flags != 0;
-	s->bodyReportFlags = flags;
-	if (turnedOn)
-	{
-		// the pose copy is of the bodies as they stand, the timers start at +0; the last step's report (if any) is not of these passes
-		return bodyReportPrepare(s);
-	}
-	return S2AMD_OK;
+	// (the pose copy is of the bodies as they stand, the timers start at +0)
+	return reportSet(ref(s), flags, S2AMD_BODY_REPORT_STATES | S2AMD_BODY_REPORT_REST | S2AMD_BODY_REPORT_ISLANDS | S2AMD_BODY_REPORT_MOVED_ONLY, bodyReportPrepare);
 }
 
 int s2amd_world_set_rest_thresholds(s2amdSolver* s, float linearSpeed, float angularSpeed, float seconds)
@@ -897,80 +848,29 @@ int s2amd_world_set_rest_thresholds(s2amdSolver* s, float linearSpeed, float ang
 
 int s2amd_world_body_states(s2amdSolver* s, s2amdBodyState* out, int32_t capacity, int32_t* count)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = bodyReportGetterState(s, S2AMD_BODY_REPORT_STATES, "s2amd_world_body_states");
-	if (rc || (rc = bodyReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*count = s->hBodyReportHead.counts[0];
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "body-state buffer too small");
-	}
-	return bodyReportFetch(s, out, layoutOf(s).records, *count, sizeof(s2amdBodyState));
+	return reportGetList(ref(s), S2AMD_BODY_REPORT_STATES, "s2amd_world_body_states", "body-state buffer too small", 0, at(s, &BodyReportLayout::records), sizeof(*out), out, capacity,
+						 count);
 }
 
 int s2amd_world_body_rest_events(s2amdSolver* s, int32_t* rested, int32_t restedCapacity, int32_t* restedCount, int32_t* woke, int32_t wokeCapacity, int32_t* wokeCount)
 {
-	if (!s || !restedCount || !wokeCount || restedCapacity < 0 || wokeCapacity < 0 || (restedCapacity > 0 && !rested) || (wokeCapacity > 0 && !woke))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = bodyReportGetterState(s, S2AMD_BODY_REPORT_REST, "s2amd_world_body_rest_events");
-	if (rc || (rc = bodyReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*restedCount = s->hBodyReportHead.counts[1];
-	*wokeCount = s->hBodyReportHead.counts[2];
-	if (*restedCount > restedCapacity || *wokeCount > wokeCapacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "body rest event buffer too small");
-	}
-	const BodyReportLayout l = layoutOf(s);
-	if ((rc = bodyReportFetch(s, rested, l.rested, *restedCount, sizeof(int32_t))) != 0)
-	{
-		return rc;
-	}
-	return bodyReportFetch(s, woke, l.woke, *wokeCount, sizeof(int32_t));
+	return reportGetEvents(ref(s), S2AMD_BODY_REPORT_REST, "s2amd_world_body_rest_events", "body rest event buffer too small", 1, at(s, &BodyReportLayout::rested),
+						   at(s, &BodyReportLayout::woke), rested, restedCapacity, restedCount, woke, wokeCapacity, wokeCount);
 }
 
 int s2amd_world_islands(s2amdSolver* s, s2amdIslandState* out, int32_t capacity, int32_t* count)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = bodyReportGetterState(s, S2AMD_BODY_REPORT_ISLANDS, "s2amd_world_islands");
-	if (rc || (rc = bodyReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*count = s->hBodyReportHead.counts[3];
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "island buffer too small");
-	}
-	return bodyReportFetch(s, out, layoutOf(s).islands, *count, sizeof(s2amdIslandState));
+	return reportGetList(ref(s), S2AMD_BODY_REPORT_ISLANDS, "s2amd_world_islands", "island buffer too small", 3, at(s, &BodyReportLayout::islands), sizeof(*out), out, capacity, count);
 }
 
 int s2amd_world_body_summary(s2amdSolver* s, s2amdBodySummary* out)
 {
-	if (!s || !out)
+	const int rc = out ? reportHeadFor(ref(s), 0, "s2amd_world_body_summary") : fail(S2AMD_E_INVALID, "bad argument");
+	if (rc == S2AMD_OK)
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		*out = s->hBodyReportHead.summary;
 	}
-	int rc = bodyReportGetterState(s, 0, "s2amd_world_body_summary");
-	if (rc || (rc = bodyReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*out = s->hBodyReportHead.summary;
-	return S2AMD_OK;
+	return rc;
 }
 
 } // extern "C"

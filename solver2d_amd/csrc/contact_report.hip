@@ -14,7 +14,7 @@
 //
 // The byte array is the report's own (not world.hip's pointBytes, which advance inside the retry loop of s2amd_world_step): the passes
 // are enqueued once per step, behind the attempt that stands, so a repeated step reports once.  All device memory is one block sized
-// by reportPrepare (at upload / set_report); a step allocates nothing and waits for nothing -- the getters do.
+// by contactReportPrepare (at upload / set_report); a step allocates nothing and waits for nothing -- the getters do.
 #include "report_common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -34,25 +34,20 @@ ReportLayout reportLayout(int nc, int nb, size_t sortTmpBytes)
 {
 	ReportLayout l{};
 	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t here = at;
-		at += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-		return here;
-	};
 	l.tiles = (nc + S2_BLOCK - 1) / S2_BLOCK;
-	l.was = take((size_t)nc);
-	l.counts = take((size_t)3 * l.tiles * sizeof(int));
-	l.head = take(4 * sizeof(int32_t));
-	l.began = take((size_t)nc * sizeof(int32_t));
-	l.ended = take((size_t)nc * sizeof(int32_t));
-	l.records = take((size_t)nc * sizeof(s2amdTouchingContact));
-	l.keysIn = take((size_t)2 * nc * sizeof(uint32_t));
-	l.keysOut = take((size_t)2 * nc * sizeof(uint32_t));
-	l.valsIn = take((size_t)2 * nc * sizeof(int));
-	l.valsOut = take((size_t)2 * nc * sizeof(int));
-	l.ranges = take((size_t)2 * nb * sizeof(int));
-	l.sums = take((size_t)nb * sizeof(s2amdBodyContactSum));
-	l.sortTmp = take(sortTmpBytes);
+	l.was = reportTake(at, (size_t)nc);
+	l.counts = reportTake(at, (size_t)3 * l.tiles * sizeof(int));
+	l.head = reportTake(at, 4 * sizeof(int32_t));
+	l.began = reportTake(at, (size_t)nc * sizeof(int32_t));
+	l.ended = reportTake(at, (size_t)nc * sizeof(int32_t));
+	l.records = reportTake(at, (size_t)nc * sizeof(s2amdTouchingContact));
+	l.keysIn = reportTake(at, (size_t)2 * nc * sizeof(uint32_t));
+	l.keysOut = reportTake(at, (size_t)2 * nc * sizeof(uint32_t));
+	l.valsIn = reportTake(at, (size_t)2 * nc * sizeof(int));
+	l.valsOut = reportTake(at, (size_t)2 * nc * sizeof(int));
+	l.ranges = reportTake(at, (size_t)2 * nb * sizeof(int));
+	l.sums = reportTake(at, (size_t)nb * sizeof(s2amdBodyContactSum));
+	l.sortTmp = reportTake(at, sortTmpBytes);
 	l.total = at;
 	return l;
 }
@@ -289,44 +284,26 @@ __global__ __launch_bounds__(S2_BLOCK) void reportBodySumKernel(const s2amdConta
 
 ReportLayout layoutOf(const s2amdSolver* s)
 {
-	return reportLayout(s->contactCapacity, s->bodyCapacity, s->reportSortTmpBytes);
+	return reportLayout(s->contactCapacity, s->bodyCapacity, s->contactReport.sortTmpBytes);
 }
 
-// the counts of the last step's lists, once per step
-int reportFetchHead(s2amdSolver* s)
+ReportRef ref(s2amdSolver* s)
 {
-	if (s->reportHeadKnown)
-	{
-		return S2AMD_OK;
-	}
-	HIP_TRY(hipSetDevice(s->device));
-	const ReportLayout l = layoutOf(s);
-	HIP_TRY(hipMemcpyAsync(s->hReportHead, (const char*)s->dReport.p + l.head, sizeof(s->hReportHead), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	s->reportHeadKnown = true;
-	return S2AMD_OK;
+	return s ? ReportRef{s, &s->contactReport, s->hReportHead, sizeof(s->hReportHead), "report", "s2amd_world_set_report"} : ReportRef{};
 }
 
-int reportGetterState(const s2amdSolver* s, int flag, const char* what)
+// where a piece of the block lies, for a getter (0 for the null solver it will refuse)
+size_t at(const s2amdSolver* s, size_t ReportLayout::*piece)
 {
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	if ((s->reportStepFlags & flag) == 0)
-	{
-		return fail(S2AMD_E_STATE, std::string(what) + ": the last s2amd_world_step did not run with this report flag set (s2amd_world_set_report, then a step)");
-	}
-	return S2AMD_OK;
+	return s ? layoutOf(s).*piece : 0;
 }
 
 } // namespace
 
-int reportPrepare(s2amdSolver* s)
+int contactReportPrepare(s2amdSolver* s)
 {
-	s->reportStepFlags = 0;
-	s->reportHeadKnown = false;
-	if (s->reportFlags == 0 || !s->worldResident)
+	ReportState& r = s->contactReport;
+	if (!reportPrepareBegin(s, r))
 	{
 		return S2AMD_OK;
 	}
@@ -337,16 +314,16 @@ int reportPrepare(s2amdSolver* s)
 	{
 		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)2 * nc, 0, bodyKeyBits(nb), s->stream));
 	}
-	s->reportSortTmpBytes = tmp;
+	r.sortTmpBytes = tmp;
 	const ReportLayout l = layoutOf(s);
-	int rc = s->dReport.ensure(l.total);
+	int rc = reportPrepareBlock(r, l.total, l.head);
 	if (rc)
 	{
 		return rc;
 	}
 	if (nc > 0)
 	{
-		reportInitKernel<<<gridFor((size_t)nc), dim3(S2_BLOCK), 0, s->stream>>>((const s2amdContact*)s->dContacts.p, nc, (uint8_t*)s->dReport.p + l.was);
+		reportInitKernel<<<gridFor((size_t)nc), dim3(S2_BLOCK), 0, s->stream>>>((const s2amdContact*)s->dContacts.p, nc, (uint8_t*)r.block.p + l.was);
 		HIP_TRY(hipGetLastError());
 	}
 	return S2AMD_OK;
@@ -354,27 +331,32 @@ int reportPrepare(s2amdSolver* s)
 
 int reportNoteSetContacts(s2amdSolver* s, const int32_t* dSlots, int count, const s2amdContact* dNewContacts)
 {
-	if (s->reportFlags == 0 || count <= 0 || s->dReport.p == nullptr)
+	if (s->contactReport.flags == 0 || count <= 0 || s->contactReport.block.p == nullptr)
 	{
 		return S2AMD_OK;
 	}
 	const ReportLayout l = layoutOf(s);
-	reportSetKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, s->stream>>>(dSlots, count, dNewContacts, (uint8_t*)s->dReport.p + l.was);
+	reportSetKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, s->stream>>>(dSlots, count, dNewContacts, (uint8_t*)s->contactReport.block.p + l.was);
 	HIP_TRY(hipGetLastError());
 	return S2AMD_OK;
 }
 
-int reportEnqueue(s2amdSolver* s)
+int contactReportEnqueue(s2amdSolver* s, const s2amdStepParams*)
 {
-	const int flags = s->reportFlags;
+	ReportState& r = s->contactReport;
+	const int flags = r.flags;
 	const int nc = s->contactCapacity, nb = s->bodyCapacity;
 	const ReportLayout l = layoutOf(s);
-	if (flags == 0 || s->dReport.p == nullptr || s->dReport.bytes < l.total)
+	if (flags == 0)
 	{
-		return flags == 0 ? S2AMD_OK : fail(S2AMD_E_STATE, "internal: the contact report's device block was not prepared");
+		return S2AMD_OK;
+	}
+	if (int rc = reportEnqueueGuard(r, l.total, "contact"))
+	{
+		return rc;
 	}
 	hipStream_t st = s->stream;
-	char* base = (char*)s->dReport.p;
+	char* base = (char*)r.block.p;
 	const s2amdContact* contacts = (const s2amdContact*)s->dContacts.p;
 	const s2amdPairState* pairs = (const s2amdPairState*)s->dPairs.p;
 	if (nc > 0)
@@ -387,13 +369,14 @@ int reportEnqueue(s2amdSolver* s)
 	}
 	else
 	{
-		HIP_TRY(hipMemsetAsync(base + l.head, 0, 4 * sizeof(int32_t), st));
+		// (a world without contact slots launches no tile: its head is known here)
+		memset(s->hReportHead, 0, sizeof(s->hReportHead));
 	}
 	if ((flags & S2AMD_REPORT_BODY_SUMS) != 0 && nb > 0)
 	{
 		if (nc > 0)
 		{
-			size_t tmp = s->reportSortTmpBytes;
+			size_t tmp = r.sortTmpBytes;
 			reportBodyKeysKernel<<<gridFor((size_t)2 * nc), dim3(S2_BLOCK), 0, st>>>(contacts, pairs, nc, nb, (uint32_t*)(base + l.keysIn), (int*)(base + l.valsIn));
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(rocprim::radix_sort_pairs((void*)(base + l.sortTmp), tmp, (uint32_t*)(base + l.keysIn), (uint32_t*)(base + l.keysOut), (int*)(base + l.valsIn),
@@ -408,8 +391,8 @@ int reportEnqueue(s2amdSolver* s)
 																											  nb, (s2amdBodyContactSum*)(base + l.sums));
 		HIP_TRY(hipGetLastError());
 	}
-	s->reportStepFlags = flags;
-	s->reportHeadKnown = false;
+	r.stepFlags = flags;
+	r.headKnown = nc <= 0;
 	return S2AMD_OK;
 }
 
@@ -419,103 +402,24 @@ extern "C"
 
 int s2amd_world_set_report(s2amdSolver* s, int32_t flags)
 {
-	if (!s)
-	{
-		return fail(S2AMD_E_INVALID, "null solver");
-	}
-	if ((flags & ~(S2AMD_REPORT_TOUCH | S2AMD_REPORT_CONTACTS | S2AMD_REPORT_BODY_SUMS)) != 0)
-	{
-		return fail(S2AMD_E_INVALID, "unknown report flag bits");
-	}
-	const bool turnedOn = s->reportFlags == 0 && flags != 0;
-	s->reportFlags = flags;
-	if (turnedOn)
-	{
-		// "before" starts as the world stands now; the last step's report (if any) is not of these passes
-		return reportPrepare(s);
-	}
-	return S2AMD_OK;
+	return reportSet(ref(s), flags, S2AMD_REPORT_TOUCH | S2AMD_REPORT_CONTACTS | S2AMD_REPORT_BODY_SUMS, contactReportPrepare);
 }
 
 int s2amd_world_touch_events(s2amdSolver* s, int32_t* began, int32_t beganCapacity, int32_t* beganCount, int32_t* ended, int32_t endedCapacity, int32_t* endedCount)
 {
-	if (!s || !beganCount || !endedCount || beganCapacity < 0 || endedCapacity < 0 || (beganCapacity > 0 && !began) || (endedCapacity > 0 && !ended))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = reportGetterState(s, S2AMD_REPORT_TOUCH, "s2amd_world_touch_events");
-	if (rc || (rc = reportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*beganCount = s->hReportHead[0];
-	*endedCount = s->hReportHead[1];
-	if (*beganCount > beganCapacity || *endedCount > endedCapacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "touch event buffer too small");
-	}
-	const ReportLayout l = layoutOf(s);
-	const char* base = (const char*)s->dReport.p;
-	if (*beganCount > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(began, base + l.began, (size_t)*beganCount * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	}
-	if (*endedCount > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(ended, base + l.ended, (size_t)*endedCount * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	}
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return reportGetEvents(ref(s), S2AMD_REPORT_TOUCH, "s2amd_world_touch_events", "touch event buffer too small", 0, at(s, &ReportLayout::began), at(s, &ReportLayout::ended), began,
+						   beganCapacity, beganCount, ended, endedCapacity, endedCount);
 }
 
 int s2amd_world_touching(s2amdSolver* s, s2amdTouchingContact* out, int32_t capacity, int32_t* count)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = reportGetterState(s, S2AMD_REPORT_CONTACTS, "s2amd_world_touching");
-	if (rc || (rc = reportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*count = s->hReportHead[2];
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "touching-contact buffer too small");
-	}
-	if (*count > 0)
-	{
-		const ReportLayout l = layoutOf(s);
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->dReport.p + l.records, (size_t)*count * sizeof(s2amdTouchingContact), hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	return reportGetList(ref(s), S2AMD_REPORT_CONTACTS, "s2amd_world_touching", "touching-contact buffer too small", 2, at(s, &ReportLayout::records), sizeof(*out), out, capacity,
+						 count);
 }
 
 int s2amd_world_body_sums(s2amdSolver* s, s2amdBodyContactSum* out, int32_t bodyCapacity)
 {
-	if (!s || bodyCapacity < 0 || (bodyCapacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = reportGetterState(s, S2AMD_REPORT_BODY_SUMS, "s2amd_world_body_sums");
-	if (rc)
-	{
-		return rc;
-	}
-	if (bodyCapacity < s->bodyCapacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "body-sum array smaller than the resident body array");
-	}
-	if (s->bodyCapacity > 0)
-	{
-		HIP_TRY(hipSetDevice(s->device));
-		const ReportLayout l = layoutOf(s);
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->dReport.p + l.sums, (size_t)s->bodyCapacity * sizeof(s2amdBodyContactSum), hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	return reportGetBodyArray(ref(s), S2AMD_REPORT_BODY_SUMS, "s2amd_world_body_sums", at(s, &ReportLayout::sums), sizeof(*out), out, bodyCapacity);
 }
 
 } // extern "C"

@@ -52,26 +52,21 @@ JointReportLayout jointReportLayout(int nj, int nb, size_t sortTmpBytes)
 {
 	JointReportLayout l{};
 	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t here = at;
-		at += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-		return here;
-	};
 	l.tiles = (nj + S2_BLOCK - 1) / S2_BLOCK;
-	l.was = take((size_t)nj);
-	l.counts = take((size_t)3 * l.tiles * sizeof(int));
-	l.partials = take((size_t)l.tiles * sizeof(JointTilePartial));
-	l.head = take(sizeof(JointReportHead));
-	l.began = take((size_t)2 * nj * sizeof(int32_t));
-	l.ended = take((size_t)2 * nj * sizeof(int32_t));
-	l.records = take((size_t)nj * sizeof(s2amdJointState));
-	l.keysIn = take((size_t)2 * nj * sizeof(uint32_t));
-	l.keysOut = take((size_t)2 * nj * sizeof(uint32_t));
-	l.valsIn = take((size_t)2 * nj * sizeof(int));
-	l.valsOut = take((size_t)2 * nj * sizeof(int));
-	l.ranges = take((size_t)2 * nb * sizeof(int));
-	l.sums = take((size_t)nb * sizeof(s2amdBodyJointSum));
-	l.sortTmp = take(sortTmpBytes);
+	l.was = reportTake(at, (size_t)nj);
+	l.counts = reportTake(at, (size_t)3 * l.tiles * sizeof(int));
+	l.partials = reportTake(at, (size_t)l.tiles * sizeof(JointTilePartial));
+	l.head = reportTake(at, sizeof(JointReportHead));
+	l.began = reportTake(at, (size_t)2 * nj * sizeof(int32_t));
+	l.ended = reportTake(at, (size_t)2 * nj * sizeof(int32_t));
+	l.records = reportTake(at, (size_t)nj * sizeof(s2amdJointState));
+	l.keysIn = reportTake(at, (size_t)2 * nj * sizeof(uint32_t));
+	l.keysOut = reportTake(at, (size_t)2 * nj * sizeof(uint32_t));
+	l.valsIn = reportTake(at, (size_t)2 * nj * sizeof(int));
+	l.valsOut = reportTake(at, (size_t)2 * nj * sizeof(int));
+	l.ranges = reportTake(at, (size_t)2 * nb * sizeof(int));
+	l.sums = reportTake(at, (size_t)nb * sizeof(s2amdBodyJointSum));
+	l.sortTmp = reportTake(at, sortTmpBytes);
 	l.total = at;
 	return l;
 }
@@ -428,46 +423,27 @@ __global__ __launch_bounds__(S2_BLOCK) void jointBodySumKernel(const s2amdJoint*
 
 JointReportLayout layoutOf(const s2amdSolver* s)
 {
-	return jointReportLayout(s->jointCapacity, s->bodyCapacity, s->jointReportSortTmpBytes);
+	return jointReportLayout(s->jointCapacity, s->bodyCapacity, s->jointReport.sortTmpBytes);
 }
 
-// the counts and the summary of the last step's report, once per step
-int jointReportFetchHead(s2amdSolver* s)
+ReportRef ref(s2amdSolver* s)
 {
-	if (s->jointReportHeadKnown)
-	{
-		return S2AMD_OK;
-	}
 	static_assert(sizeof(s->hJointReportHead) == sizeof(JointReportHead), "the host copy of the report's head");
-	HIP_TRY(hipSetDevice(s->device));
-	const JointReportLayout l = layoutOf(s);
-	HIP_TRY(hipMemcpyAsync(&s->hJointReportHead, (const char*)s->dJointReport.p + l.head, sizeof(JointReportHead), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	s->jointReportHeadKnown = true;
-	return S2AMD_OK;
+	return s ? ReportRef{s, &s->jointReport, &s->hJointReportHead, sizeof(s->hJointReportHead), "joint-report", "s2amd_world_set_joint_report"} : ReportRef{};
 }
 
-// flag 0: any flag will do (s2amd_world_joint_summary)
-int jointReportGetterState(const s2amdSolver* s, int flag, const char* what)
+// where a piece of the block lies, for a getter (0 for the null solver it will refuse)
+size_t at(const s2amdSolver* s, size_t JointReportLayout::*piece)
 {
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	if (flag != 0 ? (s->jointReportStepFlags & flag) == 0 : s->jointReportStepFlags == 0)
-	{
-		return fail(S2AMD_E_STATE, std::string(what) + ": the last s2amd_world_step did not run with this joint-report flag set (s2amd_world_set_joint_report, then a step)");
-	}
-	return S2AMD_OK;
+	return s ? layoutOf(s).*piece : 0;
 }
 
 } // namespace
 
 int jointReportPrepare(s2amdSolver* s)
 {
-	s->jointReportStepFlags = 0;
-	s->jointReportHeadKnown = false;
-	if (s->jointReportFlags == 0 || !s->worldResident)
+	ReportState& r = s->jointReport;
+	if (!reportPrepareBegin(s, r))
 	{
 		return S2AMD_OK;
 	}
@@ -478,15 +454,15 @@ int jointReportPrepare(s2amdSolver* s)
 	{
 		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)2 * nj, 0, bodyKeyBits(nb), s->stream));
 	}
-	s->jointReportSortTmpBytes = tmp;
+	r.sortTmpBytes = tmp;
 	const JointReportLayout l = layoutOf(s);
-	int rc = s->dJointReport.ensure(l.total);
+	int rc = reportPrepareBlock(r, l.total, l.head);
 	if (rc)
 	{
 		return rc;
 	}
 	hipStream_t st = s->stream;
-	char* base = (char*)s->dJointReport.p;
+	char* base = (char*)r.block.p;
 	const s2amdJoint* joints = (const s2amdJoint*)s->dJoints.p;
 	if (nb > 0)
 	{
@@ -509,17 +485,22 @@ int jointReportPrepare(s2amdSolver* s)
 	return S2AMD_OK;
 }
 
-int jointReportEnqueue(s2amdSolver* s)
+int jointReportEnqueue(s2amdSolver* s, const s2amdStepParams*)
 {
-	const int flags = s->jointReportFlags;
+	ReportState& r = s->jointReport;
+	const int flags = r.flags;
 	const int nj = s->jointCapacity, nb = s->bodyCapacity;
 	const JointReportLayout l = layoutOf(s);
-	if (flags == 0 || s->dJointReport.p == nullptr || s->dJointReport.bytes < l.total)
+	if (flags == 0)
 	{
-		return flags == 0 ? S2AMD_OK : fail(S2AMD_E_STATE, "internal: the joint report's device block was not prepared");
+		return S2AMD_OK;
+	}
+	if (int rc = reportEnqueueGuard(r, l.total, "joint"))
+	{
+		return rc;
 	}
 	hipStream_t st = s->stream;
-	char* base = (char*)s->dJointReport.p;
+	char* base = (char*)r.block.p;
 	const s2amdJoint* joints = (const s2amdJoint*)s->dJoints.p;
 	const s2amdBody* bodies = (const s2amdBody*)s->dBodies.p;
 	if (nj > 0)
@@ -544,8 +525,8 @@ int jointReportEnqueue(s2amdSolver* s)
 																													 nb, (s2amdBodyJointSum*)(base + l.sums));
 		HIP_TRY(hipGetLastError());
 	}
-	s->jointReportStepFlags = flags;
-	s->jointReportHeadKnown = nj <= 0; // (a world without joint slots: the head is known without asking the device)
+	r.stepFlags = flags;
+	r.headKnown = nj <= 0; // (a world without joint slots: the head is known without asking the device)
 	return S2AMD_OK;
 }
 
@@ -555,118 +536,34 @@ extern "C"
 
 int s2amd_world_set_joint_report(s2amdSolver* s, int32_t flags)
 {
-	if (!s)
-	{
-		return fail(S2AMD_E_INVALID, "null solver");
-	}
-	if ((flags & ~(S2AMD_JOINT_REPORT_STATES | S2AMD_JOINT_REPORT_LIMITS | S2AMD_JOINT_REPORT_BODY_SUMS)) != 0)
-	{
-		return fail(S2AMD_E_INVALID, "unknown joint-report flag bits");
-	}
-	const bool turnedOn = s->jointReportFlags == 0 && flags != 0;
-	s->jointReportFlags = flags;
-	if (turnedOn)
-	{
-		// "before" starts as the joints stand now; the last step's report (if any) is not of these passes
-		return jointReportPrepare(s);
-	}
-	return S2AMD_OK;
+	return reportSet(ref(s), flags, S2AMD_JOINT_REPORT_STATES | S2AMD_JOINT_REPORT_LIMITS | S2AMD_JOINT_REPORT_BODY_SUMS, jointReportPrepare);
 }
 
 int s2amd_world_joint_states(s2amdSolver* s, s2amdJointState* out, int32_t capacity, int32_t* count)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = jointReportGetterState(s, S2AMD_JOINT_REPORT_STATES, "s2amd_world_joint_states");
-	if (rc || (rc = jointReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*count = s->hJointReportHead.counts[0];
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "joint-state buffer too small");
-	}
-	if (*count > 0)
-	{
-		const JointReportLayout l = layoutOf(s);
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->dJointReport.p + l.records, (size_t)*count * sizeof(s2amdJointState), hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	return reportGetList(ref(s), S2AMD_JOINT_REPORT_STATES, "s2amd_world_joint_states", "joint-state buffer too small", 0, at(s, &JointReportLayout::records), sizeof(*out), out,
+						 capacity, count);
 }
 
 int s2amd_world_joint_limit_events(s2amdSolver* s, int32_t* began, int32_t beganCapacity, int32_t* beganCount, int32_t* ended, int32_t endedCapacity, int32_t* endedCount)
 {
-	if (!s || !beganCount || !endedCount || beganCapacity < 0 || endedCapacity < 0 || (beganCapacity > 0 && !began) || (endedCapacity > 0 && !ended))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = jointReportGetterState(s, S2AMD_JOINT_REPORT_LIMITS, "s2amd_world_joint_limit_events");
-	if (rc || (rc = jointReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*beganCount = s->hJointReportHead.counts[1];
-	*endedCount = s->hJointReportHead.counts[2];
-	if (*beganCount > beganCapacity || *endedCount > endedCapacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "joint limit event buffer too small");
-	}
-	const JointReportLayout l = layoutOf(s);
-	const char* base = (const char*)s->dJointReport.p;
-	if (*beganCount > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(began, base + l.began, (size_t)*beganCount * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	}
-	if (*endedCount > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(ended, base + l.ended, (size_t)*endedCount * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	}
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return reportGetEvents(ref(s), S2AMD_JOINT_REPORT_LIMITS, "s2amd_world_joint_limit_events", "joint limit event buffer too small", 1, at(s, &JointReportLayout::began),
+						   at(s, &JointReportLayout::ended), began, beganCapacity, beganCount, ended, endedCapacity, endedCount);
 }
 
 int s2amd_world_body_joint_sums(s2amdSolver* s, s2amdBodyJointSum* out, int32_t bodyCapacity)
 {
-	if (!s || bodyCapacity < 0 || (bodyCapacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = jointReportGetterState(s, S2AMD_JOINT_REPORT_BODY_SUMS, "s2amd_world_body_joint_sums");
-	if (rc)
-	{
-		return rc;
-	}
-	if (bodyCapacity < s->bodyCapacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "body-sum array smaller than the resident body array");
-	}
-	if (s->bodyCapacity > 0)
-	{
-		HIP_TRY(hipSetDevice(s->device));
-		const JointReportLayout l = layoutOf(s);
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->dJointReport.p + l.sums, (size_t)s->bodyCapacity * sizeof(s2amdBodyJointSum), hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	return reportGetBodyArray(ref(s), S2AMD_JOINT_REPORT_BODY_SUMS, "s2amd_world_body_joint_sums", at(s, &JointReportLayout::sums), sizeof(*out), out, bodyCapacity);
 }
 
 int s2amd_world_joint_summary(s2amdSolver* s, s2amdJointSummary* out)
 {
-	if (!s || !out)
+	const int rc = out ? reportHeadFor(ref(s), 0, "s2amd_world_joint_summary") : fail(S2AMD_E_INVALID, "bad argument");
+	if (rc == S2AMD_OK)
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		*out = s->hJointReportHead.summary;
 	}
-	int rc = jointReportGetterState(s, 0, "s2amd_world_joint_summary");
-	if (rc || (rc = jointReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*out = s->hJointReportHead.summary;
-	return S2AMD_OK;
+	return rc;
 }
 
 } // extern "C"

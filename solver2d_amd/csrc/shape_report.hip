@@ -76,19 +76,14 @@ ShapeReportLayout shapeReportLayout(int ns)
 {
 	ShapeReportLayout l{};
 	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t here = at;
-		at += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-		return here;
-	};
 	l.tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	l.was = take((size_t)ns);
-	l.counts = take((size_t)3 * l.tiles * sizeof(int));
-	l.partials = take((size_t)l.tiles * sizeof(ShapeTilePartial));
-	l.head = take(sizeof(ShapeReportHead));
-	l.entered = take((size_t)ns * sizeof(int32_t));
-	l.left = take((size_t)ns * sizeof(int32_t));
-	l.records = take((size_t)ns * sizeof(s2amdShapeDraw));
+	l.was = reportTake(at, (size_t)ns);
+	l.counts = reportTake(at, (size_t)3 * l.tiles * sizeof(int));
+	l.partials = reportTake(at, (size_t)l.tiles * sizeof(ShapeTilePartial));
+	l.head = reportTake(at, sizeof(ShapeReportHead));
+	l.entered = reportTake(at, (size_t)ns * sizeof(int32_t));
+	l.left = reportTake(at, (size_t)ns * sizeof(int32_t));
+	l.records = reportTake(at, (size_t)ns * sizeof(s2amdShapeDraw));
 	l.total = at;
 	return l;
 }
@@ -485,34 +480,16 @@ ShapeView viewOf(const s2amdSolver* s)
 	return v;
 }
 
-// the counts and the summary of the last step's report, once per step
-int shapeReportFetchHead(s2amdSolver* s)
+ReportRef ref(s2amdSolver* s)
 {
-	if (s->shapeReportHeadKnown)
-	{
-		return S2AMD_OK;
-	}
 	static_assert(sizeof(s->hShapeReportHead) == sizeof(ShapeReportHead), "the host copy of the report's head");
-	HIP_TRY(hipSetDevice(s->device));
-	const ShapeReportLayout l = layoutOf(s);
-	HIP_TRY(hipMemcpyAsync(&s->hShapeReportHead, (const char*)s->dShapeReport.p + l.head, sizeof(ShapeReportHead), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	s->shapeReportHeadKnown = true;
-	return S2AMD_OK;
+	return s ? ReportRef{s, &s->shapeReport, &s->hShapeReportHead, sizeof(s->hShapeReportHead), "shape-report", "s2amd_world_set_shape_report"} : ReportRef{};
 }
 
-// flag 0: any flag will do (s2amd_world_shape_summary)
-int shapeReportGetterState(const s2amdSolver* s, int flag, const char* what)
+// where a piece of the block lies, for a getter (0 for the null solver it will refuse)
+size_t at(const s2amdSolver* s, size_t ShapeReportLayout::*piece)
 {
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	if (flag != 0 ? (s->shapeReportStepFlags & flag) == 0 : s->shapeReportStepFlags == 0)
-	{
-		return fail(S2AMD_E_STATE, std::string(what) + ": the last s2amd_world_step did not run with this shape-report flag set (s2amd_world_set_shape_report, then a step)");
-	}
-	return S2AMD_OK;
+	return s ? layoutOf(s).*piece : 0;
 }
 
 // "before" := in view as the resident shapes stand now, under the view as it is now
@@ -520,54 +497,48 @@ int shapeReportRestate(s2amdSolver* s)
 {
 	const int ns = s->shapeCapacity;
 	const ShapeReportLayout l = layoutOf(s);
-	if (ns <= 0 || s->dShapeReport.p == nullptr || s->dShapeReport.bytes < l.total)
+	if (ns <= 0 || s->shapeReport.block.p == nullptr || s->shapeReport.block.bytes < l.total)
 	{
 		return S2AMD_OK;
 	}
 	HIP_TRY(hipSetDevice(s->device));
 	shapeInitKernel<<<gridFor((size_t)ns), dim3(S2_BLOCK), 0, s->stream>>>((const uint32_t*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, s->bodyCapacity, viewOf(s),
-																		   (uint8_t*)((char*)s->dShapeReport.p + l.was));
+																		   (uint8_t*)((char*)s->shapeReport.block.p + l.was));
 	HIP_TRY(hipGetLastError());
 	return S2AMD_OK;
 }
 
 } // namespace
 
-size_t shapeReportHeadOffset(const s2amdSolver* s)
-{
-	return layoutOf(s).head;
-}
-
 int shapeReportPrepare(s2amdSolver* s)
 {
-	s->shapeReportStepFlags = 0;
-	s->shapeReportHeadKnown = false;
-	if (s->shapeReportFlags == 0 || !s->worldResident)
+	if (!reportPrepareBegin(s, s->shapeReport))
 	{
 		return S2AMD_OK;
 	}
 	const ShapeReportLayout l = layoutOf(s);
-	int rc = s->dShapeReport.ensure(l.total);
-	if (rc)
-	{
-		return rc;
-	}
-	return shapeReportRestate(s);
+	const int rc = reportPrepareBlock(s->shapeReport, l.total, l.head);
+	return rc ? rc : shapeReportRestate(s);
 }
 
-int shapeReportEnqueue(s2amdSolver* s)
+int shapeReportEnqueue(s2amdSolver* s, const s2amdStepParams*)
 {
-	const int flags = s->shapeReportFlags;
+	ReportState& r = s->shapeReport;
+	const int flags = r.flags;
 	const int ns = s->shapeCapacity;
 	const ShapeReportLayout l = layoutOf(s);
-	if (flags == 0 || s->dShapeReport.p == nullptr || s->dShapeReport.bytes < l.total)
+	if (flags == 0)
 	{
-		return flags == 0 ? S2AMD_OK : fail(S2AMD_E_STATE, "internal: the shape report's device block was not prepared");
+		return S2AMD_OK;
+	}
+	if (int rc = reportEnqueueGuard(r, l.total, "shape"))
+	{
+		return rc;
 	}
 	if (ns > 0)
 	{
 		hipStream_t st = s->stream;
-		char* base = (char*)s->dShapeReport.p;
+		char* base = (char*)r.block.p;
 		const uint32_t* shapeWords = (const uint32_t*)s->dShapes.p;
 		const s2amdBody* bodies = (const s2amdBody*)s->dBodies.p;
 		shapeCountKernel<<<dim3((unsigned)l.tiles), dim3(S2_BLOCK), 0, st>>>(shapeWords, (uint8_t*)(base + l.was), ns, l.tiles, bodies, s->bodyCapacity, viewOf(s),
@@ -587,8 +558,8 @@ int shapeReportEnqueue(s2amdSolver* s)
 		s->hShapeReportHead.summary.viewBounds[0] = s->hShapeReportHead.summary.viewBounds[1] = INFINITY;
 		s->hShapeReportHead.summary.viewBounds[2] = s->hShapeReportHead.summary.viewBounds[3] = -INFINITY;
 	}
-	s->shapeReportStepFlags = flags;
-	s->shapeReportHeadKnown = ns <= 0;
+	r.stepFlags = flags;
+	r.headKnown = ns <= 0;
 	return S2AMD_OK;
 }
 
@@ -598,22 +569,7 @@ extern "C"
 
 int s2amd_world_set_shape_report(s2amdSolver* s, int32_t flags)
 {
-	if (!s)
-	{
-		return fail(S2AMD_E_INVALID, "null solver");
-	}
-	if ((flags & ~(S2AMD_SHAPE_REPORT_DRAW | S2AMD_SHAPE_REPORT_VIEW | S2AMD_SHAPE_REPORT_BOUNDS)) != 0)
-	{
-		return fail(S2AMD_E_INVALID, "unknown shape-report flag bits");
-	}
-	const bool turnedOn = s->shapeReportFlags == 0 && flags != 0;
-	s->shapeReportFlags = flags;
-	if (turnedOn)
-	{
-		// "before" starts as the shapes stand now; the last step's report (if any) is not of these passes
-		return shapeReportPrepare(s);
-	}
-	return S2AMD_OK;
+	return reportSet(ref(s), flags, S2AMD_SHAPE_REPORT_DRAW | S2AMD_SHAPE_REPORT_VIEW | S2AMD_SHAPE_REPORT_BOUNDS, shapeReportPrepare);
 }
 
 int s2amd_world_set_shape_view(s2amdSolver* s, const float* box)
@@ -632,7 +588,7 @@ int s2amd_world_set_shape_view(s2amdSolver* s, const float* box)
 		s->shapeView[0] = box[0], s->shapeView[1] = box[1], s->shapeView[2] = box[2], s->shapeView[3] = box[3];
 	}
 	s->shapeViewSet = box != nullptr;
-	if (s->shapeReportFlags != 0 && s->worldResident)
+	if (s->shapeReport.flags != 0 && s->worldResident)
 	{
 		// "before" of the next step is taken under the new view: the change itself is no event
 		return shapeReportRestate(s);
@@ -642,73 +598,24 @@ int s2amd_world_set_shape_view(s2amdSolver* s, const float* box)
 
 int s2amd_world_shape_draws(s2amdSolver* s, s2amdShapeDraw* out, int32_t capacity, int32_t* count)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = shapeReportGetterState(s, S2AMD_SHAPE_REPORT_DRAW, "s2amd_world_shape_draws");
-	if (rc || (rc = shapeReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*count = s->hShapeReportHead.counts[0];
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "shape-draw buffer too small");
-	}
-	if (*count > 0)
-	{
-		const ShapeReportLayout l = layoutOf(s);
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->dShapeReport.p + l.records, (size_t)*count * sizeof(s2amdShapeDraw), hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	return reportGetList(ref(s), S2AMD_SHAPE_REPORT_DRAW, "s2amd_world_shape_draws", "shape-draw buffer too small", 0, at(s, &ShapeReportLayout::records), sizeof(*out), out, capacity,
+						 count);
 }
 
 int s2amd_world_shape_view_events(s2amdSolver* s, int32_t* entered, int32_t enteredCapacity, int32_t* enteredCount, int32_t* left, int32_t leftCapacity, int32_t* leftCount)
 {
-	if (!s || !enteredCount || !leftCount || enteredCapacity < 0 || leftCapacity < 0 || (enteredCapacity > 0 && !entered) || (leftCapacity > 0 && !left))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	int rc = shapeReportGetterState(s, S2AMD_SHAPE_REPORT_VIEW, "s2amd_world_shape_view_events");
-	if (rc || (rc = shapeReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*enteredCount = s->hShapeReportHead.counts[1];
-	*leftCount = s->hShapeReportHead.counts[2];
-	if (*enteredCount > enteredCapacity || *leftCount > leftCapacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "shape view event buffer too small");
-	}
-	const ShapeReportLayout l = layoutOf(s);
-	const char* base = (const char*)s->dShapeReport.p;
-	if (*enteredCount > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(entered, base + l.entered, (size_t)*enteredCount * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	}
-	if (*leftCount > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(left, base + l.left, (size_t)*leftCount * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	}
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return reportGetEvents(ref(s), S2AMD_SHAPE_REPORT_VIEW, "s2amd_world_shape_view_events", "shape view event buffer too small", 1, at(s, &ShapeReportLayout::entered),
+						   at(s, &ShapeReportLayout::left), entered, enteredCapacity, enteredCount, left, leftCapacity, leftCount);
 }
 
 int s2amd_world_shape_summary(s2amdSolver* s, s2amdShapeSummary* out)
 {
-	if (!s || !out)
+	const int rc = out ? reportHeadFor(ref(s), 0, "s2amd_world_shape_summary") : fail(S2AMD_E_INVALID, "bad argument");
+	if (rc == S2AMD_OK)
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		*out = s->hShapeReportHead.summary;
 	}
-	int rc = shapeReportGetterState(s, 0, "s2amd_world_shape_summary");
-	if (rc || (rc = shapeReportFetchHead(s)) != 0)
-	{
-		return rc;
-	}
-	*out = s->hShapeReportHead.summary;
-	return S2AMD_OK;
+	return rc;
 }
 
 } // extern "C"

@@ -5,6 +5,7 @@
 //   solver_plan.cpp       the ten reference drivers as lists of Ops
 //   solver_structure.cpp  islands, groups, strips, colour batches and their device tables
 //   graph_coloring.cpp    greedy colouring, batch formation
+//   report_host.cpp       the host side the reports behind s2amd_world_step share
 #pragma once
 
 #include "launch.h"
@@ -453,6 +454,20 @@ struct SolverStructure
 	int graphLaunches = 0;
 };
 
+// What the host keeps for one report of the resident world (report_host.cpp).  All its device memory is one block, carved by the
+// report's layout function and sized by its prepare (at s2amd_world_upload and when its setter turns it on): a step allocates nothing
+// and waits for nothing -- the getters do.
+struct ReportState
+{
+	int flags = 0;			 // what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
+	int stepFlags = 0;		 // ... and what the last one did: the getters answer for these only
+	bool headKnown = false;	 // the host copy of the head holds the last step's counts and summary (fetched by the first getter that asks)
+	DevBuf block;
+	size_t total = 0;		 // bytes of the block the layout needs, as of the last prepare
+	size_t headOffset = 0;	 // ... and where the head lies in it (tests/hostcheck writes one there, in place of the kernels it cannot run)
+	size_t sortTmpBytes = 0; // rocPRIM's scratch, for the two reports that sort by body
+};
+
 struct AsyncBuild;
 
 // ... and the rest: the device, the wire arrays and the world chain's arrays, what the host knows of them, the options, the plan.
@@ -527,28 +542,17 @@ struct SolverRest
 	std::vector<uint8_t> hSlotBytes;
 	bool slotBytesFresh = false; // hSlotBytes is of the state the device is in right now (cleared by every world call that changes it)
 	std::vector<int32_t> hSeparated;
-	// contact report (contact_report.hip; s2amd_world_set_report): compacted behind stage 4 of the step attempt that stands
-	int reportFlags = 0;	 // S2AMD_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
-	int reportStepFlags = 0; // ... and what the last one did: the getters answer for these only
-	bool reportHeadKnown = false; // hReportHead holds the last step's counts (fetched by the first getter that asks)
+	// The five reports behind s2amd_world_step, in the order a step enqueues them (report_host.cpp: the table and the helpers their host sides
+	// share).  Each has a ReportState and, where its getters read counts or a summary, a typed host copy of the head its write pass leaves.
+	ReportState contactReport; // contact_report.hip; s2amd_world_set_report: S2AMD_REPORT_*
 	int32_t hReportHead[4] = {0, 0, 0, 0}; // {began, ended, touching, 0}
-	DevBuf dReport;			 // one block, carved by reportLayout(): was-touching bytes, tile counts, head, the three lists, sort arrays, body sums
-	size_t reportSortTmpBytes = 0;
-	// joint report (joint_report.hip; s2amd_world_set_joint_report): the same shape, behind the contact report
-	int jointReportFlags = 0;	  // S2AMD_JOINT_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
-	int jointReportStepFlags = 0; // ... and what the last one did
-	bool jointReportHeadKnown = false; // hJointReportHead holds the last step's counts and summary
+	ReportState jointReport; // joint_report.hip; s2amd_world_set_joint_report: S2AMD_JOINT_REPORT_*
 	struct
 	{
 		int32_t counts[4]; // {live, began, ended, 0}
 		s2amdJointSummary summary;
 	} hJointReportHead = {};
-	DevBuf dJointReport;		  // one block, carved by jointReportLayout(): limit-state bytes, tile counts and partials, head, lists, records, adjacency, body sums
-	size_t jointReportSortTmpBytes = 0;
-	// shape report (shape_report.hip; s2amd_world_set_shape_report, s2amd_world_set_shape_view): the same shape, behind the joint report
-	int shapeReportFlags = 0;	  // S2AMD_SHAPE_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
-	int shapeReportStepFlags = 0; // ... and what the last one did
-	bool shapeReportHeadKnown = false; // hShapeReportHead holds the last step's counts and summary
+	ReportState shapeReport; // shape_report.hip; s2amd_world_set_shape_report, s2amd_world_set_shape_view: S2AMD_SHAPE_REPORT_*
 	bool shapeViewSet = false;	  // false: every live shape is in view
 	float shapeView[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // {lower.x, lower.y, upper.x, upper.y}
 	struct
@@ -556,25 +560,19 @@ struct SolverRest
 		int32_t counts[4]; // {in view, entered, left, 0}
 		s2amdShapeSummary summary;
 	} hShapeReportHead = {};
-	DevBuf dShapeReport;		  // one block, carved by shapeReportLayout(): in-view state bytes, tile counts and partials, head, lists, records
-	// body report (body_report.hip; s2amd_world_set_body_report, s2amd_world_set_rest_thresholds): the same shape, behind the shape report
-	int bodyReportFlags = 0;	 // S2AMD_BODY_REPORT_*: what the next s2amd_world_step compacts (0: a step enqueues nothing for it)
-	int bodyReportStepFlags = 0; // ... and what the last one did
-	bool bodyReportHeadKnown = false; // hBodyReportHead holds the last step's counts and summary
+	ReportState bodyReport; // body_report.hip; s2amd_world_set_body_report, s2amd_world_set_rest_thresholds: S2AMD_BODY_REPORT_*
 	float restLinearSpeed = 0.01f, restAngularSpeed = 0.0349065850f, restSeconds = 0.5f; // s2amd_world_set_rest_thresholds
 	struct
 	{
 		int32_t counts[4]; // {records, rested, woke, islands}
 		s2amdBodySummary summary;
 	} hBodyReportHead = {};
-	DevBuf dBodyReport;			 // one block, carved by bodyReportLayout(): pose copies, timers, state bytes, union-find, island sums, tile counts, head, lists, records
-	// step metrics (step_metrics.hip; s2amd_world_set_metrics): one 128-byte record per step into a ring in device memory, behind the body report
-	int metricsFlags = 0;	  // S2AMD_METRICS_*: what the next s2amd_world_step reduces (0: a step enqueues nothing for it)
-	int metricsLength = 0;	  // records the ring holds (1..S2AMD_METRICS_MAX_HISTORY while metricsFlags != 0)
-	int metricsStepFlags = 0; // the flags the last step recorded with (0: it recorded nothing, or the recorder was restarted since)
+	// step metrics (step_metrics.hip; s2amd_world_set_metrics: S2AMD_METRICS_*): one 128-byte record per step into a ring in device memory.
+	// Its block holds the tiles' partials between the two kernels; it has no head (the getters read the ring).
+	ReportState metrics;
+	int metricsLength = 0;	  // records the ring holds (1..S2AMD_METRICS_MAX_HISTORY while metrics.flags != 0)
 	long long metricsWritten = 0; // records written since the recorder was restarted: the next record's `step`
 	DevBuf dMetricsRing;	  // metricsLength records (allocated by the setter)
-	DevBuf dMetricsPartials;  // the tiles' partials between the two kernels, carved by metricsLayout() (sized at upload and by the setter)
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -814,39 +812,60 @@ int refreshConstraintIndexOnDevice(s2amdSolver* s);
 int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
-// contact_report.hip.  reportPrepare: the report's device block for the resident world, its "was touching" bytes from the resident
-// contacts (at s2amd_world_upload and when s2amd_world_set_report turns the report on: nothing is allocated inside a step);
-// reportNoteSetContacts: the slots s2amd_world_set_contacts has just staged take pointCount > 0 of what was written (device pointers);
-// reportEnqueue: the step's report passes on the solve stream, behind the attempt that stands
-int reportPrepare(s2amdSolver* s);
+// The reports behind s2amd_world_step.  Each file keeps its layout, kernels, prepare and enqueue; report_host.cpp holds the table of
+// the five in step order and what their host sides share.
+//   <x>Prepare   the report's device block for the resident world and its "before" state from the arrays just uploaded
+//   <x>Enqueue   the step's passes on the step's stream, behind stage 4 of the attempt that stands (never part of the captured graph)
+int contactReportPrepare(s2amdSolver* s);
+int contactReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+// the slots s2amd_world_set_contacts has just staged take pointCount > 0 of what was written as their "was touching" (device pointers)
 int reportNoteSetContacts(s2amdSolver* s, const int32_t* dSlots, int count, const s2amdContact* dNewContacts);
-int reportEnqueue(s2amdSolver* s);
-// joint_report.hip.  jointReportPrepare: the joint report's device block, its limit-state bytes from the resident joints and the
-// body -> joint adjacency (at s2amd_world_upload and when s2amd_world_set_joint_report turns the report on);
-// jointReportEnqueue: the step's passes on the solve stream, behind the attempt that stands
 int jointReportPrepare(s2amdSolver* s);
-int jointReportEnqueue(s2amdSolver* s);
-// shape_report.hip.  shapeReportPrepare: the shape report's device block and its in-view state bytes from the resident shapes under the
-// view as set (at s2amd_world_upload and when s2amd_world_set_shape_report turns the report on); shapeReportEnqueue: the step's passes on
-// the solve stream, behind the joint report
+int jointReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int shapeReportPrepare(s2amdSolver* s);
-int shapeReportEnqueue(s2amdSolver* s);
-// where the report's head -- int32 counts[4] = {in view, entered, left, 0}, then s2amdShapeSummary -- lies in dShapeReport (the host-side
-// check of tests/hostcheck writes one there, in place of the kernels it cannot run)
-size_t shapeReportHeadOffset(const s2amdSolver* s);
-// body_report.hip.  bodyReportPrepare: the body report's device block, its pose copies from the resident bodies and its timers at +0 (at
-// s2amd_world_upload and when s2amd_world_set_body_report turns the report on); bodyReportEnqueue: the step's passes on the step's stream
-// behind stage 4 (never part of the captured graph); `dt` is the step's params->dt.
+int shapeReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int bodyReportPrepare(s2amdSolver* s);
-int bodyReportEnqueue(s2amdSolver* s, float dt);
-// where the report's head -- int32 counts[4] = {records, rested, woke, islands}, then s2amdBodySummary -- lies in dBodyReport (the
-// host-side sanitizer program writes it in place of the kernels)
-size_t bodyReportHeadOffset(const s2amdSolver* s);
-// step_metrics.hip.  metricsPrepare: restarts the recorder and sizes the partials for the resident world (at s2amd_world_upload and in
-// s2amd_world_set_metrics); metricsEnqueue: the step's two kernels on the step's stream behind stage 4 and the body report (never part
-// of the captured graph); `params` is the step's.
-int metricsPrepare(s2amdSolver* s);
+int bodyReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+int metricsPrepare(s2amdSolver* s); // (restarts the recorder as well)
 int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+
+// report_host.cpp: the walks over the table ...
+void reportsForget(s2amdSolver* s);									 // no report is of the last step any more (a new upload)
+int reportsPrepare(s2amdSolver* s);									 // every prepare, in step order
+int reportsEnqueue(s2amdSolver* s, const s2amdStepParams* params);	 // every enqueue whose report is on, in step order
+void reportsRelease(s2amdSolver* s);								 // every block (s2amd_destroy)
+// ... and the pieces of a report's host side.
+// One report as its helpers see it: the solver, the state, the typed host head, and the names its messages use.  A null solver gives
+// an empty one, which every exported entry point answers with its "bad argument" / "null solver".
+struct ReportRef
+{
+	s2amdSolver* s;
+	ReportState* r;
+	void* head;		  // int32 counts[4], then the summary where the report has one
+	size_t headBytes;
+	const char* name; // "report", "joint-report", ...: as the messages spell it
+	const char* setter;
+};
+// carves `bytes` (at least one) off a block at `at`, 256-byte aligned: the offset of the piece
+size_t reportTake(size_t& at, size_t bytes);
+// prepare: the last step's report is void; false: the report is off or no world is resident, nothing to prepare
+bool reportPrepareBegin(const s2amdSolver* s, ReportState& r);
+// ... the block grown to the layout's `total`, both figures noted
+int reportPrepareBlock(ReportState& r, size_t total, size_t headOffset);
+// enqueue: the block is the one prepare made for a layout of `total` bytes, else E_STATE "internal: the <which> report's device block ..."
+int reportEnqueueGuard(const ReportState& r, size_t total, const char* which);
+// a setter: null and unknown-bits checks, the flags, and `prepare` when the report is turned on
+int reportSet(const ReportRef& f, int32_t flags, int32_t known, int (*prepare)(s2amdSolver*));
+// a getter's state: a resident world whose last step ran with `flag` (0: any flag) set, and the head of that step on the host
+int reportHeadFor(const ReportRef& f, int flag, const char* what);
+// the three getter shapes, each with its argument check, reportHeadFor, the capacity check (message `tooSmall`) and the copy:
+// one list counted by counts[countIndex] ...
+int reportGetList(const ReportRef& f, int flag, const char* what, const char* tooSmall, int countIndex, size_t offset, size_t size, void* out, int32_t capacity, int32_t* count);
+// ... two lists of slots counted by counts[firstIndex] and counts[firstIndex + 1] ...
+int reportGetEvents(const ReportRef& f, int flag, const char* what, const char* tooSmall, int firstIndex, size_t firstOffset, size_t secondOffset, int32_t* first,
+					int32_t firstCapacity, int32_t* firstCount, int32_t* second, int32_t secondCapacity, int32_t* secondCount);
+// ... and one entry per resident body slot (no count, so no head either)
+int reportGetBodyArray(const ReportRef& f, int flag, const char* what, size_t offset, size_t size, void* out, int32_t bodyCapacity);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

@@ -77,17 +77,12 @@ MetricsLayout metricsLayout(int nc, int nb, int nj)
 {
 	MetricsLayout l{};
 	size_t at = 0;
-	auto take = [&](size_t bytes) {
-		const size_t here = at;
-		at += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-		return here;
-	};
 	l.contactTiles = (nc + S2_BLOCK - 1) / S2_BLOCK, l.bodyTiles = (nb + S2_BLOCK - 1) / S2_BLOCK, l.jointTiles = (nj + S2_BLOCK - 1) / S2_BLOCK;
-	l.contactPartials = take((size_t)l.contactTiles * sizeof(ContactTilePartial));
-	l.bodyCounts = take((size_t)l.bodyTiles * sizeof(int32_t));
-	l.jointPartials = take((size_t)l.jointTiles * sizeof(JointTilePartial));
+	l.contactPartials = reportTake(at, (size_t)l.contactTiles * sizeof(ContactTilePartial));
+	l.bodyCounts = reportTake(at, (size_t)l.bodyTiles * sizeof(int32_t));
+	l.jointPartials = reportTake(at, (size_t)l.jointTiles * sizeof(JointTilePartial));
 	l.sumStride = (std::max(std::max(l.contactTiles, l.bodyTiles), std::max(l.jointTiles, 1)) + 63) & ~63;
-	l.sums = take((size_t)S2_SUM_COUNT * l.sumStride * sizeof(float));
+	l.sums = reportTake(at, (size_t)S2_SUM_COUNT * l.sumStride * sizeof(float));
 	l.total = at;
 	return l;
 }
@@ -520,18 +515,17 @@ int metricsFetch(s2amdSolver* s, s2amdStepMetrics* out, int first, int count)
 
 int metricsPrepare(s2amdSolver* s)
 {
-	s->metricsStepFlags = 0;
 	s->metricsWritten = 0;
-	if (s->metricsFlags == 0 || !s->worldResident)
+	if (!reportPrepareBegin(s, s->metrics))
 	{
 		return S2AMD_OK;
 	}
-	return s->dMetricsPartials.ensure(metricsLayout(s->contactCapacity, s->bodyCapacity, s->jointCapacity).total);
+	return reportPrepareBlock(s->metrics, metricsLayout(s->contactCapacity, s->bodyCapacity, s->jointCapacity).total, 0);
 }
 
 int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params)
 {
-	const int flags = s->metricsFlags;
+	const int flags = s->metrics.flags;
 	if (flags == 0)
 	{
 		return S2AMD_OK;
@@ -539,11 +533,11 @@ int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params)
 	const int nc = s->contactCapacity, nb = s->bodyCapacity, nj = s->jointCapacity;
 	const MetricsLayout l = metricsLayout(nc, nb, nj);
 	if (s->metricsLength < 1 || s->dMetricsRing.p == nullptr || s->dMetricsRing.bytes < (size_t)s->metricsLength * sizeof(s2amdStepMetrics) ||
-		s->dMetricsPartials.p == nullptr || s->dMetricsPartials.bytes < l.total)
+		s->metrics.block.p == nullptr || s->metrics.block.bytes < l.total)
 	{
 		return fail(S2AMD_E_STATE, "internal: the step metrics' device blocks were not prepared");
 	}
-	char* base = (char*)s->dMetricsPartials.p;
+	char* base = (char*)s->metrics.block.p;
 	MetricsBuffers buffers;
 	buffers.contactPartials = (ContactTilePartial*)(base + l.contactPartials);
 	buffers.bodyCounts = (int32_t*)(base + l.bodyCounts);
@@ -567,7 +561,7 @@ int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params)
 	metricsFinishKernel<<<dim3(1), dim3(S2_BLOCK), 0, st>>>(step, buffers, (uint4*)((s2amdStepMetrics*)s->dMetricsRing.p + position));
 	HIP_TRY(hipGetLastError());
 	s->metricsWritten += 1;
-	s->metricsStepFlags = flags;
+	s->metrics.stepFlags = flags;
 	return S2AMD_OK;
 }
 
@@ -605,7 +599,7 @@ int s2amd_world_set_metrics(s2amdSolver* s, int32_t flags, int32_t historyLength
 		}
 		s->metricsLength = historyLength;
 	}
-	s->metricsFlags = flags;
+	s->metrics.flags = flags;
 	return metricsPrepare(s);
 }
 
@@ -620,7 +614,7 @@ int s2amd_world_metrics(s2amdSolver* s, s2amdStepMetrics* out)
 	{
 		return rc;
 	}
-	if (s->metricsStepFlags == 0 || s->metricsWritten < 1)
+	if (s->metrics.stepFlags == 0 || s->metricsWritten < 1)
 	{
 		return fail(S2AMD_E_STATE, "s2amd_world_metrics: the last s2amd_world_step recorded nothing (s2amd_world_set_metrics, then a step)");
 	}
@@ -643,7 +637,7 @@ int s2amd_world_metrics_history(s2amdSolver* s, s2amdStepMetrics* out, int32_t c
 	{
 		return rc;
 	}
-	if (s->metricsFlags == 0)
+	if (s->metrics.flags == 0)
 	{
 		return fail(S2AMD_E_STATE, "s2amd_world_metrics_history: the recorder is off (s2amd_world_set_metrics)");
 	}

@@ -533,11 +533,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		}
 	}
 	s->worldResident = false;
-	s->reportStepFlags = 0;
-	s->jointReportStepFlags = 0;
-	s->shapeReportStepFlags = 0;
-	s->bodyReportStepFlags = 0;
-	s->metricsStepFlags = 0;
+	reportsForget(s);
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -626,33 +622,10 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	s->shapeCapacity = shapeCapacity;
 	s->worldResident = true;
+	// (the reports' blocks and their "before" states from the arrays just uploaded, the step metrics' recorder restarted: report_host.cpp)
+	if ((rc = reportsPrepare(s)) != 0)
 	{
-		// (the contact report's block and its "was touching" bytes, from the contacts just uploaded: contact_report.hip)
-		int rcReport = reportPrepare(s);
-		if (rcReport)
-		{
-			return rcReport;
-		}
-		// (... and the joint report's: limit-state bytes and the body -> joint adjacency from the joints just uploaded: joint_report.hip)
-		if ((rcReport = jointReportPrepare(s)) != 0)
-		{
-			return rcReport;
-		}
-		// (... and the shape report's: in-view state bytes from the shapes just uploaded, under the view as set: shape_report.hip)
-		if ((rcReport = shapeReportPrepare(s)) != 0)
-		{
-			return rcReport;
-		}
-		// (... and the body report's: pose copies from the bodies just uploaded, timers at +0: body_report.hip)
-		if ((rcReport = bodyReportPrepare(s)) != 0)
-		{
-			return rcReport;
-		}
-		// (... and the step metrics': the recorder restarts, the tiles' partials fit the capacities just uploaded: step_metrics.hip)
-		if ((rcReport = metricsPrepare(s)) != 0)
-		{
-			return rcReport;
-		}
+		return rc;
 	}
 	if (s->optAsyncBuild != 0)
 	{
@@ -1012,32 +985,9 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 			return rc;
 		}
 	}
-	s->reportStepFlags = 0;
-	if (s->reportFlags != 0 && (rc = reportEnqueue(s)) != 0)
+	if ((rc = reportsEnqueue(s, params)) != 0)
 	{
-		// (the contact report of the attempt that stands, enqueued behind its impulse store and stage 4: a repeated step reports once;
-		// nothing waits for it here -- contact_report.hip)
-		return rc;
-	}
-	s->jointReportStepFlags = 0;
-	if (s->jointReportFlags != 0 && (rc = jointReportEnqueue(s)) != 0)
-	{
-		return rc; // (the joint report, the same way: joint_report.hip)
-	}
-	s->shapeReportStepFlags = 0;
-	if (s->shapeReportFlags != 0 && (rc = shapeReportEnqueue(s)) != 0)
-	{
-		return rc; // (the shape report, the same way: shape_report.hip)
-	}
-	s->bodyReportStepFlags = 0;
-	if (s->bodyReportFlags != 0 && (rc = bodyReportEnqueue(s, params->dt)) != 0)
-	{
-		return rc; // (the body report, the same way: body_report.hip)
-	}
-	s->metricsStepFlags = 0;
-	if (s->metricsFlags != 0 && (rc = metricsEnqueue(s, params)) != 0)
-	{
-		return rc; // (the step metrics, the same way: step_metrics.hip)
+		return rc; // (contact, joint, shape and body report, then the step metrics: report_host.cpp)
 	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;

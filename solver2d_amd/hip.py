@@ -429,6 +429,39 @@ class Solver:
                                            wire.as_ptr(origins), wire.as_ptr(status)))
         return bodies, contacts, joints, shapes, pairs, origins, status
 
+    # ---- the reports of the resident world: the three shapes their getters have ----
+    def _world_list(self, fn, dtype, expected):
+        """One counted list: grown to the count the library states when it answers S2AMD_E_CAPACITY (the count is set, nothing was consumed)."""
+        cap = max(int(expected), 1)
+        while True:
+            out = np.zeros(cap, dtype=dtype)
+            n = ctypes.c_int32()
+            rc = fn(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
+                cap = n.value
+                continue
+            self._ck(rc)
+            return out[: n.value].copy()
+
+    def _world_event_pair(self, fn, expected):
+        """Two counted lists of int32 codes, grown the same way."""
+        cap_a = cap_b = max(int(expected), 1)
+        while True:
+            a, b = np.zeros(cap_a, dtype=np.int32), np.zeros(cap_b, dtype=np.int32)
+            na, nb = ctypes.c_int32(), ctypes.c_int32()
+            rc = fn(self._h, wire.as_ptr(a), cap_a, ctypes.byref(na), wire.as_ptr(b), cap_b, ctypes.byref(nb))
+            if rc == -5 and (na.value > cap_a or nb.value > cap_b):  # S2AMD_E_CAPACITY
+                cap_a, cap_b = max(cap_a, na.value), max(cap_b, nb.value)
+                continue
+            self._ck(rc)
+            return a[: na.value].copy(), b[: nb.value].copy()
+
+    def _world_record(self, fn, dtype):
+        """One record."""
+        out = np.zeros(1, dtype=dtype)
+        self._ck(fn(self._h, wire.as_ptr(out)))
+        return out[0]
+
     # ---- contact report of the resident world (s2amd_world_set_report): what touches what, and how hard ----
     def world_set_report(self, flags):
         """wire.REPORT_* bits: what every world_step from the next one on compacts on the device (0: nothing, the default)."""
@@ -436,29 +469,11 @@ class Solver:
 
     def world_touch_events(self, expected=64):
         """(began, ended): the contact slots that started / stopped touching in the last world_step, each ascending."""
-        cap_b = cap_e = max(int(expected), 1)
-        while True:
-            began, ended = np.zeros(cap_b, dtype=np.int32), np.zeros(cap_e, dtype=np.int32)
-            nb, ne = ctypes.c_int32(), ctypes.c_int32()
-            rc = self._L.s2amd_world_touch_events(self._h, wire.as_ptr(began), cap_b, ctypes.byref(nb), wire.as_ptr(ended), cap_e, ctypes.byref(ne))
-            if rc == -5 and (nb.value > cap_b or ne.value > cap_e):  # S2AMD_E_CAPACITY: the counts are set, nothing was consumed
-                cap_b, cap_e = max(cap_b, nb.value), max(cap_e, ne.value)
-                continue
-            self._ck(rc)
-            return began[: nb.value].copy(), ended[: ne.value].copy()
+        return self._world_event_pair(self._L.s2amd_world_touch_events, expected)
 
     def world_touching(self, expected=1024):
         """wire.touching_contact_dtype records of the contacts touching after the last world_step, ascending by slot."""
-        cap = max(int(expected), 1)
-        while True:
-            out = np.zeros(cap, dtype=wire.touching_contact_dtype)
-            n = ctypes.c_int32()
-            rc = self._L.s2amd_world_touching(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
-            if rc == -5 and n.value > cap:
-                cap = n.value
-                continue
-            self._ck(rc)
-            return out[: n.value].copy()
+        return self._world_list(self._L.s2amd_world_touching, wire.touching_contact_dtype, expected)
 
     def world_body_sums(self, body_capacity=None):
         """wire.body_contact_sum_dtype per body slot: net contact impulse, normal load and touching count after the last world_step
@@ -476,30 +491,12 @@ class Solver:
 
     def world_joint_states(self, expected=256):
         """wire.joint_state_dtype records of the live joint slots after the last world_step, ascending by slot."""
-        cap = max(int(expected), 1)
-        while True:
-            out = np.zeros(cap, dtype=wire.joint_state_dtype)
-            n = ctypes.c_int32()
-            rc = self._L.s2amd_world_joint_states(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
-            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY: the count is set, nothing was consumed
-                cap = n.value
-                continue
-            self._ck(rc)
-            return out[: n.value].copy()
+        return self._world_list(self._L.s2amd_world_joint_states, wire.joint_state_dtype, expected)
 
     def world_joint_limit_events(self, expected=64):
         """(began, ended): the codes 2 * slot + side (0 lower, 1 upper) of the joint limits that became / stopped being active in the
         last world_step, each ascending."""
-        cap_b = cap_e = max(int(expected), 1)
-        while True:
-            began, ended = np.zeros(cap_b, dtype=np.int32), np.zeros(cap_e, dtype=np.int32)
-            nb, ne = ctypes.c_int32(), ctypes.c_int32()
-            rc = self._L.s2amd_world_joint_limit_events(self._h, wire.as_ptr(began), cap_b, ctypes.byref(nb), wire.as_ptr(ended), cap_e, ctypes.byref(ne))
-            if rc == -5 and (nb.value > cap_b or ne.value > cap_e):
-                cap_b, cap_e = max(cap_b, nb.value), max(cap_e, ne.value)
-                continue
-            self._ck(rc)
-            return began[: nb.value].copy(), ended[: ne.value].copy()
+        return self._world_event_pair(self._L.s2amd_world_joint_limit_events, expected)
 
     def world_body_joint_sums(self, body_capacity=None):
         """wire.body_joint_sum_dtype per body slot: net joint impulse, axial impulse and joint count after the last world_step
@@ -512,9 +509,7 @@ class Solver:
 
     def world_joint_summary(self):
         """One wire.joint_summary_dtype record: joint counts, limits active, the largest anchor gap after the last world_step."""
-        out = np.zeros(1, dtype=wire.joint_summary_dtype)
-        self._ck(self._L.s2amd_world_joint_summary(self._h, wire.as_ptr(out)))
-        return out[0]
+        return self._world_record(self._L.s2amd_world_joint_summary, wire.joint_summary_dtype)
 
     # ---- shape report of the resident world (s2amd_world_set_shape_report): draw records, view events, bounds ----
     def world_set_shape_report(self, flags):
@@ -532,35 +527,15 @@ class Solver:
 
     def world_shape_draws(self, expected=1024):
         """wire.shape_draw_dtype records of the live shapes in view after the last world_step, ascending by shape slot."""
-        cap = max(int(expected), 1)
-        while True:
-            out = np.zeros(cap, dtype=wire.shape_draw_dtype)
-            n = ctypes.c_int32()
-            rc = self._L.s2amd_world_shape_draws(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
-            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY: the count is set, nothing was consumed
-                cap = n.value
-                continue
-            self._ck(rc)
-            return out[: n.value].copy()
+        return self._world_list(self._L.s2amd_world_shape_draws, wire.shape_draw_dtype, expected)
 
     def world_shape_view_events(self, expected=64):
         """(entered, left): the shape slots that came into / went out of view in the last world_step, each ascending."""
-        cap_e = cap_l = max(int(expected), 1)
-        while True:
-            entered, left = np.zeros(cap_e, dtype=np.int32), np.zeros(cap_l, dtype=np.int32)
-            ne, nl = ctypes.c_int32(), ctypes.c_int32()
-            rc = self._L.s2amd_world_shape_view_events(self._h, wire.as_ptr(entered), cap_e, ctypes.byref(ne), wire.as_ptr(left), cap_l, ctypes.byref(nl))
-            if rc == -5 and (ne.value > cap_e or nl.value > cap_l):
-                cap_e, cap_l = max(cap_e, ne.value), max(cap_l, nl.value)
-                continue
-            self._ck(rc)
-            return entered[: ne.value].copy(), left[: nl.value].copy()
+        return self._world_event_pair(self._L.s2amd_world_shape_view_events, expected)
 
     def world_shape_summary(self):
         """One wire.shape_summary_dtype record: shape counts, shapes in view, the movable and the in-view bounds after the last world_step."""
-        out = np.zeros(1, dtype=wire.shape_summary_dtype)
-        self._ck(self._L.s2amd_world_shape_summary(self._h, wire.as_ptr(out)))
-        return out[0]
+        return self._world_record(self._L.s2amd_world_shape_summary, wire.shape_summary_dtype)
 
     # ---- body report of the resident world (s2amd_world_set_body_report): states, rest events, islands ----
     def world_set_body_report(self, flags):
@@ -571,44 +546,21 @@ class Solver:
         """At rest: speed <= linear_speed and |w| <= angular_speed for `seconds`; holds from the next world_step on."""
         self._ck(self._L.s2amd_world_set_rest_thresholds(self._h, float(np.float32(linear_speed)), float(np.float32(angular_speed)), float(np.float32(seconds))))
 
-    def _world_body_list(self, fn, dtype, expected):
-        cap = max(int(expected), 1)
-        while True:
-            out = np.zeros(cap, dtype=dtype)
-            n = ctypes.c_int32()
-            rc = fn(self._h, wire.as_ptr(out), cap, ctypes.byref(n))
-            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY: the count is set, nothing was consumed
-                cap = n.value
-                continue
-            self._ck(rc)
-            return out[: n.value].copy()
-
     def world_body_states(self, expected=1024):
         """wire.body_state_dtype records of the reported bodies (under MOVED_ONLY: the moved ones) after the last world_step, ascending by slot."""
-        return self._world_body_list(self._L.s2amd_world_body_states, wire.body_state_dtype, expected)
+        return self._world_list(self._L.s2amd_world_body_states, wire.body_state_dtype, expected)
 
     def world_body_rest_events(self, expected=64):
         """(rested, woke): the body slots that came to rest / woke up in the last world_step, each ascending."""
-        cap_r = cap_w = max(int(expected), 1)
-        while True:
-            rested, woke = np.zeros(cap_r, dtype=np.int32), np.zeros(cap_w, dtype=np.int32)
-            nr, nw = ctypes.c_int32(), ctypes.c_int32()
-            rc = self._L.s2amd_world_body_rest_events(self._h, wire.as_ptr(rested), cap_r, ctypes.byref(nr), wire.as_ptr(woke), cap_w, ctypes.byref(nw))
-            if rc == -5 and (nr.value > cap_r or nw.value > cap_w):
-                cap_r, cap_w = max(cap_r, nr.value), max(cap_w, nw.value)
-                continue
-            self._ck(rc)
-            return rested[: nr.value].copy(), woke[: nw.value].copy()
+        return self._world_event_pair(self._L.s2amd_world_body_rest_events, expected)
 
     def world_islands(self, expected=256):
         """wire.island_state_dtype records of the islands of the world as it stands after the last world_step, by lowest body slot."""
-        return self._world_body_list(self._L.s2amd_world_islands, wire.island_state_dtype, expected)
+        return self._world_list(self._L.s2amd_world_islands, wire.island_state_dtype, expected)
 
     def world_body_summary(self):
         """One wire.body_summary_dtype record: body, rest and island counts, the largest island, the fastest body after the last world_step."""
-        out = np.zeros(1, dtype=wire.body_summary_dtype)
-        self._ck(self._L.s2amd_world_body_summary(self._h, wire.as_ptr(out)))
-        return out[0]
+        return self._world_record(self._L.s2amd_world_body_summary, wire.body_summary_dtype)
 
     # ---- step metrics of the resident world (s2amd_world_set_metrics): one record per step, kept in a ring on the device ----
     def world_set_metrics(self, flags, history_length=1):
@@ -618,13 +570,11 @@ class Solver:
 
     def world_metrics(self):
         """One wire.step_metrics_dtype record: the last world_step's."""
-        out = np.zeros(1, dtype=wire.step_metrics_dtype)
-        self._ck(self._L.s2amd_world_metrics(self._h, wire.as_ptr(out)))
-        return out[0]
+        return self._world_record(self._L.s2amd_world_metrics, wire.step_metrics_dtype)
 
     def world_metrics_history(self, expected=wire.METRICS_MAX_HISTORY):
         """wire.step_metrics_dtype records of the steps the ring still holds, oldest first, in one read."""
-        return self._world_body_list(self._L.s2amd_world_metrics_history, wire.step_metrics_dtype, expected)
+        return self._world_list(self._L.s2amd_world_metrics_history, wire.step_metrics_dtype, expected)
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

@@ -6,34 +6,7 @@
 // record's `step` at position step % length): what is checked is that the host side touches only memory it owns -- every output buffer
 // is a heap block of exactly the size passed -- and that the history comes out oldest first.  Built and run by
 // tests/test_step_metrics_host.py.
-#include "solver_internal.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-static int failures = 0;
-
-#define EXPECT(expr, want)                                                                                   \
-	do                                                                                                       \
-	{                                                                                                        \
-		const int got_ = (expr);                                                                             \
-		if (got_ != (want))                                                                                  \
-		{                                                                                                    \
-			printf("line %d: %s = %d, expected %d (%s)\n", __LINE__, #expr, got_, (int)(want), s2amd_last_error()); \
-			failures += 1;                                                                                   \
-		}                                                                                                    \
-	} while (0)
-
-struct World
-{
-	std::vector<s2amdBody> bodies;
-	std::vector<s2amdContact> contacts;
-	std::vector<s2amdJoint> joints;
-	std::vector<s2amdShape> shapes;
-	std::vector<s2amdPairState> pairs;
-	std::vector<float> origins;
-};
+#include "report_main_common.h"
 
 // body 0 static with a ground box; `count` unit-mass bodies above it, one small box each that collides with nothing; `contactSlots` free
 // contact slots and `jointSlots` free joint slots (the metrics' tiles are sized by the capacities, whatever the slots hold)
@@ -90,12 +63,6 @@ static World makeWorld(int count, int contactSlots, int jointSlots)
 	return w;
 }
 
-static int upload(s2amdSolver* s, const World& w)
-{
-	return s2amd_world_upload(s, w.bodies.data(), (int32_t)w.bodies.size(), w.contacts.data(), (int32_t)w.contacts.size(), w.joints.data(), (int32_t)w.joints.size(),
-							  w.shapes.data(), (int32_t)w.shapes.size(), w.pairs.data(), w.origins.data());
-}
-
 // in place of the finishing kernel: the record of step `step` at its ring position
 static void writeRecord(s2amdSolver* s, int step, int flags, int length)
 {
@@ -104,18 +71,10 @@ static void writeRecord(s2amdSolver* s, int step, int flags, int length)
 	memcpy((s2amdStepMetrics*)s->dMetricsRing.p + step % length, &r, sizeof(r));
 }
 
-// a heap block of exactly n records (n == 0: a null pointer)
-struct Exact
-{
-	s2amdStepMetrics* p;
-	explicit Exact(int n) : p(n > 0 ? (s2amdStepMetrics*)malloc((size_t)n * sizeof(s2amdStepMetrics)) : nullptr) {}
-	~Exact() { free(p); }
-};
-
 // the history with a buffer of `capacity` records; on success the steps are wantFirst, wantFirst + 1, ...
 static void askHistory(s2amdSolver* s, int capacity, int wantRc, int wantCount, int wantFirst)
 {
-	Exact out(capacity);
+	Exact<s2amdStepMetrics> out(capacity);
 	int32_t count = -7;
 	EXPECT(s2amd_world_metrics_history(s, out.p, capacity, &count), wantRc);
 	EXPECT(count, wantCount);
