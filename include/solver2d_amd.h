@@ -748,6 +748,71 @@ typedef struct s2amdStepMetrics /* 128 bytes */
 int s2amd_world_metrics(s2amdSolver* solver, s2amdStepMetrics* out);
 int s2amd_world_metrics_history(s2amdSolver* solver, s2amdStepMetrics* out, int32_t capacity, int32_t* count);
 
+/* (additive, API 5) Scene queries: "what is here?" asked of the resident world -- a mouse pick, a sensor sweep, a line-of-sight test --
+ * without a host copy of the shapes or the trees.  The reference's world query is s2World_QueryAABB (src/world.c:605-615); picking in its
+ * samples is that query followed by s2Shape_TestPoint (src/shape.c:110-137); its ray functions are s2RayCastCircle / Capsule / Segment /
+ * Polygon (src/geometry.c:393-730) and s2DynamicTree_RayCast (src/dynamic_tree.c:1213-1290).  The three batched calls below answer from the
+ * resident arrays.  They describe the world as it stands -- after the last s2amd_world_upload, s2amd_world_step or
+ * s2amd_world_set_contacts --, are enqueued behind it on the solver's stream, may be called any number of times between steps, change
+ * nothing resident, add no host wait to a step, and do not need the device trees of s2amd_world_set_tree.  S2AMD_E_STATE without a
+ * resident world; count == 0 succeeds and touches nothing.  Every answer is an order-free statement:
+ *   A shape slot is LIVE when type != S2AMD_SHAPE_FREE.  xf(body) = {origins[body], bodies[body].rot}, the resident arrays S2_TRANSFORM
+ *   reads.  A shape s PASSES a query q when (s.categoryBits & q.maskBits) != 0, as in the trees' filtered walks
+ *   (src/dynamic_tree.c:1145, :1253).
+ *   s2amd_world_query_boxes   the hits of box q: the live shapes that pass and satisfy s2AABB_Overlaps(fatAABB, q.box)
+ *                             (include/solver2d/aabb.h:111), ascending by slot.  With maskBits 0xFFFFFFFF this is the set s2World_QueryAABB
+ *                             calls back for, in every world whose shapes have non-zero category bits.
+ *   s2amd_world_point_probe   candidates: live, passing, s2AABB_Overlaps(fatAABB, {p, p}).  A candidate is a hit when s2PointInCircle /
+ *                             Capsule / Polygon(s2InvTransformPoint(xf(body), p), geometry) is true (src/shape.c:110-137; s2PointInPolygon
+ *                             is the GJK call of src/geometry.c:376-389); segments never hit.  Ascending by slot.
+ *   Both lists come in CSR form: the hits of query i are shapes[offsets[i] .. offsets[i + 1]), *total = offsets[count].  When capacity <
+ *   *total the call returns S2AMD_E_CAPACITY with offsets and *total filled and shapes untouched; the caller asks again (as
+ *   s2amd_world_find_pairs).
+ *   s2amd_world_ray_cast      s2IsValidRay (src/geometry.c:15-20) is checked on the host for every ray before anything is enqueued: one
+ *                             failing ray makes the whole call return S2AMD_E_INVALID with hits untouched (the reference only asserts).
+ *                             The segment box runs from s2Min(p1, t) to s2Max(p1, t) with t = s2MulAdd(p1, maxFraction, s2Sub(p2, p1))
+ *                             (src/dynamic_tree.c:1231-1238).  Candidates: live, passing, s2AABB_Overlaps(fatAABB, segment box) -- no other
+ *                             pruning decides a result.  For a candidate both p1 and p2 go through s2InvTransformPoint(xf(body), .),
+ *                             maxFraction unchanged, then s2RayCast<type>, capsules through the circle fallbacks as src/geometry.c:450-581.
+ *                             The answer is the candidate with hit == true and the smallest fraction, compared as float values (-0 equals
+ *                             +0), ties to the lowest shape slot.  fraction = the winner's own bits; normal = s2RotateVector(rot,
+ *                             output.normal); point = s2MulAdd(p1, fraction, s2Sub(p2, p1)) on the world-space inputs; body = the shape's
+ *                             body.  No hit: shape = body = -1, fraction = maxFraction, the rest +0.
+ *                             The reference has no world-level ray cast: this composition is ours -- the closest-hit use of
+ *                             s2DynamicTree_RayCast restated without its traversal order (shrinking maxFraction during a walk only changes
+ *                             hit or no-hit for shapes beyond the current best).
+ * All arithmetic is fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in
+ * libs2amd.so and in libs2amd_fast.so alike. */
+typedef struct s2amdRay /* 24 bytes */
+{
+	float p1[2], p2[2];
+	float maxFraction;
+	uint32_t maskBits;
+} s2amdRay;
+typedef struct s2amdRayHit /* 32 bytes */
+{
+	int32_t shape, body;
+	float fraction;
+	float point[2];
+	float normal[2];
+	int32_t pad;
+} s2amdRayHit;
+typedef struct s2amdPointProbe /* 12 bytes */
+{
+	float p[2];
+	uint32_t maskBits;
+} s2amdPointProbe;
+typedef struct s2amdBoxQuery /* 20 bytes */
+{
+	float box[4]; /* {lower.x, lower.y, upper.x, upper.y} */
+	uint32_t maskBits;
+} s2amdBoxQuery;
+int s2amd_world_ray_cast(s2amdSolver* solver, const s2amdRay* rays, int32_t count, s2amdRayHit* hits /* [count] */);
+int s2amd_world_point_probe(s2amdSolver* solver, const s2amdPointProbe* probes, int32_t count, int32_t* offsets /* [count + 1] */, int32_t* shapes,
+							int32_t capacity, int32_t* total);
+int s2amd_world_query_boxes(s2amdSolver* solver, const s2amdBoxQuery* boxes, int32_t count, int32_t* offsets /* [count + 1] */, int32_t* shapes,
+							int32_t capacity, int32_t* total);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

@@ -533,6 +533,8 @@ struct SolverRest
 	unsigned long long* hostPairLog = nullptr; // ... its pinned host copy (the host appends, the device reads)
 	bool pairLogDirty = false;
 	DevBuf dShapeBoxes;		// world chain: s2amd_world_download_boxes' staging
+	DevBuf dQuery;			// scene queries (scene_query.hip): the queries, the passes' scratch and the results of one call; grows on demand, kept between calls
+	std::vector<int32_t> hQueryStage; // ... where the list calls' {offsets, entries} land before they are split into the caller's two arrays
 	DevBuf dRefitOrder, dStepBack; // s2amd_world_set_refit_order; staging of s2amd_world_download_step {count, moved boxes} and the poses
 	int refitOrderCount = 0;
 	int optTreeStream = 1;		  // "tree_stream": the device trees' rebuild on a stream of its own beside stage 3 and the solve (0: on the step's stream; tree_mirror.hip)

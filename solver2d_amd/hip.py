@@ -31,6 +31,7 @@ EXPORTS = [
     "s2amd_world_set_body_report", "s2amd_world_set_rest_thresholds", "s2amd_world_body_states", "s2amd_world_body_rest_events", "s2amd_world_islands",
     "s2amd_world_body_summary",
     "s2amd_world_set_metrics", "s2amd_world_metrics", "s2amd_world_metrics_history",
+    "s2amd_world_ray_cast", "s2amd_world_point_probe", "s2amd_world_query_boxes",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -121,6 +122,9 @@ def load(fast=False):
     L.s2amd_world_set_metrics.argtypes = [vp, i32, i32]
     L.s2amd_world_metrics.argtypes = [vp, vp]
     L.s2amd_world_metrics_history.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_ray_cast.argtypes = [vp, vp, i32, vp]
+    L.s2amd_world_point_probe.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_query_boxes.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -428,6 +432,39 @@ class Solver:
         self._ck(self._L.s2amd_world_download(self._h, *self._args(bodies, contacts, joints), wire.as_ptr(shapes), len(shapes), wire.as_ptr(pairs),
                                            wire.as_ptr(origins), wire.as_ptr(status)))
         return bodies, contacts, joints, shapes, pairs, origins, status
+
+    # ---- scene queries on the resident world: the world as it stands now, nothing resident changes ----
+    def world_ray_cast(self, rays):
+        """Closest hit of every ray (wire.ray_dtype) -> wire.ray_hit_dtype[len(rays)]; shape == -1: no hit."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == wire.ray_dtype
+        hits = np.zeros(len(rays), dtype=wire.ray_hit_dtype)
+        self._ck(self._L.s2amd_world_ray_cast(self._h, wire.as_ptr(rays), len(rays), wire.as_ptr(hits)))
+        return hits
+
+    def _world_csr(self, fn, queries, dtype, expected):
+        """(offsets, shapes) of a list query: asked again with the total the library states when it answers S2AMD_E_CAPACITY."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.dtype == dtype
+        offsets = np.zeros(len(queries) + 1, dtype=np.int32)
+        cap = max(int(expected), 1)
+        while True:
+            shapes = np.zeros(cap, dtype=np.int32)
+            n = ctypes.c_int32()
+            rc = fn(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(shapes), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
+                cap = n.value
+                continue
+            self._ck(rc)
+            return offsets, shapes[: n.value].copy()
+
+    def world_point_probe(self, probes, expected=None):
+        """The shapes that contain each point (wire.point_probe_dtype): (offsets[len + 1], shapes), ascending by slot per probe."""
+        return self._world_csr(self._L.s2amd_world_point_probe, probes, wire.point_probe_dtype, expected or 4 * len(probes) + 64)
+
+    def world_query_boxes(self, boxes, expected=None):
+        """The shapes whose fat box overlaps each box (wire.box_query_dtype): (offsets[len + 1], shapes), ascending by slot per box."""
+        return self._world_csr(self._L.s2amd_world_query_boxes, boxes, wire.box_query_dtype, expected or 16 * len(boxes) + 64)
 
     # ---- the reports of the resident world: the three shapes their getters have ----
     def _world_list(self, fn, dtype, expected):

@@ -219,3 +219,13 @@ step_metrics_dtype = np.dtype([("step", np.int32), ("flags", np.int32), ("solver
                                ("revoluteJoints", np.int32), ("maxJointGapSlot", np.int32), ("maxJointGapSquared", np.float32), ("sumJointGapSquared", np.float32),
                                ("pad", np.int32, 8)])
 assert step_metrics_dtype.itemsize == 128
+
+# scene queries on the resident world (include/solver2d_amd.h: s2amd_world_ray_cast, s2amd_world_point_probe, s2amd_world_query_boxes)
+# s2amdRay, s2amdRayHit, s2amdPointProbe, s2amdBoxQuery
+ray_dtype = np.dtype([("p1", np.float32, 2), ("p2", np.float32, 2), ("maxFraction", np.float32), ("maskBits", np.uint32)])
+ray_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("fraction", np.float32), ("point", np.float32, 2), ("normal", np.float32, 2),
+                          ("pad", np.int32)])
+point_probe_dtype = np.dtype([("p", np.float32, 2), ("maskBits", np.uint32)])
+box_query_dtype = np.dtype([("box", np.float32, 4), ("maskBits", np.uint32)])
+RAY_SIZE, RAY_HIT_SIZE, POINT_PROBE_SIZE, BOX_QUERY_SIZE = ray_dtype.itemsize, ray_hit_dtype.itemsize, point_probe_dtype.itemsize, box_query_dtype.itemsize
+assert RAY_SIZE == 24 and RAY_HIT_SIZE == 32 and POINT_PROBE_SIZE == 12 and BOX_QUERY_SIZE == 20
