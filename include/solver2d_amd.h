@@ -813,6 +813,57 @@ int s2amd_world_point_probe(s2amdSolver* solver, const s2amdPointProbe* probes, 
 int s2amd_world_query_boxes(s2amdSolver* solver, const s2amdBoxQuery* boxes, int32_t count, int32_t* offsets /* [count + 1] */, int32_t* shapes,
 							int32_t capacity, int32_t* total);
 
+/* (additive, API 5) Proximity queries: "what is near this shape, and how near?" asked of the resident world -- a blast radius, a
+ * spawn-clearance test, a trigger volume that is not a box, a proximity sensor, picking with a tolerance.  The reference answers it with
+ * s2ShapeDistance (include/solver2d/distance.h:71, src/distance.c:485-636) over the proxies of s2Shape_MakeDistanceProxy
+ * (src/shape.c:75-93); the two batched calls below answer from the resident arrays, under the general terms of the scene queries above:
+ * the world as it stands, enqueued behind whatever changed it last on the solver's stream, any number of times between steps, nothing
+ * resident written, no host wait added to a step, no device trees needed, S2AMD_E_STATE without a resident world, count == 0 succeeds
+ * and touches nothing.  LIVE, xf(body) and PASSES are the scene queries' definitions.
+ *   Validation    on the host, for every query before anything is enqueued: 1 <= count <= 8; vertices[0 .. count), radius, position, rot
+ *                 and maxDistance finite; radius >= 0; maxDistance >= 0.  One failing query makes the whole call return S2AMD_E_INVALID
+ *                 with every output untouched.  rot is not checked for normalisation.
+ *   Query box     w_i = s2TransformPoint({position, rot}, vertices[i]) for i < count; lower = w_0 folded with s2Min over w_1, w_2, ... in
+ *                 index order (lower = s2Min(lower, w_i)), upper likewise with s2Max; r = radius + maxDistance (one fp32 add); the box is
+ *                 {lower.x - r, lower.y - r, upper.x + r, upper.y + r}.
+ *   Candidates    live, passing, s2AABB_Overlaps(fatAABB, box).  No other pruning decides a result.
+ *   D(q, s)       s2ShapeDistance with a cache of count == 0, proxyA = s2MakeProxy(q.vertices, q.count, q.radius), proxyB =
+ *                 s2Shape_MakeDistanceProxy(s) -- capsule: 2 points + radius; circle: 1 point + radius; polygon: count vertices (clamped
+ *                 to 8) + radius; segment: 2 points, radius 0 --, transformA = {q.position, q.rot}, transformB = xf(s.body), useRadii =
+ *                 true, the distance < FLT_EPSILON branch of src/distance.c:612-619 included.  D is a whole s2DistanceOutput.
+ *   In range      a candidate s with D.distance <= q.maxDistance, compared as floats.  maxDistance 0 asks what overlaps or touches.
+ *   s2amd_world_shapes_in_range  the in-range shapes of every query, ascending by slot, in the CSR form and with the S2AMD_E_CAPACITY
+ *                 protocol of s2amd_world_point_probe (offsets and *total filled, shapes and distances untouched, the caller asks
+ *                 again).  Where distances != NULL, distances[k] holds the bits of D.distance for shapes[k].
+ *   s2amd_world_closest_shape    the in-range shape of least distance, ties to the lowest slot (distances are >= +0, so their bits order
+ *                 as their values).  The record holds that shape's own D -- distance, pointA (on the query), pointB (on the shape),
+ *                 iterations -- and its body.  Nothing in range: shape = body = -1, distance = maxDistance, points +0, iterations 0.
+ * The composition is ours (the reference has no world-level distance query); every D is the reference's bit for bit.  All arithmetic is
+ * fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in libs2amd.so and in
+ * libs2amd_fast.so alike.  Not offered: sharded worlds, shape casts, a simplex cache kept between calls, queries or answers in device
+ * memory. */
+typedef struct s2amdProximityQuery /* 96 bytes */
+{
+	float vertices[8][2]; /* the query's proxy in its own frame: s2MakeProxy(vertices, count, radius) */
+	int32_t count;		  /* 1..8: 1 = circle / point, 2 = capsule / segment, 3.. = (rounded) polygon */
+	float radius;		  /* >= 0 */
+	float position[2];	  /* transformA.p */
+	float rot[2];		  /* transformA.q {s, c} */
+	float maxDistance;	  /* >= 0, finite: 0 asks "what overlaps or touches" */
+	uint32_t maskBits;
+} s2amdProximityQuery;
+typedef struct s2amdProximityHit /* 32 bytes */
+{
+	int32_t shape, body;
+	float distance;
+	float pointA[2];	/* on the query */
+	float pointB[2];	/* on the shape */
+	int32_t iterations; /* s2DistanceOutput.iterations */
+} s2amdProximityHit;
+int s2amd_world_closest_shape(s2amdSolver* solver, const s2amdProximityQuery* queries, int32_t count, s2amdProximityHit* hits /* [count] */);
+int s2amd_world_shapes_in_range(s2amdSolver* solver, const s2amdProximityQuery* queries, int32_t count, int32_t* offsets /* [count + 1] */,
+								int32_t* shapes, float* distances /* [capacity], may be NULL */, int32_t capacity, int32_t* total);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

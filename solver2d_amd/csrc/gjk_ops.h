@@ -1,7 +1,8 @@
-// GJK of the reference (src/distance.c:120-604) in the one form its callers here use -- identity transforms, no radii -- with the
-// small transform and vector helpers and the LDS polygon it addresses by computed index.  Shared by the narrow phase
+// GJK of the reference (src/distance.c:120-604) in the one form the contact and containment callers use -- identity transforms, no radii
+// -- with the small transform and vector helpers and the LDS polygon it addresses by computed index: shared by the narrow phase
 // (narrowphase.hip: s2CollidePolygons, src/manifold.c:523-530) and the scene queries (scene_query.hip: s2PointInPolygon,
-// src/geometry.c:376-389).  The including file defines S2_NP_BLOCK, the stride of its LDS polygons (its workgroup size), and
+// src/geometry.c:376-389).  Below it the general form (:485-636: both transforms, radii, iteration count) of the proximity queries
+// (proximity_query.hip).  The including file defines S2_NP_BLOCK, the stride of its LDS polygons (its workgroup size), and
 // S2_NP_MAX_VERTS first.  Everything is in an unnamed namespace: each file holds its own copy.
 #pragma once
 
@@ -369,6 +370,269 @@ S2_DEV DistanceOutput shapeDistance(Cache& cache, const PolyRef& A, const PolyRe
 	if (count > 2)
 	{
 		cache.indexA[2] = s2.indexA & 0xff, cache.indexB[2] = s2.indexB & 0xff;
+	}
+	return out;
+}
+
+// ---- s2ShapeDistance in its general form (src/distance.c:485-636): both transforms, the radii epilogue, the iteration count ----
+// The proximity queries' distance (proximity_query.hip).  A proxy is vertices at a stride, wherever they lie -- a staged query read by
+// every lane (stride 1), a lane's LDS column (stride S2_NP_BLOCK), a wire record in global memory (stride 1); the cache is empty
+// (count == 0) and is not returned.  The simplex is three named vertices, as above: indexing them would put them in scratch.
+template <int STRIDE>
+struct ProxyRef
+{
+	const float2* verts;
+	int count;
+	float radius;
+	S2_DEV V2 v(int i) const
+	{
+		float2 t = verts[i * STRIDE];
+		return v2(t.x, t.y);
+	}
+};
+
+template <class P>
+S2_DEV int findSupportOf(const P& p, V2 d) // :116-131
+{
+	int best = 0;
+	float bestValue = dot(p.v(0), d);
+	for (int i = 1; i < p.count; ++i)
+	{
+		float value = dot(p.v(i), d);
+		if (value > bestValue)
+		{
+			best = i;
+			bestValue = value;
+		}
+	}
+	return best;
+}
+
+struct Simplex
+{
+	SVertex v1, v2, v3;
+	int count;
+};
+
+S2_DEV void solveSimplex2(Simplex& s) // :333-365
+{
+	V2 w1 = s.v1.w, w2 = s.v2.w;
+	V2 e12 = sub(w2, w1);
+	float d12_2 = -dot(w1, e12);
+	if (d12_2 <= 0.0f)
+	{
+		s.v1.a = 1.0f;
+		s.count = 1;
+		return;
+	}
+	float d12_1 = dot(w2, e12);
+	if (d12_1 <= 0.0f)
+	{
+		s.v2.a = 1.0f;
+		s.count = 1;
+		s.v1 = s.v2;
+		return;
+	}
+	float inv_d12 = 1.0f / (d12_1 + d12_2);
+	s.v1.a = d12_1 * inv_d12;
+	s.v2.a = d12_2 * inv_d12;
+	s.count = 2;
+}
+
+S2_DEV void solveSimplex3(Simplex& s) // :367-474
+{
+	V2 w1 = s.v1.w, w2 = s.v2.w, w3 = s.v3.w;
+	V2 e12 = sub(w2, w1);
+	float w1e12 = dot(w1, e12), w2e12 = dot(w2, e12);
+	float d12_1 = w2e12, d12_2 = -w1e12;
+	V2 e13 = sub(w3, w1);
+	float w1e13 = dot(w1, e13), w3e13 = dot(w3, e13);
+	float d13_1 = w3e13, d13_2 = -w1e13;
+	V2 e23 = sub(w3, w2);
+	float w2e23 = dot(w2, e23), w3e23 = dot(w3, e23);
+	float d23_1 = w3e23, d23_2 = -w2e23;
+	float n123 = cross(e12, e13);
+	float d123_1 = n123 * cross(w2, w3);
+	float d123_2 = n123 * cross(w3, w1);
+	float d123_3 = n123 * cross(w1, w2);
+	if (d12_2 <= 0.0f && d13_2 <= 0.0f)
+	{
+		s.v1.a = 1.0f;
+		s.count = 1;
+		return;
+	}
+	if (d12_1 > 0.0f && d12_2 > 0.0f && d123_3 <= 0.0f)
+	{
+		float inv_d12 = 1.0f / (d12_1 + d12_2);
+		s.v1.a = d12_1 * inv_d12;
+		s.v2.a = d12_2 * inv_d12;
+		s.count = 2;
+		return;
+	}
+	if (d13_1 > 0.0f && d13_2 > 0.0f && d123_2 <= 0.0f)
+	{
+		float inv_d13 = 1.0f / (d13_1 + d13_2);
+		s.v1.a = d13_1 * inv_d13;
+		s.v3.a = d13_2 * inv_d13;
+		s.count = 2;
+		s.v2 = s.v3;
+		return;
+	}
+	if (d12_1 <= 0.0f && d23_2 <= 0.0f)
+	{
+		s.v2.a = 1.0f;
+		s.count = 1;
+		s.v1 = s.v2;
+		return;
+	}
+	if (d13_1 <= 0.0f && d23_1 <= 0.0f)
+	{
+		s.v3.a = 1.0f;
+		s.count = 1;
+		s.v1 = s.v3;
+		return;
+	}
+	if (d23_1 > 0.0f && d23_2 > 0.0f && d123_1 <= 0.0f)
+	{
+		float inv_d23 = 1.0f / (d23_1 + d23_2);
+		s.v2.a = d23_1 * inv_d23;
+		s.v3.a = d23_2 * inv_d23;
+		s.count = 2;
+		s.v1 = s.v3;
+		return;
+	}
+	float inv_d123 = 1.0f / (d123_1 + d123_2 + d123_3);
+	s.v1.a = d123_1 * inv_d123;
+	s.v2.a = d123_2 * inv_d123;
+	s.v3.a = d123_3 * inv_d123;
+	s.count = 3;
+}
+
+struct ShapeDistanceOutput // s2DistanceOutput, include/solver2d/distance.h:60-66
+{
+	V2 pointA, pointB;
+	float distance;
+	int iterations;
+};
+
+// s2ShapeDistance(&emptyCache, {proxyA, proxyB, transformA, transformB, useRadii = true})
+template <class PA, class PB>
+S2_DEV ShapeDistanceOutput shapeDistanceWithRadii(const PA& A, Xf xfA, const PB& B, Xf xfB)
+{
+	Simplex s;
+	s.v2.a = s.v3.a = 0.0f; // (never read before a solve sets them; the reference leaves them unset)
+	s.v2.indexA = s.v2.indexB = s.v3.indexA = s.v3.indexB = 0;
+	s.v2.wA = s.v2.wB = s.v2.w = s.v3.wA = s.v3.wB = s.v3.w = v2(0.0f, 0.0f);
+	// s2MakeSimplexFromCache with an empty cache :198-210
+	s.v1.indexA = 0;
+	s.v1.indexB = 0;
+	s.v1.wA = xfPoint(xfA, A.v(0));
+	s.v1.wB = xfPoint(xfB, B.v(0));
+	s.v1.w = sub(s.v1.wB, s.v1.wA);
+	s.v1.a = 1.0f;
+	s.count = 1;
+
+	int saveA0 = 0, saveB0 = 0, saveA1 = 0, saveB1 = 0, saveA2 = 0, saveB2 = 0;
+	int iter = 0;
+	while (iter < 20)
+	{
+		const int saveCount = s.count;
+		saveA0 = s.v1.indexA, saveB0 = s.v1.indexB;
+		saveA1 = s.v2.indexA, saveB1 = s.v2.indexB;
+		saveA2 = s.v3.indexA, saveB2 = s.v3.indexB;
+		if (s.count == 2)
+		{
+			solveSimplex2(s);
+		}
+		else if (s.count == 3)
+		{
+			solveSimplex3(s);
+		}
+		if (s.count == 3)
+		{
+			break;
+		}
+		// s2ComputeSimplexSearchDirection :227-254
+		V2 d;
+		if (s.count == 1)
+		{
+			d = neg(s.v1.w);
+		}
+		else
+		{
+			V2 e12 = sub(s.v2.w, s.v1.w);
+			float sgn = cross(e12, neg(s.v1.w));
+			d = sgn > 0.0f ? crossSV(1.0f, e12) : crossVS(e12, 1.0f);
+		}
+		if (dot(d, d) < FLT_EPSILON * FLT_EPSILON)
+		{
+			break;
+		}
+		// :562-567: the new vertex's w*, index* are set, its barycentric coordinate stays what the slot held
+		SVertex nv;
+		nv.a = s.count == 1 ? s.v2.a : s.v3.a;
+		nv.indexA = findSupportOf(A, invRotate(xfA.q, neg(d)));
+		nv.wA = xfPoint(xfA, A.v(nv.indexA));
+		nv.indexB = findSupportOf(B, invRotate(xfB.q, d));
+		nv.wB = xfPoint(xfB, B.v(nv.indexB));
+		nv.w = sub(nv.wB, nv.wA);
+		if (s.count == 1)
+		{
+			s.v2 = nv;
+		}
+		else
+		{
+			s.v3 = nv;
+		}
+		++iter;
+		bool duplicate = nv.indexA == saveA0 && nv.indexB == saveB0; // (saveCount >= 1)
+		duplicate = duplicate || (saveCount > 1 && nv.indexA == saveA1 && nv.indexB == saveB1);
+		duplicate = duplicate || (saveCount > 2 && nv.indexA == saveA2 && nv.indexB == saveB2);
+		if (duplicate)
+		{
+			break;
+		}
+		++s.count;
+	}
+
+	// s2ComputeSimplexWitnessPoints :279-308
+	ShapeDistanceOutput out;
+	if (s.count == 1)
+	{
+		out.pointA = s.v1.wA;
+		out.pointB = s.v1.wB;
+	}
+	else if (s.count == 2)
+	{
+		out.pointA = weight2(s.v1.a, s.v1.wA, s.v2.a, s.v2.wA);
+		out.pointB = weight2(s.v1.a, s.v1.wB, s.v2.a, s.v2.wB);
+	}
+	else
+	{
+		out.pointA = weight3(s.v1.a, s.v1.wA, s.v2.a, s.v2.wA, s.v3.a, s.v3.wA);
+		out.pointB = out.pointA;
+	}
+	out.distance = distance2(out.pointA, out.pointB);
+	out.iterations = iter;
+
+	// the radii :610-633
+	if (out.distance < FLT_EPSILON)
+	{
+		V2 p = v2(0.5f * (out.pointA.x + out.pointB.x), 0.5f * (out.pointA.y + out.pointB.y));
+		out.pointA = p;
+		out.pointB = p;
+		out.distance = 0.0f;
+	}
+	else
+	{
+		float rA = A.radius, rB = B.radius;
+		float reduced = out.distance - rA - rB;
+		out.distance = S2_MAXF(0.0f, reduced);
+		V2 normal = normalize(sub(out.pointB, out.pointA));
+		V2 offsetA = v2(rA * normal.x, rA * normal.y);
+		V2 offsetB = v2(rB * normal.x, rB * normal.y);
+		out.pointA = add(out.pointA, offsetA);
+		out.pointB = sub(out.pointB, offsetB);
 	}
 	return out;
 }

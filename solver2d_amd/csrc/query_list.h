@@ -1,0 +1,155 @@
+// What the list-valued queries on the resident world share (scene_query.hip: point probes and box queries; proximity_query.hip: shapes
+// in range): the candidate rule's box test, the second half of the ballot-mask -> tile-prefix -> offsets -> write sequence that turns
+// per-wave hit masks into CSR lists ascending by slot, and the host-side checks every query call opens with.  The first half -- the mask
+// kernel -- is each file's own.  Everything is in an unnamed namespace: each file holds its own copy of the kernels under the same names.
+//
+//   masks[((query * tiles) + tile) * 4 + wave]   the wave's hits of the query, bit = lane; every word is written by the mask kernel
+//   listTilePrefixKernel  one wave per query: the exclusive prefix of the tiles' hit counts, and the query's total.
+//   listOffsetsKernel     one wave: the CSR offsets over the queries.
+//   listWriteKernel       one lane per ballot word: its set bits are consecutive entries of the query's list, at
+//                         offsets[query] + hits of the tiles before + hits of the tile's waves before: ascending by slot, no sort, no atomic.
+#pragma once
+
+#include "report_common.h"
+
+namespace
+{
+
+#define S2_QUERY_CHUNK S2_BLOCK // queries a workgroup stages: one per lane
+#define S2_QUERY_MAX_COUNT (65535 * S2_QUERY_CHUNK)
+
+// s2AABB_Overlaps(fat, box), include/solver2d/aabb.h:111-123: false only when one of the four differences is > 0
+S2_DEV bool boxesOverlap(const float* fat, float lx, float ly, float ux, float uy)
+{
+	const float d1x = lx - fat[2], d1y = ly - fat[3];
+	const float d2x = fat[0] - ux, d2y = fat[1] - uy;
+	if (d1x > 0.0f || d1y > 0.0f)
+	{
+		return false;
+	}
+	if (d2x > 0.0f || d2y > 0.0f)
+	{
+		return false;
+	}
+	return true;
+}
+
+S2_DEV int tileHits(const unsigned long long* masks, size_t tileWord)
+{
+	const ulonglong2 a = *(const ulonglong2*)(masks + tileWord), b = *(const ulonglong2*)(masks + tileWord + 2);
+	return __popcll(a.x) + __popcll(a.y) + __popcll(b.x) + __popcll(b.y);
+}
+
+// inclusive sum over the wave's lanes
+S2_DEV int waveInclusive(int v, int lane)
+{
+	for (int d = 1; d < 64; d <<= 1)
+	{
+		const int other = __shfl_up(v, d);
+		if (lane >= d)
+		{
+			v += other;
+		}
+	}
+	return v;
+}
+
+// tilePrefix[query * tiles + tile] = hits of the query in the tiles before; totals[query]
+__global__ __launch_bounds__(S2_BLOCK) void listTilePrefixKernel(const unsigned long long* masks, int count, int tiles, int* tilePrefix, int* totals)
+{
+	const int lane = (int)(threadIdx.x & 63);
+	const int q = (int)(blockIdx.x * (S2_BLOCK / 64) + (threadIdx.x >> 6));
+	if (q >= count) // (whole waves)
+	{
+		return;
+	}
+	int carry = 0;
+	for (int base = 0; base < tiles; base += 64)
+	{
+		const int t = base + lane;
+		const int c = t < tiles ? tileHits(masks, ((size_t)q * tiles + t) * 4) : 0;
+		const int inclusive = waveInclusive(c, lane);
+		if (t < tiles)
+		{
+			tilePrefix[(size_t)q * tiles + t] = carry + inclusive - c;
+		}
+		carry += __shfl(inclusive, 63);
+	}
+	if (lane == 0)
+	{
+		totals[q] = carry;
+	}
+}
+
+// offsets[0 .. count]: one wave
+__global__ __launch_bounds__(64) void listOffsetsKernel(const int* totals, int count, int* offsets)
+{
+	const int lane = (int)threadIdx.x;
+	int carry = 0;
+	for (int base = 0; base < count; base += 64)
+	{
+		const int q = base + lane;
+		const int c = q < count ? totals[q] : 0;
+		const int inclusive = waveInclusive(c, lane);
+		if (q < count)
+		{
+			offsets[q] = carry + inclusive - c;
+		}
+		carry += __shfl(inclusive, 63);
+	}
+	if (lane == 0)
+	{
+		offsets[count] = carry;
+	}
+}
+
+// out[0 .. capacity): entries beyond the caller's capacity are dropped (the call answers S2AMD_E_CAPACITY from the offsets)
+__global__ __launch_bounds__(S2_BLOCK) void listWriteKernel(const unsigned long long* masks, size_t words, int tiles, const int* tilePrefix, const int* offsets, int32_t* out,
+															 int capacity)
+{
+	const size_t w = (size_t)blockIdx.x * S2_BLOCK + threadIdx.x;
+	if (w >= words)
+	{
+		return;
+	}
+	unsigned long long m = masks[w];
+	if (m == 0ull)
+	{
+		return;
+	}
+	const int wave = (int)(w & 3);
+	const size_t qt = w >> 2;
+	const int q = (int)(qt / (size_t)tiles), tile = (int)(qt % (size_t)tiles);
+	int at = offsets[q] + tilePrefix[qt];
+	for (int v = 0; v < wave; ++v)
+	{
+		at += __popcll(masks[w - wave + v]);
+	}
+	const int base = tile * S2_BLOCK + wave * 64;
+	while (m != 0ull)
+	{
+		const int bit = __ffsll((long long)m) - 1;
+		m &= m - 1ull;
+		if (at < capacity)
+		{
+			out[at] = base + bit;
+		}
+		at += 1;
+	}
+}
+
+inline size_t roundUp(size_t bytes)
+{
+	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
+}
+
+inline int queryState(const s2amdSolver* s)
+{
+	if (!s->worldResident || !s->resident)
+	{
+		return fail(S2AMD_E_STATE, "no resident world");
+	}
+	return S2AMD_OK;
+}
+
+} // namespace

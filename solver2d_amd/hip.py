@@ -32,6 +32,7 @@ EXPORTS = [
     "s2amd_world_body_summary",
     "s2amd_world_set_metrics", "s2amd_world_metrics", "s2amd_world_metrics_history",
     "s2amd_world_ray_cast", "s2amd_world_point_probe", "s2amd_world_query_boxes",
+    "s2amd_world_closest_shape", "s2amd_world_shapes_in_range",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -125,6 +126,8 @@ def load(fast=False):
     L.s2amd_world_ray_cast.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_point_probe.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_query_boxes.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_closest_shape.argtypes = [vp, vp, i32, vp]
+    L.s2amd_world_shapes_in_range.argtypes = [vp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -465,6 +468,37 @@ class Solver:
     def world_query_boxes(self, boxes, expected=None):
         """The shapes whose fat box overlaps each box (wire.box_query_dtype): (offsets[len + 1], shapes), ascending by slot per box."""
         return self._world_csr(self._L.s2amd_world_query_boxes, boxes, wire.box_query_dtype, expected or 16 * len(boxes) + 64)
+
+    # ---- proximity queries on the resident world: s2ShapeDistance between a caller's proxy and the shapes near it ----
+    def world_closest_shape(self, queries):
+        """The in-range shape of least distance for every query (wire.proximity_query_dtype) -> wire.proximity_hit_dtype[len(queries)];
+        shape == -1: nothing within maxDistance."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.dtype == wire.proximity_query_dtype
+        hits = np.zeros(len(queries), dtype=wire.proximity_hit_dtype)
+        self._ck(self._L.s2amd_world_closest_shape(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(hits)))
+        return hits
+
+    def world_shapes_in_range(self, queries, distances=False, expected=None):
+        """The shapes within maxDistance of each query: (offsets[len + 1], shapes), ascending by slot per query; with distances=True
+        (offsets, shapes, distances).  Asked again with the total the library states when it answers S2AMD_E_CAPACITY."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.dtype == wire.proximity_query_dtype
+        offsets = np.zeros(len(queries) + 1, dtype=np.int32)
+        cap = max(int(expected or 8 * len(queries) + 64), 1)
+        while True:
+            shapes = np.zeros(cap, dtype=np.int32)
+            dist = np.zeros(cap, dtype=np.float32) if distances else None
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_shapes_in_range(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(shapes),
+                                                     wire.as_ptr(dist) if distances else None, cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
+                cap = n.value
+                continue
+            self._ck(rc)
+            if distances:
+                return offsets, shapes[: n.value].copy(), dist[: n.value].copy()
+            return offsets, shapes[: n.value].copy()
 
     # ---- the reports of the resident world: the three shapes their getters have ----
     def _world_list(self, fn, dtype, expected):

@@ -229,3 +229,12 @@ point_probe_dtype = np.dtype([("p", np.float32, 2), ("maskBits", np.uint32)])
 box_query_dtype = np.dtype([("box", np.float32, 4), ("maskBits", np.uint32)])
 RAY_SIZE, RAY_HIT_SIZE, POINT_PROBE_SIZE, BOX_QUERY_SIZE = ray_dtype.itemsize, ray_hit_dtype.itemsize, point_probe_dtype.itemsize, box_query_dtype.itemsize
 assert RAY_SIZE == 24 and RAY_HIT_SIZE == 32 and POINT_PROBE_SIZE == 12 and BOX_QUERY_SIZE == 20
+
+# proximity queries on the resident world (include/solver2d_amd.h: s2amd_world_closest_shape, s2amd_world_shapes_in_range)
+# s2amdProximityQuery, s2amdProximityHit
+proximity_query_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("count", np.int32), ("radius", np.float32), ("position", np.float32, 2),
+                                  ("rot", np.float32, 2), ("maxDistance", np.float32), ("maskBits", np.uint32)])
+proximity_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("distance", np.float32), ("pointA", np.float32, 2),
+                                ("pointB", np.float32, 2), ("iterations", np.int32)])
+PROXIMITY_QUERY_SIZE, PROXIMITY_HIT_SIZE = proximity_query_dtype.itemsize, proximity_hit_dtype.itemsize
+assert PROXIMITY_QUERY_SIZE == 96 and PROXIMITY_HIT_SIZE == 32
