@@ -864,6 +864,72 @@ int s2amd_world_closest_shape(s2amdSolver* solver, const s2amdProximityQuery* qu
 int s2amd_world_shapes_in_range(s2amdSolver* solver, const s2amdProximityQuery* queries, int32_t count, int32_t* offsets /* [count + 1] */,
 								int32_t* shapes, float* distances /* [capacity], may be NULL */, int32_t capacity, int32_t* total);
 
+/* (additive, API 5) Contact queries: "if this shape stood here, what would it touch, where, and how deep?" asked of the resident world
+ * -- a character controller, a ghost or trigger shape, spawn placement with push-out, a "will this fit" test.  The reference answers it
+ * with its nine manifold functions s2Collide* (include/solver2d/manifold.h:56-85), dispatched by s_registers (src/contact.c:139-151);
+ * the two batched calls below answer from the resident arrays, under the general terms of the scene queries above: the world as it
+ * stands, enqueued behind whatever changed it last on the solver's stream, any number of times between steps, nothing resident written,
+ * no host wait added to a step, no device trees needed, S2AMD_E_STATE without a resident world, count == 0 succeeds and touches nothing.
+ * LIVE, xf(body) and PASSES are the scene queries' definitions.
+ *   Validation    on the host, for every query before anything is enqueued: type is one of the four; a polygon has 3 <= count <= 8; the
+ *                 vertices the type reads (circle 1, capsule and segment 2, polygon count) are finite, and for a polygon so are
+ *                 normals[0 .. count); position and rot are finite; radius is finite and >= 0 where the type reads it (not for a
+ *                 segment).  One failing query makes the whole call return S2AMD_E_INVALID with every output untouched.  rot is not
+ *                 checked for normalisation, the normals not for length.
+ *   Query box     what stage 4 would store in shape->aabb for this shape at the transform {position, rot}: s2Shape_ComputeAABB
+ *                 (src/geometry.c:288-339) per type, grown by s2_speculativeDistance on every side (src/world.c:286-290).
+ *   Candidates    live, passing, s2AABB_Overlaps(fatAABB, query box), and a type pair that has a manifold function: segment against
+ *                 segment has none.  No other pruning decides a result.  (A slot whose type is none of the four, or a polygon slot
+ *                 with count > 8 -- no s2Polygon holds one -- is never a candidate.)
+ *   Order         the manifold's shape A is the query when s_registers[q.type][s.type].primary is true: for equal types and when the
+ *                 query's type is the pair's first at src/contact.c:143-151 (capsule-circle, polygon-circle, polygon-capsule,
+ *                 segment-circle, segment-capsule, segment-polygon).  Otherwise shape A is the world shape, as s2CreateContact flips it,
+ *                 and queryIsB = 1.  The query's transform is {position, rot}, the world shape's xf(body).
+ *   M(q, s)       the pair's s2Collide* with a distance cache of count == 0 where the function takes one: what a contact created this
+ *                 step gets from its first s2UpdateContact.  Capsules and segments go through s2MakeCapsule as src/manifold.c sends
+ *                 them; a segment's radius is 0.
+ *   Hit           a candidate with M.pointCount > 0.  Speculative points (separation > 0) are included as in the reference: the caller
+ *                 reads `separation`.  The record is M: normal (from A to B, world space), per point localAnchorA (the contact point in
+ *                 A's frame), localAnchorB (the same point in B's frame), separation and id, as the s2Collide* function leaves them.
+ *   s2amd_world_collide_shape    the hits of every query, ascending by slot, in the CSR form and with the S2AMD_E_CAPACITY protocol of
+ *                 s2amd_world_point_probe: with capacity < *total, offsets and *total are filled, hits is untouched, the caller asks
+ *                 again.
+ *   s2amd_world_deepest_contact  per query the hit whose least point separation (over its pointCount points) is smallest, compared as
+ *                 float values (-0 equals +0), ties to the lowest slot; the record is that hit's own.  No hit: shape = body = -1 and
+ *                 every other field zero.
+ * The composition is ours (the reference has no world-level manifold query); every M is the reference's bit for bit.  All arithmetic is
+ * fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in libs2amd.so and in
+ * libs2amd_fast.so alike.  Not offered: sharded worlds, shape casts, a simplex cache kept between calls, queries or answers in device
+ * memory, the drop-in's contacts routed through these calls, the device trees as an accelerator. */
+typedef struct s2amdContactQuery /* 160 bytes */
+{
+	float vertices[8][2]; /* geometry as s2amdShape holds it: circle = vertices[0]; capsule / segment = vertices[0..1]; polygon = [0..count) */
+	float normals[8][2];  /* polygon edge normals as the caller's s2Polygon has them; not recomputed, not checked for length */
+	int32_t type;		  /* S2AMD_SHAPE_CAPSULE / _CIRCLE / _POLYGON / _SEGMENT */
+	int32_t count;		  /* polygon: 3..8; ignored otherwise */
+	float radius;		  /* circle, capsule, rounded polygon; ignored for a segment */
+	float position[2];	  /* the query's transform: p (the "body origin" its anchors are relative to) */
+	float rot[2];		  /* q {s, c}; not checked for normalisation */
+	uint32_t maskBits;
+} s2amdContactQuery;
+typedef struct s2amdContactHit /* 80 bytes */
+{
+	int32_t shape, body; /* the world shape and its body */
+	int32_t pointCount;	 /* 1 or 2 in a hit */
+	int32_t queryIsB;	 /* 0: the manifold's shape A is the query; 1: shape A is the world shape (see "Order") */
+	float normal[2];	 /* s2Manifold.normal: from A to B */
+	struct
+	{
+		float localAnchorA[2], localAnchorB[2];
+		float separation;
+		uint32_t id;
+	} points[2];		 /* a point >= pointCount is all zero bits */
+	int32_t pad[2];		 /* 0 */
+} s2amdContactHit;
+int s2amd_world_collide_shape(s2amdSolver* solver, const s2amdContactQuery* queries, int32_t count, int32_t* offsets /* [count + 1] */,
+							  s2amdContactHit* hits, int32_t capacity, int32_t* total);
+int s2amd_world_deepest_contact(s2amdSolver* solver, const s2amdContactQuery* queries, int32_t count, s2amdContactHit* hits /* [count] */);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

@@ -33,6 +33,7 @@ EXPORTS = [
     "s2amd_world_set_metrics", "s2amd_world_metrics", "s2amd_world_metrics_history",
     "s2amd_world_ray_cast", "s2amd_world_point_probe", "s2amd_world_query_boxes",
     "s2amd_world_closest_shape", "s2amd_world_shapes_in_range",
+    "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -128,6 +129,8 @@ def load(fast=False):
     L.s2amd_world_query_boxes.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_closest_shape.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_shapes_in_range.argtypes = [vp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_collide_shape.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_deepest_contact.argtypes = [vp, vp, i32, vp]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -499,6 +502,34 @@ class Solver:
             if distances:
                 return offsets, shapes[: n.value].copy(), dist[: n.value].copy()
             return offsets, shapes[: n.value].copy()
+
+    # ---- contact queries on the resident world: the reference's manifolds between a caller's shape and the shapes near it ----
+    def world_deepest_contact(self, queries):
+        """The hit of least separation for every query (wire.contact_query_dtype) -> wire.contact_hit_dtype[len(queries)];
+        shape == -1: the query touches nothing."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.dtype == wire.contact_query_dtype
+        hits = np.zeros(len(queries), dtype=wire.contact_hit_dtype)
+        self._ck(self._L.s2amd_world_deepest_contact(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(hits)))
+        return hits
+
+    def world_collide_shape(self, queries, expected=None):
+        """The manifolds of each query against the shapes it touches: (offsets[len + 1], hits), ascending by slot per query.  Asked again
+        with the total the library states when it answers S2AMD_E_CAPACITY."""
+        queries = np.ascontiguousarray(queries)
+        assert queries.dtype == wire.contact_query_dtype
+        offsets = np.zeros(len(queries) + 1, dtype=np.int32)
+        cap = max(int(expected or 4 * len(queries) + 64), 1)
+        while True:
+            hits = np.zeros(cap, dtype=wire.contact_hit_dtype)
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_collide_shape(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(hits), cap,
+                                                   ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
+                cap = n.value
+                continue
+            self._ck(rc)
+            return offsets, hits[: n.value].copy()
 
     # ---- the reports of the resident world: the three shapes their getters have ----
     def _world_list(self, fn, dtype, expected):

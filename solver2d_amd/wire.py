@@ -238,3 +238,13 @@ proximity_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("dista
                                 ("pointB", np.float32, 2), ("iterations", np.int32)])
 PROXIMITY_QUERY_SIZE, PROXIMITY_HIT_SIZE = proximity_query_dtype.itemsize, proximity_hit_dtype.itemsize
 assert PROXIMITY_QUERY_SIZE == 96 and PROXIMITY_HIT_SIZE == 32
+
+# contact queries on the resident world (include/solver2d_amd.h: s2amd_world_collide_shape, s2amd_world_deepest_contact)
+# s2amdContactQuery, s2amdContactHit
+contact_query_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("normals", np.float32, (8, 2)), ("type", np.int32), ("count", np.int32),
+                                ("radius", np.float32), ("position", np.float32, 2), ("rot", np.float32, 2), ("maskBits", np.uint32)])
+contact_hit_point_dtype = np.dtype([("localAnchorA", np.float32, 2), ("localAnchorB", np.float32, 2), ("separation", np.float32), ("id", np.uint32)])
+contact_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("pointCount", np.int32), ("queryIsB", np.int32), ("normal", np.float32, 2),
+                              ("points", contact_hit_point_dtype, 2), ("pad", np.int32, 2)])
+CONTACT_QUERY_SIZE, CONTACT_HIT_SIZE = contact_query_dtype.itemsize, contact_hit_dtype.itemsize
+assert CONTACT_QUERY_SIZE == 160 and CONTACT_HIT_SIZE == 80
