@@ -930,6 +930,58 @@ int s2amd_world_collide_shape(s2amdSolver* solver, const s2amdContactQuery* quer
 							  s2amdContactHit* hits, int32_t capacity, int32_t* total);
 int s2amd_world_deepest_contact(s2amdSolver* solver, const s2amdContactQuery* queries, int32_t count, s2amdContactHit* hits /* [count] */);
 
+/* (additive, API 5) World edits: the reference's eight cheap setters an interactive program calls every frame -- a body dragged by the
+ * mouse joint, a motor whose speed follows a controller, wind, a thrown ball, an explosion -- applied to the resident world where it
+ * lies.  Nothing is downloaded, nothing uploaded again and the constraint-graph structure is kept: no colouring, strip table or tree
+ * depends on a field an edit writes.
+ *   Result        the resident `bodies` and `joints` after the call are what applying edits[0], edits[1], ... one after another to the
+ *                 wire records gives, each as the reference's function of the same name does it (the lines are beside the kinds):
+ *                   SET_LINEAR_VELOCITY    linearVelocity = {v[0], v[1]}
+ *                   SET_ANGULAR_VELOCITY   angularVelocity = v[0]
+ *                   APPLY_FORCE_TO_CENTER  force = s2Add(force, {v[0], v[1]})
+ *                   APPLY_LINEAR_IMPULSE   on a body of type S2AMD_BODY_DYNAMIC only (any other live type: nothing, the reference's early
+ *                                          return): linearVelocity = s2MulAdd(linearVelocity, invMass, impulse); angularVelocity +=
+ *                                          invI * s2Cross(s2Sub(point, position), impulse), impulse = {v[0], v[1]}, point = {v[2], v[3]}
+ *                   MOUSE_SET_TARGET       targetA = {v[0], v[1]}
+ *                   REVOLUTE_ENABLE_LIMIT  enableLimit = (flag != 0);  REVOLUTE_ENABLE_MOTOR  enableMotor = (flag != 0)
+ *                   REVOLUTE_SET_MOTOR_SPEED  motorSpeed = v[0]
+ *                 fp32 in the reference's operation order without contraction, in libs2amd.so and in libs2amd_fast.so alike.  Kinds 1-3
+ *                 write whatever the body's type is, as the reference does.  Every other array of the world -- contacts, shapes, pairs,
+ *                 origins, trees, the reports' state -- is untouched byte for byte.  An edit reads and writes its own target's record
+ *                 only: edits on different targets commute, and only the order of the edits on one target matters (to the bit: force
+ *                 adds and impulse adds are float sums).
+ *   Targets       `target` is a body slot for kinds 1-4 and a joint slot for kinds 5-8.
+ *   Validation    on the host, for every edit before anything is applied: a kind outside 1..8, a target outside the uploaded capacity,
+ *                 reserved != 0, a NULL list with count > 0 or a negative count return S2AMD_E_INVALID and the world is unchanged -- by
+ *                 valid entries earlier in the list too.  S2AMD_E_STATE without a resident world (no s2amd_world_upload, or the solver
+ *                 has left the world chain).  count == 0 succeeds and does nothing.  Float values are not checked: their bits pass through.
+ *   Skipped       only the device knows a slot's type: an edit whose target is a free body slot, a free joint slot or a joint of the
+ *                 other type (a mouse edit on a revolute joint, a revolute edit on a mouse joint) writes nothing and is counted in
+ *                 *skipped.  An APPLY_LINEAR_IMPULSE on a static or kinematic body writes nothing and is NOT counted.
+ *   Ordering      the edits are enqueued on the stream s2amd_world_step uses: they land after the step before and before the step after.
+ *                 With skipped == NULL the call only enqueues and reads nothing back; with a pointer it reads back one int.  The caller
+ *                 may reuse `edits` as soon as the call returns.  Forces are consumed by the next step's stage 4, as the reference's are.
+ * Not offered: s2Body_SetTransform (the reference declares it and never defines it; it would also move boxes and trees); mass, type or
+ * damping edits; creating or destroying anything; sharded worlds; edit lists in device memory; the drop-in's setters routed through
+ * this call. */
+#define S2AMD_EDIT_BODY_SET_LINEAR_VELOCITY 1	/* v[0..1]                      src/body.c:337-342 */
+#define S2AMD_EDIT_BODY_SET_ANGULAR_VELOCITY 2	/* v[0]                         src/body.c:344-350 */
+#define S2AMD_EDIT_BODY_APPLY_FORCE_TO_CENTER 3 /* v[0..1] added to force       src/body.c:352-357 */
+#define S2AMD_EDIT_BODY_APPLY_LINEAR_IMPULSE 4	/* v[0..1] impulse, v[2..3] world point; dynamic bodies only, src/body.c:359-370 */
+#define S2AMD_EDIT_MOUSE_SET_TARGET 5			/* v[0..1]                      src/mouse_joint.c:18-29 */
+#define S2AMD_EDIT_REVOLUTE_ENABLE_LIMIT 6		/* flag                         src/revolute_joint.c:890-901 */
+#define S2AMD_EDIT_REVOLUTE_ENABLE_MOTOR 7		/* flag                         src/revolute_joint.c:903-914 */
+#define S2AMD_EDIT_REVOLUTE_SET_MOTOR_SPEED 8	/* v[0]                         src/revolute_joint.c:916-927 */
+typedef struct s2amdWorldEdit /* 32 bytes */
+{
+	int32_t kind;	  /* S2AMD_EDIT_* */
+	int32_t target;	  /* body slot (kinds 1-4) or joint slot (kinds 5-8) */
+	int32_t flag;	  /* kinds 6, 7: stored as flag != 0 */
+	int32_t reserved; /* 0 */
+	float v[4];
+} s2amdWorldEdit;
+int s2amd_world_edit(s2amdSolver* solver, const s2amdWorldEdit* edits, int32_t count, int32_t* skipped /* may be NULL */);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

@@ -276,7 +276,7 @@ void s2amd_destroy(s2amdSolver* s)
 					  &s->dJointTail.buf, &s->dMsg,			  &s->dStripA.buf,	 &s->dStripB.buf,	 &s->dStripLean,	&s->dPersist,
 					  &s->dGranules,	&s->dOverflowBodies, &s->dPairLog, &s->dPersistOps, &s->dJacobi, &s->dJacobiGran,	  &s->dShapes,		 &s->dPairs,		 &s->dOrigins,		&s->dStatus,
 					  &s->dPointBytes,	&s->dWorldSummary, &s->dJointedKeys,	 &s->dContactStage, &s->dPairScratch,	  &s->dPairKeys,		 &s->dPatches,		 &s->dScanTmp,		 &s->dResident.buf,	 &s->dResidentDesc, &s->dResidentOps, &s->dWatched, &s->dRefitOrder, &s->dStepBack,
-					  &s->dSlotBytes,	  &s->dJointAdjRange, &s->dJointAdjList, &s->dShapeBoxes, &s->dMetricsRing, &s->dQuery};
+					  &s->dSlotBytes,	  &s->dJointAdjRange, &s->dJointAdjList, &s->dShapeBoxes, &s->dMetricsRing, &s->dQuery, &s->dEdit};
 	for (DevBuf* b : bufs)
 	{
 		b->release();
@@ -298,6 +298,14 @@ void s2amd_destroy(s2amdSolver* s)
 	if (s->hostStepBack)
 	{
 		(void)hipHostFree(s->hostStepBack);
+	}
+	if (s->hostEditStage)
+	{
+		(void)hipHostFree(s->hostEditStage);
+	}
+	if (s->evEditStaged)
+	{
+		(void)hipEventDestroy(s->evEditStaged);
 	}
 	if (s->hostPairLog)
 	{

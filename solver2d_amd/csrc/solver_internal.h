@@ -535,6 +535,12 @@ struct SolverRest
 	DevBuf dShapeBoxes;		// world chain: s2amd_world_download_boxes' staging
 	DevBuf dQuery;			// scene queries (scene_query.hip): the queries, the passes' scratch and the results of one call; grows on demand, kept between calls
 	std::vector<int32_t> hQueryStage; // ... where the list calls' {offsets, entries} land before they are split into the caller's two arrays
+	DevBuf dEdit;					  // world edits (world_edit.hip): the skip count, the staged list, the sort's keys and scratch of one call; grows on demand, kept between calls
+	char* hostEditStage = nullptr;	  // ... the pinned copy of the caller's list the device copy reads, and the event of that copy (the next call waits for it before it overwrites the stage)
+	size_t hostEditStageBytes = 0;
+	hipEvent_t evEditStaged = nullptr;
+	std::vector<uint32_t> hEditBodyStamp, hEditJointStamp; // ... the last call (editGeneration) that edited a body / joint slot: how a call notices a target that occurs twice
+	uint32_t editGeneration = 0;
 	DevBuf dRefitOrder, dStepBack; // s2amd_world_set_refit_order; staging of s2amd_world_download_step {count, moved boxes} and the poses
 	int refitOrderCount = 0;
 	int optTreeStream = 1;		  // "tree_stream": the device trees' rebuild on a stream of its own beside stage 3 and the solve (0: on the step's stream; tree_mirror.hip)

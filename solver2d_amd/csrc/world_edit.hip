@@ -1,0 +1,456 @@
+// World edits on the resident world (include/solver2d_amd.h: s2amd_world_edit): the reference's eight per-frame setters --
+// s2Body_SetLinearVelocity, _SetAngularVelocity, _ApplyForceToCenter, _ApplyLinearImpulse (src/body.c:337-370), s2MouseJoint_SetTarget
+// (src/mouse_joint.c:18-29), s2RevoluteJoint_EnableLimit, _EnableMotor, _SetMotorSpeed (src/revolute_joint.c:890-927) -- as writes into
+// the wire records the device owns between steps.  Nothing is downloaded, nothing is marked stale, the structure is kept: an edit
+// changes no field a colouring, a strip table or a tree was made from.  Everything is enqueued on the solver's stream, so a call lands
+// after the step before it and before the step after it.
+//
+// The statement (the header) is sequential: edits[0], edits[1], ... one after another.  An edit reads and writes its own target's
+// record only, so only the order of the edits ON ONE TARGET matters -- to the bit, because force adds and impulse adds are float sums.
+// The host's validation pass looks at every record anyway; it also stamps every target (one word per body slot and per joint slot,
+// a generation counter instead of a clear) and so knows whether any target occurs twice.
+//
+//   all targets distinct   editDistinctKernel: one lane per edit.  The lane reads its record's type word and the fields its kind reads,
+//                          and writes the fields of its kind.
+//   a target twice         editKeysKernel writes key = (joint ? 1 : 0) << 63 | target << 32 | list index; rocPRIM's radix sort orders the
+//                          keys (they are unique, so the result does not depend on the sort's internals); editWalkKernel: one lane per
+//                          sorted key, the first lane of a target's segment walks the segment -- its edits in list order -- with the
+//                          record's edited fields in registers, and writes them once.  A list that puts thousands of edits on one body is
+//                          walked by one lane: correct, not fast.
+//
+// The skip count (a free slot, a joint of the other type): a wave ballot (distinct) or a wave sum (walk), then one integer atomic per
+// wave that has any.  No float atomics.  The arithmetic is fp32 in the reference's operation order; this file is compiled without
+// contraction in both libraries (Makefile), because the result is stated bit for bit.
+#include "solver_internal.h"
+
+#include "report_common.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <cstring>
+
+namespace
+{
+
+static_assert(sizeof(s2amdWorldEdit) == 32, "the edit record");
+static_assert(sizeof(s2amdBody) == 88 && sizeof(s2amdJoint) == 92, "the wire records");
+
+#define S2_EDIT_FIRST_JOINT_KIND S2AMD_EDIT_MOUSE_SET_TARGET
+#define S2_EDIT_LAST_KIND S2AMD_EDIT_REVOLUTE_SET_MOTOR_SPEED
+
+// which fields of a record an edit (or a walk) has written
+#define S2_EDIT_W_LINEAR 1
+#define S2_EDIT_W_ANGULAR 2
+#define S2_EDIT_W_FORCE 4
+#define S2_EDIT_W_MOTOR 1
+#define S2_EDIT_W_LIMIT 2
+#define S2_EDIT_W_SPEED 4
+#define S2_EDIT_W_TARGET 8
+
+// what the body kinds read and never write ...
+struct BodyFixed
+{
+	int type;
+	float invMass, invI, px, py;
+};
+
+// ... and what they write
+struct BodyFields
+{
+	float vx, vy, w, fx, fy;
+	int written;
+};
+
+struct JointFields
+{
+	int enableMotor, enableLimit;
+	float motorSpeed, tx, ty;
+	int written;
+};
+
+__device__ inline s2amdWorldEdit loadEdit(const s2amdWorldEdit* edits, size_t i)
+{
+	// (32 bytes, 32-byte aligned: two 16-byte loads)
+	const int4 a = ((const int4*)edits)[2 * i];
+	const float4 b = ((const float4*)edits)[2 * i + 1];
+	s2amdWorldEdit e;
+	e.kind = a.x, e.target = a.y, e.flag = a.z, e.reserved = a.w;
+	e.v[0] = b.x, e.v[1] = b.y, e.v[2] = b.z, e.v[3] = b.w;
+	return e;
+}
+
+__device__ inline void loadBody(const s2amdBody* b, BodyFixed& k, BodyFields& f)
+{
+	k.type = b->type;
+	k.invMass = b->invMass, k.invI = b->invI;
+	k.px = b->position[0], k.py = b->position[1];
+	f.vx = b->linearVelocity[0], f.vy = b->linearVelocity[1];
+	f.w = b->angularVelocity;
+	f.fx = b->force[0], f.fy = b->force[1];
+	f.written = 0;
+}
+
+__device__ inline void storeBody(s2amdBody* b, const BodyFields& f)
+{
+	if ((f.written & S2_EDIT_W_LINEAR) != 0)
+	{
+		b->linearVelocity[0] = f.vx, b->linearVelocity[1] = f.vy;
+	}
+	if ((f.written & S2_EDIT_W_ANGULAR) != 0)
+	{
+		b->angularVelocity = f.w;
+	}
+	if ((f.written & S2_EDIT_W_FORCE) != 0)
+	{
+		b->force[0] = f.fx, b->force[1] = f.fy;
+	}
+}
+
+// one body edit on a live slot (kinds 1-4); the reference's statements, in its order
+__device__ inline void applyBodyEdit(const s2amdWorldEdit& e, const BodyFixed& k, BodyFields& f)
+{
+	if (e.kind == S2AMD_EDIT_BODY_SET_LINEAR_VELOCITY)
+	{
+		f.vx = e.v[0], f.vy = e.v[1]; // body.c:341
+		f.written |= S2_EDIT_W_LINEAR;
+	}
+	else if (e.kind == S2AMD_EDIT_BODY_SET_ANGULAR_VELOCITY)
+	{
+		f.w = e.v[0]; // body.c:349
+		f.written |= S2_EDIT_W_ANGULAR;
+	}
+	else if (e.kind == S2AMD_EDIT_BODY_APPLY_FORCE_TO_CENTER)
+	{
+		f.fx = f.fx + e.v[0], f.fy = f.fy + e.v[1]; // body.c:356: s2Add(body->force, force)
+		f.written |= S2_EDIT_W_FORCE;
+	}
+	else if (k.type == S2AMD_BODY_DYNAMIC) // S2AMD_EDIT_BODY_APPLY_LINEAR_IMPULSE; body.c:363-366: any other type returns
+	{
+		// body.c:368: s2MulAdd(v, invMass, impulse) = {v.x + invMass * impulse.x, v.y + invMass * impulse.y}
+		f.vx = f.vx + k.invMass * e.v[0];
+		f.vy = f.vy + k.invMass * e.v[1];
+		// body.c:369: w += invI * s2Cross(s2Sub(point, position), impulse)
+		const float rx = e.v[2] - k.px, ry = e.v[3] - k.py;
+		f.w = f.w + k.invI * (rx * e.v[1] - ry * e.v[0]);
+		f.written |= S2_EDIT_W_LINEAR | S2_EDIT_W_ANGULAR;
+	}
+}
+
+__device__ inline void loadJoint(const s2amdJoint* j, JointFields& f)
+{
+	f.enableMotor = j->enableMotor, f.enableLimit = j->enableLimit;
+	f.motorSpeed = j->motorSpeed;
+	f.tx = j->targetA[0], f.ty = j->targetA[1];
+	f.written = 0;
+}
+
+__device__ inline void storeJoint(s2amdJoint* j, const JointFields& f)
+{
+	if ((f.written & S2_EDIT_W_MOTOR) != 0)
+	{
+		j->enableMotor = f.enableMotor;
+	}
+	if ((f.written & S2_EDIT_W_LIMIT) != 0)
+	{
+		j->enableLimit = f.enableLimit;
+	}
+	if ((f.written & S2_EDIT_W_SPEED) != 0)
+	{
+		j->motorSpeed = f.motorSpeed;
+	}
+	if ((f.written & S2_EDIT_W_TARGET) != 0)
+	{
+		j->targetA[0] = f.tx, j->targetA[1] = f.ty;
+	}
+}
+
+// one joint edit (kinds 5-8) on a slot of type `type`; false: the joint is free or of the other type, nothing is written
+__device__ inline bool applyJointEdit(const s2amdWorldEdit& e, int type, JointFields& f)
+{
+	if (e.kind == S2AMD_EDIT_MOUSE_SET_TARGET)
+	{
+		if (type != S2AMD_JOINT_MOUSE)
+		{
+			return false;
+		}
+		f.tx = e.v[0], f.ty = e.v[1]; // mouse_joint.c:28
+		f.written |= S2_EDIT_W_TARGET;
+		return true;
+	}
+	if (type != S2AMD_JOINT_REVOLUTE)
+	{
+		return false;
+	}
+	if (e.kind == S2AMD_EDIT_REVOLUTE_ENABLE_LIMIT)
+	{
+		f.enableLimit = e.flag != 0 ? 1 : 0; // revolute_joint.c:900
+		f.written |= S2_EDIT_W_LIMIT;
+	}
+	else if (e.kind == S2AMD_EDIT_REVOLUTE_ENABLE_MOTOR)
+	{
+		f.enableMotor = e.flag != 0 ? 1 : 0; // revolute_joint.c:913
+		f.written |= S2_EDIT_W_MOTOR;
+	}
+	else
+	{
+		f.motorSpeed = e.v[0]; // revolute_joint.c:926
+		f.written |= S2_EDIT_W_SPEED;
+	}
+	return true;
+}
+
+// All targets distinct: one lane per edit.  The host has checked kind and target of every record against the capacities.
+__global__ __launch_bounds__(S2_BLOCK) void editDistinctKernel(const s2amdWorldEdit* edits, int count, s2amdBody* bodies, s2amdJoint* joints, int* skipped)
+{
+	const size_t i = (size_t)blockIdx.x * S2_BLOCK + threadIdx.x;
+	bool skip = false;
+	if (i < (size_t)count)
+	{
+		const s2amdWorldEdit e = loadEdit(edits, i);
+		if (e.kind < S2_EDIT_FIRST_JOINT_KIND)
+		{
+			s2amdBody* b = bodies + e.target;
+			BodyFixed k;
+			BodyFields f;
+			loadBody(b, k, f);
+			skip = k.type == S2AMD_BODY_FREE;
+			if (!skip)
+			{
+				applyBodyEdit(e, k, f);
+				storeBody(b, f);
+			}
+		}
+		else
+		{
+			s2amdJoint* j = joints + e.target;
+			JointFields f;
+			loadJoint(j, f);
+			skip = !applyJointEdit(e, j->type, f);
+			storeJoint(j, f);
+		}
+	}
+	if (skipped != nullptr)
+	{
+		const unsigned long long m = __ballot(skip);
+		if (m != 0ull && (threadIdx.x & 63) == 0)
+		{
+			atomicAdd(skipped, __popcll(m));
+		}
+	}
+}
+
+// the sort key of edit i: joints behind bodies, then the target, then the place in the list
+__global__ __launch_bounds__(S2_BLOCK) void editKeysKernel(const s2amdWorldEdit* edits, int count, unsigned long long* keys)
+{
+	const size_t i = (size_t)blockIdx.x * S2_BLOCK + threadIdx.x;
+	if (i >= (size_t)count)
+	{
+		return;
+	}
+	const int2 kt = *(const int2*)(edits + i); // {kind, target}
+	const unsigned int who = (kt.x >= S2_EDIT_FIRST_JOINT_KIND ? 0x80000000u : 0u) | (unsigned int)kt.y;
+	keys[i] = ((unsigned long long)who << 32) | (unsigned long long)i;
+}
+
+// Repeated targets: one lane per sorted key; the first lane of a target's segment walks it.
+__global__ __launch_bounds__(S2_BLOCK) void editWalkKernel(const s2amdWorldEdit* edits, const unsigned long long* keys, int count, s2amdBody* bodies, s2amdJoint* joints,
+															 int* skipped)
+{
+	const size_t i = (size_t)blockIdx.x * S2_BLOCK + threadIdx.x;
+	int skips = 0;
+	if (i < (size_t)count)
+	{
+		const unsigned int who = (unsigned int)(keys[i] >> 32);
+		if (i == 0 || (unsigned int)(keys[i - 1] >> 32) != who)
+		{
+			const int target = (int)(who & 0x7fffffffu);
+			if ((who & 0x80000000u) == 0u)
+			{
+				s2amdBody* b = bodies + target;
+				BodyFixed k;
+				BodyFields f;
+				loadBody(b, k, f);
+				for (size_t at = i; at < (size_t)count && (unsigned int)(keys[at] >> 32) == who; ++at)
+				{
+					if (k.type == S2AMD_BODY_FREE)
+					{
+						skips += 1;
+						continue;
+					}
+					applyBodyEdit(loadEdit(edits, (size_t)(unsigned int)keys[at]), k, f);
+				}
+				storeBody(b, f);
+			}
+			else
+			{
+				s2amdJoint* j = joints + target;
+				const int type = j->type;
+				JointFields f;
+				loadJoint(j, f);
+				for (size_t at = i; at < (size_t)count && (unsigned int)(keys[at] >> 32) == who; ++at)
+				{
+					skips += applyJointEdit(loadEdit(edits, (size_t)(unsigned int)keys[at]), type, f) ? 0 : 1;
+				}
+				storeJoint(j, f);
+			}
+		}
+	}
+	if (skipped != nullptr)
+	{
+		// the wave's sum, then one atomic
+		for (int offset = 32; offset > 0; offset >>= 1)
+		{
+			skips += __shfl_down(skips, offset, 64);
+		}
+		if ((threadIdx.x & 63) == 0 && skips != 0)
+		{
+			atomicAdd(skipped, skips);
+		}
+	}
+}
+
+inline size_t roundUp(size_t bytes)
+{
+	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
+}
+
+// The pass over the caller's list: every record checked, copied to the pinned stage, its target stamped.  -1: a record is invalid
+// (*bad is its index); 0: all targets distinct; 1: some target occurs twice.
+int checkAndStage(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count, int32_t* bad)
+{
+	const int nb = s->bodyCapacity, nj = s->jointCapacity;
+	if ((int)s->hEditBodyStamp.size() != nb || (int)s->hEditJointStamp.size() != nj || s->editGeneration == UINT32_MAX)
+	{
+		s->hEditBodyStamp.assign((size_t)nb, 0u);
+		s->hEditJointStamp.assign((size_t)nj, 0u);
+		s->editGeneration = 0;
+	}
+	const uint32_t generation = ++s->editGeneration;
+	s2amdWorldEdit* stage = (s2amdWorldEdit*)s->hostEditStage;
+	bool repeated = false;
+	for (int32_t i = 0; i < count; ++i)
+	{
+		const s2amdWorldEdit& e = edits[i];
+		const bool joint = e.kind >= S2_EDIT_FIRST_JOINT_KIND;
+		if (e.kind < S2AMD_EDIT_BODY_SET_LINEAR_VELOCITY || e.kind > S2_EDIT_LAST_KIND || e.reserved != 0 || e.target < 0 || e.target >= (joint ? nj : nb))
+		{
+			*bad = i;
+			return -1;
+		}
+		uint32_t& stamp = joint ? s->hEditJointStamp[(size_t)e.target] : s->hEditBodyStamp[(size_t)e.target];
+		repeated = repeated || stamp == generation;
+		stamp = generation;
+		stage[i] = e;
+	}
+	return repeated ? 1 : 0;
+}
+
+} // namespace
+
+#pragma GCC visibility push(default)
+extern "C"
+{
+
+int s2amd_world_edit(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count, int32_t* skipped)
+{
+	if (!s || count < 0 || (count > 0 && !edits))
+	{
+		return fail(S2AMD_E_INVALID, "bad argument");
+	}
+	if (!s->worldResident || !s->resident)
+	{
+		return fail(S2AMD_E_STATE, "no resident world");
+	}
+	if (count == 0)
+	{
+		if (skipped)
+		{
+			*skipped = 0;
+		}
+		return S2AMD_OK;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	hipStream_t st = s->stream;
+	// the pinned stage: the caller's list is copied while it is checked, so the caller may reuse it at once and the copy to the device
+	// is a true asynchronous one.  The copy of the call before may still be reading the stage: its event is waited for first.
+	const size_t listBytes = (size_t)count * sizeof(s2amdWorldEdit);
+	if (!s->evEditStaged)
+	{
+		HIP_TRY(hipEventCreateWithFlags(&s->evEditStaged, hipEventDisableTiming));
+	}
+	else
+	{
+		HIP_TRY(hipEventSynchronize(s->evEditStaged));
+	}
+	if (s->hostEditStageBytes < listBytes)
+	{
+		if (s->hostEditStage)
+		{
+			(void)hipHostFree(s->hostEditStage);
+			s->hostEditStage = nullptr;
+			s->hostEditStageBytes = 0;
+		}
+		const size_t want = std::max(roundUp(listBytes + listBytes / 2), (size_t)4096);
+		HIP_TRY(hipHostMalloc((void**)&s->hostEditStage, want, hipHostMallocDefault));
+		s->hostEditStageBytes = want;
+	}
+	int32_t bad = -1;
+	const int repeated = checkAndStage(s, edits, count, &bad);
+	if (repeated < 0)
+	{
+		return fail(S2AMD_E_INVALID, "world edit " + std::to_string(bad) +
+										 " is invalid (a kind outside 1..8, a target outside the uploaded capacity, reserved != 0): nothing was applied");
+	}
+	// dEdit: {the skip count, the list, [the keys, the sorted keys, rocPRIM's scratch]}
+	size_t at = roundUp(sizeof(int));
+	const size_t listAt = at;
+	at += roundUp(listBytes);
+	size_t keysAt = 0, sortedAt = 0, tmpAt = 0, tmpBytes = 0;
+	if (repeated)
+	{
+		HIP_TRY(rocprim::radix_sort_keys(nullptr, tmpBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)count, 0, 64, st));
+		keysAt = at;
+		at += roundUp((size_t)count * sizeof(unsigned long long));
+		sortedAt = at;
+		at += roundUp((size_t)count * sizeof(unsigned long long));
+		tmpAt = at;
+		at += roundUp(tmpBytes);
+	}
+	if (int rc = s->dEdit.ensure(at))
+	{
+		return rc;
+	}
+	char* base = (char*)s->dEdit.p;
+	int* dSkipped = skipped ? (int*)base : nullptr;
+	const s2amdWorldEdit* dList = (const s2amdWorldEdit*)(base + listAt);
+	if (skipped)
+	{
+		HIP_TRY(hipMemsetAsync(base, 0, sizeof(int), st));
+	}
+	HIP_TRY(hipMemcpyAsync(base + listAt, s->hostEditStage, listBytes, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipEventRecord(s->evEditStaged, st));
+	s2amdBody* bodies = (s2amdBody*)s->dBodies.p;
+	s2amdJoint* joints = (s2amdJoint*)s->dJoints.p;
+	if (!repeated)
+	{
+		editDistinctKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>(dList, count, bodies, joints, dSkipped);
+	}
+	else
+	{
+		unsigned long long* keys = (unsigned long long*)(base + keysAt);
+		unsigned long long* sorted = (unsigned long long*)(base + sortedAt);
+		editKeysKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>(dList, count, keys);
+		HIP_TRY(rocprim::radix_sort_keys(base + tmpAt, tmpBytes, keys, sorted, (size_t)count, 0, 64, st));
+		editWalkKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>(dList, sorted, count, bodies, joints, dSkipped);
+	}
+	HIP_TRY(hipGetLastError());
+	if (skipped)
+	{
+		HIP_TRY(hipMemcpyAsync(skipped, base, sizeof(int), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+	}
+	return S2AMD_OK;
+}
+
+} // extern "C"
+#pragma GCC visibility pop

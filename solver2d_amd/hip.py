@@ -34,6 +34,7 @@ EXPORTS = [
     "s2amd_world_ray_cast", "s2amd_world_point_probe", "s2amd_world_query_boxes",
     "s2amd_world_closest_shape", "s2amd_world_shapes_in_range",
     "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
+    "s2amd_world_edit",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -131,6 +132,7 @@ def load(fast=False):
     L.s2amd_world_shapes_in_range.argtypes = [vp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_collide_shape.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_deepest_contact.argtypes = [vp, vp, i32, vp]
+    L.s2amd_world_edit.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -530,6 +532,17 @@ class Solver:
                 continue
             self._ck(rc)
             return offsets, hits[: n.value].copy()
+
+    # ---- world edits: the reference's eight per-frame setters applied to the resident records, the structure kept ----
+    def world_edit(self, edits, want_skipped=True):
+        """Applies wire.world_edit_dtype records (wire.edit_*) to the resident bodies and joints in list order, behind the last step and
+        before the next.  Returns how many were skipped (a free slot, a joint of the other type); with want_skipped=False the call only
+        enqueues, reads nothing back and returns None."""
+        edits = np.ascontiguousarray(edits)
+        assert edits.dtype == wire.world_edit_dtype
+        skipped = ctypes.c_int32(-1)
+        self._ck(self._L.s2amd_world_edit(self._h, wire.as_ptr(edits), len(edits), ctypes.byref(skipped) if want_skipped else None))
+        return skipped.value if want_skipped else None
 
     # ---- the reports of the resident world: the three shapes their getters have ----
     def _world_list(self, fn, dtype, expected):

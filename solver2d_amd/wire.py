@@ -248,3 +248,56 @@ contact_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("pointCo
                               ("points", contact_hit_point_dtype, 2), ("pad", np.int32, 2)])
 CONTACT_QUERY_SIZE, CONTACT_HIT_SIZE = contact_query_dtype.itemsize, contact_hit_dtype.itemsize
 assert CONTACT_QUERY_SIZE == 160 and CONTACT_HIT_SIZE == 80
+
+# world edits on the resident world (include/solver2d_amd.h: s2amd_world_edit): s2amdWorldEdit and the S2AMD_EDIT_* kinds
+world_edit_dtype = np.dtype([("kind", np.int32), ("target", np.int32), ("flag", np.int32), ("reserved", np.int32), ("v", np.float32, 4)])
+WORLD_EDIT_SIZE = world_edit_dtype.itemsize
+assert WORLD_EDIT_SIZE == 32
+EDIT_BODY_SET_LINEAR_VELOCITY, EDIT_BODY_SET_ANGULAR_VELOCITY, EDIT_BODY_APPLY_FORCE_TO_CENTER, EDIT_BODY_APPLY_LINEAR_IMPULSE = 1, 2, 3, 4
+EDIT_MOUSE_SET_TARGET, EDIT_REVOLUTE_ENABLE_LIMIT, EDIT_REVOLUTE_ENABLE_MOTOR, EDIT_REVOLUTE_SET_MOTOR_SPEED = 5, 6, 7, 8
+EDIT_KINDS = {"BODY_SET_LINEAR_VELOCITY": 1, "BODY_SET_ANGULAR_VELOCITY": 2, "BODY_APPLY_FORCE_TO_CENTER": 3, "BODY_APPLY_LINEAR_IMPULSE": 4,
+              "MOUSE_SET_TARGET": 5, "REVOLUTE_ENABLE_LIMIT": 6, "REVOLUTE_ENABLE_MOTOR": 7, "REVOLUTE_SET_MOTOR_SPEED": 8}
+
+
+def _edit(kind, target, v=(), flag=0):
+    e = np.zeros(1, dtype=world_edit_dtype)[0]
+    e["kind"], e["target"], e["flag"] = kind, target, flag
+    e["v"][:len(v)] = v
+    return e
+
+
+def edit_set_linear_velocity(body, velocity):
+    return _edit(EDIT_BODY_SET_LINEAR_VELOCITY, body, velocity)
+
+
+def edit_set_angular_velocity(body, w):
+    return _edit(EDIT_BODY_SET_ANGULAR_VELOCITY, body, (w,))
+
+
+def edit_apply_force_to_center(body, force):
+    return _edit(EDIT_BODY_APPLY_FORCE_TO_CENTER, body, force)
+
+
+def edit_apply_linear_impulse(body, impulse, point):
+    return _edit(EDIT_BODY_APPLY_LINEAR_IMPULSE, body, tuple(impulse) + tuple(point))
+
+
+def edit_mouse_set_target(joint, target):
+    return _edit(EDIT_MOUSE_SET_TARGET, joint, target)
+
+
+def edit_revolute_enable_limit(joint, flag):
+    return _edit(EDIT_REVOLUTE_ENABLE_LIMIT, joint, flag=1 if flag else 0)
+
+
+def edit_revolute_enable_motor(joint, flag):
+    return _edit(EDIT_REVOLUTE_ENABLE_MOTOR, joint, flag=1 if flag else 0)
+
+
+def edit_revolute_set_motor_speed(joint, speed):
+    return _edit(EDIT_REVOLUTE_SET_MOTOR_SPEED, joint, (speed,))
+
+
+def edit_list(edits):
+    """A list of the records above (or an array of them) as one contiguous wire.world_edit_dtype array."""
+    return np.ascontiguousarray(np.array(list(edits), dtype=world_edit_dtype)) if len(edits) else np.zeros(0, dtype=world_edit_dtype)
