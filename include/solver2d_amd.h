@@ -840,8 +840,7 @@ int s2amd_world_query_boxes(s2amdSolver* solver, const s2amdBoxQuery* boxes, int
  *                 iterations -- and its body.  Nothing in range: shape = body = -1, distance = maxDistance, points +0, iterations 0.
  * The composition is ours (the reference has no world-level distance query); every D is the reference's bit for bit.  All arithmetic is
  * fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in libs2amd.so and in
- * libs2amd_fast.so alike.  Not offered: sharded worlds, shape casts, a simplex cache kept between calls, queries or answers in device
- * memory. */
+ * libs2amd_fast.so alike.  Not offered: sharded worlds, a simplex cache kept between calls, queries or answers in device memory. */
 typedef struct s2amdProximityQuery /* 96 bytes */
 {
 	float vertices[8][2]; /* the query's proxy in its own frame: s2MakeProxy(vertices, count, radius) */
@@ -899,7 +898,7 @@ int s2amd_world_shapes_in_range(s2amdSolver* solver, const s2amdProximityQuery* 
  *                 every other field zero.
  * The composition is ours (the reference has no world-level manifold query); every M is the reference's bit for bit.  All arithmetic is
  * fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in libs2amd.so and in
- * libs2amd_fast.so alike.  Not offered: sharded worlds, shape casts, a simplex cache kept between calls, queries or answers in device
+ * libs2amd_fast.so alike.  Not offered: sharded worlds, a simplex cache kept between calls, queries or answers in device
  * memory, the drop-in's contacts routed through these calls, the device trees as an accelerator. */
 typedef struct s2amdContactQuery /* 160 bytes */
 {
@@ -929,6 +928,70 @@ typedef struct s2amdContactHit /* 80 bytes */
 int s2amd_world_collide_shape(s2amdSolver* solver, const s2amdContactQuery* queries, int32_t count, int32_t* offsets /* [count + 1] */,
 							  s2amdContactHit* hits, int32_t capacity, int32_t* total);
 int s2amd_world_deepest_contact(s2amdSolver* solver, const s2amdContactQuery* queries, int32_t count, s2amdContactHit* hits /* [count] */);
+
+/* (additive, API 5) Shape casts: "this shape moves from here along this vector: what does it hit first, where, and at which fraction of
+ * the way?" asked of the resident world -- a bullet, a character controller's move-and-slide, a thick ray, a swept placement test, a
+ * swept sensor.  The reference has no continuous collision at all (a fast body tunnels); the composition below is ours: conservative
+ * advancement in which every distance is the reference's own s2ShapeDistance (src/distance.c:485-636), bit for bit.  The two batched
+ * calls answer from the resident arrays, under the general terms of the scene queries above: the world as it stands, enqueued behind
+ * whatever changed it last on the solver's stream, any number of times between steps, nothing resident written, no host wait added to a
+ * step, no device trees needed, S2AMD_E_STATE without a resident world, count == 0 succeeds and touches nothing.  LIVE, xf(body) and
+ * PASSES are the scene queries' definitions.
+ *   Validation    on the host, for every cast before anything is enqueued: 1 <= count <= 8; vertices[0 .. count), radius, position, rot,
+ *                 translation and maxFraction finite; radius >= 0; maxFraction >= 0.  One failing cast makes the whole call return
+ *                 S2AMD_E_INVALID with every output untouched.  rot is not checked for normalisation.
+ *   Constants     all fp32: target = s2_linearSlop (0.005f); tolerance = 0.25f * s2_linearSlop; threshold = target + tolerance (one
+ *                 add); CAP = 20.
+ *   Swept box     e = s2MulAdd(position, maxFraction, translation).  lower0 / upper0: the bounds of s2TransformPoint({position, rot},
+ *                 vertices[i]) for i < count, folded from vertex 0 in index order with s2Min / s2Max as the proximity queries' box is;
+ *                 lower1 / upper1: the same fold at {e, rot}.  lower = s2Min(lower0, lower1), upper = s2Max(upper0, upper1);
+ *                 r = radius + s2_speculativeDistance (one add; 0.02 >= threshold, so no shape within reach of the path is pruned);
+ *                 the box is {lower.x - r, lower.y - r, upper.x + r, upper.y + r}.
+ *   Candidates    live, passing, s2AABB_Overlaps(fatAABB, box).  No other pruning decides a result.
+ *   C(q, s)       the proxies and xfB = xf(s.body) are those of the proximity queries' D(q, s); the cache is empty, useRadii = true.
+ *                 t_0 = +0.  For k = 0, 1, ...:
+ *                   1. D_k = s2ShapeDistance with transformA = {s2MulAdd(position, t_k, translation), rot}.
+ *                   2. D_k.distance < threshold: HIT at t_k.
+ *                   3. Otherwise, k == CAP: HIT at t_k -- the sweep stops short and never passes through; the record's
+ *                      distance >= threshold says so.
+ *                   4. n = s2Normalize(s2Sub(D_k.pointB, D_k.pointA)), approach = s2Dot(translation, n).  approach <= 0: MISS (moving
+ *                      away or along; a zero translation ends here).
+ *                   5. t_{k+1} = t_k + (D_k.distance - target) / approach.  !(t_{k+1} <= maxFraction): MISS.
+ *                 The hit record is {s, s.body, t_k, D_k.distance, D_k.pointB, s2Normalize(s2Sub(D_k.pointA, D_k.pointB)), k}.
+ *   s2amd_world_cast_shape_all   the hits of every cast, ascending by slot, in the CSR form and with the S2AMD_E_CAPACITY protocol of
+ *                 s2amd_world_point_probe: with capacity < *total, offsets and *total are filled, hits is untouched, the caller asks
+ *                 again.
+ *   s2amd_world_cast_shape       per cast the hit of least fraction, ties to the lowest slot (fractions are >= +0, so their bits order
+ *                 as their values); the record is that hit's own.  No hit: shape = body = -1, fraction = maxFraction and every other
+ *                 field zero.
+ * All arithmetic is fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in
+ * libs2amd.so and in libs2amd_fast.so alike.  Not offered: rotation during the sweep, sharded worlds, casts or answers in device
+ * memory, the device trees as an accelerator. */
+typedef struct s2amdShapeCast /* 112 bytes */
+{
+	float vertices[8][2]; /* the moving proxy in its own frame: s2MakeProxy(vertices, count, radius) */
+	int32_t count;		  /* 1..8 */
+	float radius;		  /* >= 0 */
+	float position[2];	  /* transform at fraction 0: p */
+	float rot[2];		  /* q {s, c}; the cast does not rotate; not checked for normalisation */
+	float translation[2]; /* the sweep: at fraction t the proxy stands at position + t * translation */
+	float maxFraction;	  /* >= 0, finite */
+	uint32_t maskBits;
+	int32_t pad[2];		  /* ignored */
+} s2amdShapeCast;
+typedef struct s2amdShapeCastHit /* 48 bytes */
+{
+	int32_t shape, body;
+	float fraction;		/* t_k */
+	float distance;		/* D_k.distance at that fraction */
+	float point[2];		/* D_k.pointB: on the world shape */
+	float normal[2];	/* from the world shape towards the moving one; zero when they overlap */
+	int32_t iterations; /* k: the advances made; 0 = already within reach at the start */
+	int32_t pad[3];		/* 0 */
+} s2amdShapeCastHit;
+int s2amd_world_cast_shape(s2amdSolver* solver, const s2amdShapeCast* casts, int32_t count, s2amdShapeCastHit* hits /* [count] */);
+int s2amd_world_cast_shape_all(s2amdSolver* solver, const s2amdShapeCast* casts, int32_t count, int32_t* offsets /* [count + 1] */,
+							   s2amdShapeCastHit* hits, int32_t capacity, int32_t* total);
 
 /* (additive, API 5) World edits: the reference's eight cheap setters an interactive program calls every frame -- a body dragged by the
  * mouse joint, a motor whose speed follows a controller, wind, a thrown ball, an explosion -- applied to the resident world where it

@@ -34,6 +34,7 @@ EXPORTS = [
     "s2amd_world_ray_cast", "s2amd_world_point_probe", "s2amd_world_query_boxes",
     "s2amd_world_closest_shape", "s2amd_world_shapes_in_range",
     "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
+    "s2amd_world_cast_shape", "s2amd_world_cast_shape_all",
     "s2amd_world_edit",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
@@ -132,6 +133,8 @@ def load(fast=False):
     L.s2amd_world_shapes_in_range.argtypes = [vp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_collide_shape.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_deepest_contact.argtypes = [vp, vp, i32, vp]
+    L.s2amd_world_cast_shape.argtypes = [vp, vp, i32, vp]
+    L.s2amd_world_cast_shape_all.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_edit.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
@@ -527,6 +530,34 @@ class Solver:
             n = ctypes.c_int32()
             rc = self._L.s2amd_world_collide_shape(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(hits), cap,
                                                    ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
+                cap = n.value
+                continue
+            self._ck(rc)
+            return offsets, hits[: n.value].copy()
+
+    # ---- shape casts on the resident world: a caller's proxy swept along a vector, conservative advancement over s2ShapeDistance ----
+    def world_cast_shape(self, casts):
+        """The hit of least fraction for every cast (wire.shape_cast_dtype) -> wire.shape_cast_hit_dtype[len(casts)];
+        shape == -1: the sweep reaches nothing up to maxFraction."""
+        casts = np.ascontiguousarray(casts)
+        assert casts.dtype == wire.shape_cast_dtype
+        hits = np.zeros(len(casts), dtype=wire.shape_cast_hit_dtype)
+        self._ck(self._L.s2amd_world_cast_shape(self._h, wire.as_ptr(casts), len(casts), wire.as_ptr(hits)))
+        return hits
+
+    def world_cast_shape_all(self, casts, expected=None):
+        """Every shape each cast hits: (offsets[len + 1], hits), ascending by slot per cast.  Asked again with the total the library
+        states when it answers S2AMD_E_CAPACITY."""
+        casts = np.ascontiguousarray(casts)
+        assert casts.dtype == wire.shape_cast_dtype
+        offsets = np.zeros(len(casts) + 1, dtype=np.int32)
+        cap = max(int(expected or 4 * len(casts) + 64), 1)
+        while True:
+            hits = np.zeros(cap, dtype=wire.shape_cast_hit_dtype)
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_cast_shape_all(self._h, wire.as_ptr(casts), len(casts), wire.as_ptr(offsets), wire.as_ptr(hits), cap,
+                                                    ctypes.byref(n))
             if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
                 cap = n.value
                 continue

@@ -249,6 +249,16 @@ contact_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("pointCo
 CONTACT_QUERY_SIZE, CONTACT_HIT_SIZE = contact_query_dtype.itemsize, contact_hit_dtype.itemsize
 assert CONTACT_QUERY_SIZE == 160 and CONTACT_HIT_SIZE == 80
 
+# shape casts on the resident world (include/solver2d_amd.h: s2amd_world_cast_shape, s2amd_world_cast_shape_all)
+# s2amdShapeCast, s2amdShapeCastHit
+shape_cast_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("count", np.int32), ("radius", np.float32), ("position", np.float32, 2),
+                             ("rot", np.float32, 2), ("translation", np.float32, 2), ("maxFraction", np.float32), ("maskBits", np.uint32),
+                             ("pad", np.int32, 2)])
+shape_cast_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("fraction", np.float32), ("distance", np.float32),
+                                 ("point", np.float32, 2), ("normal", np.float32, 2), ("iterations", np.int32), ("pad", np.int32, 3)])
+SHAPE_CAST_SIZE, SHAPE_CAST_HIT_SIZE = shape_cast_dtype.itemsize, shape_cast_hit_dtype.itemsize
+assert SHAPE_CAST_SIZE == 112 and SHAPE_CAST_HIT_SIZE == 48
+
 # world edits on the resident world (include/solver2d_amd.h: s2amd_world_edit): s2amdWorldEdit and the S2AMD_EDIT_* kinds
 world_edit_dtype = np.dtype([("kind", np.int32), ("target", np.int32), ("flag", np.int32), ("reserved", np.int32), ("v", np.float32, 4)])
 WORLD_EDIT_SIZE = world_edit_dtype.itemsize
