@@ -863,6 +863,93 @@ int s2amd_world_closest_shape(s2amdSolver* solver, const s2amdProximityQuery* qu
 int s2amd_world_shapes_in_range(s2amdSolver* solver, const s2amdProximityQuery* queries, int32_t count, int32_t* offsets /* [count + 1] */,
 								int32_t* shapes, float* distances /* [capacity], may be NULL */, int32_t capacity, int32_t* total);
 
+/* (additive, API 5) Sensor report: "which shapes are inside this region now, which came in during this step, which went out?" --
+ * a pressure plate, a goal line, a kill zone, a pick-up radius carried by a body.  A list of up to S2AMD_MAX_SENSORS regions, each a
+ * proxy shape fixed in the world or attached to a body, is evaluated on the resident arrays behind stage 4 of every s2amd_world_step (a
+ * step the library repeats internally reports once), after the other five reports; the report owns its "before" state on the device.
+ * It generalises the shape report's one view box with its entered / left lists.  With no flag set a step enqueues nothing for it; the
+ * step gains no host wait, the getters wait.  LIVE, xf(body) and PASSES are the scene queries' definitions; every answer is an
+ * order-free statement:
+ *   Validation    on the host, in s2amd_world_set_sensors, before anything is changed: 0 <= count <= S2AMD_MAX_SENSORS; per sensor
+ *                 1 <= count <= 8; vertices[0 .. count), radius, position, rot and margin finite; radius >= 0; margin >= 0; no flag
+ *                 bits beyond the two below; body < bodyCapacity of the resident world (with no world resident, body is not bounded).
+ *                 One bad record refuses the whole list with S2AMD_E_INVALID, and the old list stands.  rot is not checked for
+ *                 normalisation.  The list holds across uploads; a sensor whose body is outside the new world's bodyCapacity is
+ *                 inactive there.  While the report is on, sensors x shapeCapacity of the resident world must stay below 2^31 (the lists are
+ *                 indexed by int32): s2amd_world_set_sensors refuses a list that exceeds it with S2AMD_E_INVALID (the old list
+ *                 stands), and so does s2amd_world_upload for a world of more than 2^31 / sensors shape slots.  Should the device
+ *                 block of the new list fail to be made, the error is returned and the old list stands as well.
+ *   Active        not S2AMD_SENSOR_DISABLED, and body < 0 or (body < bodyCapacity and bodies[body].type != S2AMD_BODY_FREE).  An
+ *                 inactive sensor holds nothing; its state has active = 0, transform and box +0, lowestShape = -1.
+ *   Transform     body < 0: {position, rot}.  Otherwise s2MulTransforms(xf(body), {position, rot}) (include/solver2d/math.h:368-374,
+ *                 s2MulRot :291-300): q.s = b.s * rot.c + b.c * rot.s, q.c = b.c * rot.c - b.s * rot.s, p = s2Add(s2RotateVector(b,
+ *                 position), origins[body]) with b = bodies[body].rot.
+ *   Box           the proximity queries' query box of {vertices, count, radius} under the transform with maxDistance = margin.
+ *   Candidates    live; (categoryBits & maskBits) != 0; s2AABB_Overlaps(fatAABB, box); shape.body != sensor.body; with
+ *                 S2AMD_SENSOR_SKIP_STATIC, bodies[shape.body].type != S2AMD_BODY_STATIC.  No other pruning decides a result.
+ *   Inside        a candidate with D.distance <= margin, D the proximity queries' D(q, s) with transformA = the transform above:
+ *                 empty cache, useRadii, the FLT_EPSILON branch included.
+ *   "Before"      the same rule evaluated at s2amd_world_upload, when the report is turned on (or its listCapacity changes), and
+ *                 whenever s2amd_world_set_sensors succeeds on a resident world: the caller's own acts raise no events, as with the shape
+ *                 view.  Each of these voids the last step's report: the getters answer S2AMD_E_STATE until the next step.
+ *   INSIDE        s2amd_world_sensor_inside: a CSR list over all sensors in list order, shape slots ascending; inactive sensors have
+ *                 empty ranges; the S2AMD_E_CAPACITY protocol of s2amd_world_point_probe (offsets and *total filled, shapes untouched).
+ *   EVENTS        s2amd_world_sensor_events: `entered` holds the (sensor, shape) pairs inside now and not before, `left` the reverse,
+ *                 both ascending by (sensor, shape); body = the shape's body as the resident array holds it, sensorBody = the sensor's.
+ *                 A sensor that turned inactive leaves everything it held; one that turned active enters everything it holds.  With a
+ *                 capacity too small both counts are filled and both lists untouched (S2AMD_E_CAPACITY).
+ *   STATES        s2amd_world_sensor_states: one record per sensor in list order (S2AMD_E_CAPACITY with *count filled when capacity is
+ *                 less); lowestShape = the lowest inside slot or -1; the inside / entered / left counts are filled whatever other flags
+ *                 are set.
+ *   Errors        those of the other reports: S2AMD_E_STATE without a resident world, when the getter's flag was not set before the
+ *                 last step, or when no step has run since; unknown flag bits and listCapacity < 0 give S2AMD_E_INVALID.
+ *   listCapacity  sizes the three device lists a step writes (entries per list).  A cost knob that never changes an answer: when a
+ *                 step's total exceeds it, the getter rebuilds that list from the kept masks into scratch of the needed size -- one more
+ *                 launch and one more wait.  listCapacity 0 gives the same bytes as an ample value.  A call that changes listCapacity,
+ *                 whatever its flags, voids the last step's report (its lists were laid out under the old value).
+ *   Memory        the masks cost sensors x ceil(shapeCapacity / 256) x 32 bytes per set, and there are four sets (now, before, entered,
+ *                 left); beside them 128 + 64 + 112 bytes per sensor, 12 bytes per sensor and tile of prefix sums, and 36 bytes per list
+ *                 entry of listCapacity.  s2amd_world_set_sensors on a resident world with the report on waits for the stream once (the
+ *                 list is copied to the device before the call returns).
+ * The reference has no sensors: the composition is ours; every distance is the reference's s2ShapeDistance bit for bit.  All arithmetic
+ * is fp32 in the reference's operation order without contraction, in libs2amd.so and in libs2amd_fast.so alike.  Not offered:
+ * body-level events, sensors in device memory, sharded worlds. */
+#define S2AMD_MAX_SENSORS 1024
+#define S2AMD_SENSOR_DISABLED 1	   /* holds nothing, raises no events */
+#define S2AMD_SENSOR_SKIP_STATIC 2 /* shapes on static bodies are not candidates */
+typedef struct s2amdSensor /* 112 bytes */
+{
+	float vertices[8][2]; /* the sensor's proxy in its own frame: s2MakeProxy(vertices, count, radius) */
+	int32_t count;		  /* 1..8 */
+	float radius;		  /* >= 0 */
+	float position[2];	  /* the frame: in the world (body < 0) or relative to the body */
+	float rot[2];		  /* {s, c} */
+	float margin;		  /* inside when D.distance <= margin; >= 0, finite */
+	uint32_t maskBits;
+	int32_t body;  /* < 0: fixed in the world */
+	int32_t flags; /* S2AMD_SENSOR_* */
+	int32_t pad[2];
+} s2amdSensor;
+int s2amd_world_set_sensors(s2amdSolver* solver, const s2amdSensor* sensors, int32_t count); /* replaces the whole list; count 0 clears */
+#define S2AMD_SENSOR_REPORT_INSIDE 1
+#define S2AMD_SENSOR_REPORT_EVENTS 2
+#define S2AMD_SENSOR_REPORT_STATES 4
+int s2amd_world_set_sensor_report(s2amdSolver* solver, int32_t flags, int32_t listCapacity);
+typedef struct s2amdSensorEvent /* 16 bytes */
+{
+	int32_t sensor, shape, body, sensorBody;
+} s2amdSensorEvent;
+typedef struct s2amdSensorState /* 64 bytes */
+{
+	int32_t sensor, body, active, inside, entered, left, lowestShape, pad;
+	float position[2], rot[2]; /* the world transform used */
+	float box[4];			   /* the candidate box used */
+} s2amdSensorState;
+int s2amd_world_sensor_inside(s2amdSolver* solver, int32_t* offsets /* [sensorCount + 1] */, int32_t* shapes, int32_t capacity, int32_t* total);
+int s2amd_world_sensor_events(s2amdSolver* solver, s2amdSensorEvent* entered, int32_t enteredCapacity, int32_t* enteredCount, s2amdSensorEvent* left,
+							  int32_t leftCapacity, int32_t* leftCount);
+int s2amd_world_sensor_states(s2amdSolver* solver, s2amdSensorState* out, int32_t capacity, int32_t* count);
+
 /* (additive, API 5) Contact queries: "if this shape stood here, what would it touch, where, and how deep?" asked of the resident world
  * -- a character controller, a ghost or trigger shape, spawn placement with push-out, a "will this fit" test.  The reference answers it
  * with its nine manifold functions s2Collide* (include/solver2d/manifold.h:56-85), dispatched by s_registers (src/contact.c:139-151);

@@ -550,7 +550,7 @@ struct SolverRest
 	std::vector<uint8_t> hSlotBytes;
 	bool slotBytesFresh = false; // hSlotBytes is of the state the device is in right now (cleared by every world call that changes it)
 	std::vector<int32_t> hSeparated;
-	// The five reports behind s2amd_world_step, in the order a step enqueues them (report_host.cpp: the table and the helpers their host sides
+	// The reports behind s2amd_world_step, in the order a step enqueues them (report_host.cpp: the table and the helpers their host sides
 	// share).  Each has a ReportState and, where its getters read counts or a summary, a typed host copy of the head its write pass leaves.
 	ReportState contactReport; // contact_report.hip; s2amd_world_set_report: S2AMD_REPORT_*
 	int32_t hReportHead[4] = {0, 0, 0, 0}; // {began, ended, touching, 0}
@@ -581,6 +581,12 @@ struct SolverRest
 	int metricsLength = 0;	  // records the ring holds (1..S2AMD_METRICS_MAX_HISTORY while metrics.flags != 0)
 	long long metricsWritten = 0; // records written since the recorder was restarted: the next record's `step`
 	DevBuf dMetricsRing;	  // metricsLength records (allocated by the setter)
+	// sensor report (sensor_report.hip; s2amd_world_set_sensors, s2amd_world_set_sensor_report: S2AMD_SENSOR_REPORT_*): the sixth of a step
+	ReportState sensorReport;
+	std::vector<s2amdSensor> hSensors; // the list as the caller set it: held across uploads, copied into the block by every prepare
+	int sensorListCapacity = 0;		   // entries of each of the three device lists a step writes
+	int sensorNowSet = 0;			   // which of the two ping-pong mask sets holds "now" of the last evaluation ("before" of the next)
+	int32_t hSensorReportHead[4] = {0, 0, 0, 0}; // {inside, entered, left, 0}: the totals over all sensors
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -821,7 +827,7 @@ int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
 // The reports behind s2amd_world_step.  Each file keeps its layout, kernels, prepare and enqueue; report_host.cpp holds the table of
-// the five in step order and what their host sides share.
+// the six in step order and what their host sides share.
 //   <x>Prepare   the report's device block for the resident world and its "before" state from the arrays just uploaded
 //   <x>Enqueue   the step's passes on the step's stream, behind stage 4 of the attempt that stands (never part of the captured graph)
 int contactReportPrepare(s2amdSolver* s);
@@ -836,6 +842,8 @@ int bodyReportPrepare(s2amdSolver* s);
 int bodyReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int metricsPrepare(s2amdSolver* s); // (restarts the recorder as well)
 int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+int sensorReportPrepare(s2amdSolver* s);
+int sensorReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 
 // report_host.cpp: the walks over the table ...
 void reportsForget(s2amdSolver* s);									 // no report is of the last step any more (a new upload)

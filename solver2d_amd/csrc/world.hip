@@ -987,7 +987,7 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	}
 	if ((rc = reportsEnqueue(s, params)) != 0)
 	{
-		return rc; // (contact, joint, shape and body report, then the step metrics: report_host.cpp)
+		return rc; // (contact, joint, shape and body report, the step metrics, then the sensor report: report_host.cpp)
 	}
 	s->activeContacts = contactsSeen.active;
 	s->stats.constraintCount = contactsSeen.active;

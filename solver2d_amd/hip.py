@@ -36,6 +36,7 @@ EXPORTS = [
     "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
     "s2amd_world_cast_shape", "s2amd_world_cast_shape_all",
     "s2amd_world_edit",
+    "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -136,6 +137,11 @@ def load(fast=False):
     L.s2amd_world_cast_shape.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_cast_shape_all.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_edit.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_set_sensors.argtypes = [vp, vp, i32]
+    L.s2amd_world_set_sensor_report.argtypes = [vp, i32, i32]
+    L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_sensor_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_sensor_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -721,6 +727,52 @@ class Solver:
     def world_metrics_history(self, expected=wire.METRICS_MAX_HISTORY):
         """wire.step_metrics_dtype records of the steps the ring still holds, oldest first, in one read."""
         return self._world_list(self._L.s2amd_world_metrics_history, wire.step_metrics_dtype, expected)
+
+    # ---- sensor report of the resident world (s2amd_world_set_sensors, s2amd_world_set_sensor_report): inside, entered, left ----
+    def world_set_sensors(self, sensors):
+        """Replaces the whole list of sensors (wire.sensor_dtype; an empty one clears it).  The list holds across uploads."""
+        sensors = np.ascontiguousarray(sensors)
+        assert sensors.dtype == wire.sensor_dtype
+        self._ck(self._L.s2amd_world_set_sensors(self._h, wire.as_ptr(sensors) if len(sensors) else None, len(sensors)))
+        self._world_sensors = len(sensors)
+
+    def world_set_sensor_report(self, flags, list_capacity=0):
+        """wire.SENSOR_REPORT_* bits: what every world_step from the next one on evaluates on the device (0: nothing, the default);
+        list_capacity sizes the device lists a step writes and never changes an answer."""
+        self._ck(self._L.s2amd_world_set_sensor_report(self._h, int(flags), int(list_capacity)))
+
+    def world_sensor_inside(self, expected=64):
+        """(offsets[sensors + 1], shapes): the shape slots inside each sensor after the last world_step, ascending per sensor.  Asked again
+        with the total the library states when it answers S2AMD_E_CAPACITY."""
+        offsets = np.zeros(getattr(self, "_world_sensors", 0) + 1, dtype=np.int32)
+        cap = max(int(expected), 1)
+        while True:
+            shapes = np.zeros(cap, dtype=np.int32)
+            n = ctypes.c_int32()
+            rc = self._L.s2amd_world_sensor_inside(self._h, wire.as_ptr(offsets), wire.as_ptr(shapes), cap, ctypes.byref(n))
+            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
+                cap = n.value
+                continue
+            self._ck(rc)
+            return offsets, shapes[: n.value].copy()
+
+    def world_sensor_events(self, expected=64):
+        """(entered, left): wire.sensor_event_dtype records of the (sensor, shape) pairs that came inside / went out in the last world_step,
+        each ascending by (sensor, shape).  Asked again with the counts the library states when it answers S2AMD_E_CAPACITY."""
+        cap_a = cap_b = max(int(expected), 1)
+        while True:
+            a, b = np.zeros(cap_a, dtype=wire.sensor_event_dtype), np.zeros(cap_b, dtype=wire.sensor_event_dtype)
+            na, nb = ctypes.c_int32(), ctypes.c_int32()
+            rc = self._L.s2amd_world_sensor_events(self._h, wire.as_ptr(a), cap_a, ctypes.byref(na), wire.as_ptr(b), cap_b, ctypes.byref(nb))
+            if rc == -5 and (na.value > cap_a or nb.value > cap_b):  # S2AMD_E_CAPACITY
+                cap_a, cap_b = max(cap_a, na.value), max(cap_b, nb.value)
+                continue
+            self._ck(rc)
+            return a[: na.value].copy(), b[: nb.value].copy()
+
+    def world_sensor_states(self, expected=None):
+        """wire.sensor_state_dtype records, one per sensor in list order, after the last world_step."""
+        return self._world_list(self._L.s2amd_world_sensor_states, wire.sensor_state_dtype, expected or getattr(self, "_world_sensors", 0))
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

@@ -239,6 +239,22 @@ proximity_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("dista
 PROXIMITY_QUERY_SIZE, PROXIMITY_HIT_SIZE = proximity_query_dtype.itemsize, proximity_hit_dtype.itemsize
 assert PROXIMITY_QUERY_SIZE == 96 and PROXIMITY_HIT_SIZE == 32
 
+# sensor report of the resident world (include/solver2d_amd.h: s2amd_world_set_sensors, s2amd_world_set_sensor_report)
+MAX_SENSORS = 1024
+SENSOR_DISABLED, SENSOR_SKIP_STATIC = 1, 2
+SENSOR_REPORT_INSIDE, SENSOR_REPORT_EVENTS, SENSOR_REPORT_STATES = 1, 2, 4
+SENSOR_REPORT_ALL = SENSOR_REPORT_INSIDE | SENSOR_REPORT_EVENTS | SENSOR_REPORT_STATES
+# s2amdSensor, s2amdSensorEvent, s2amdSensorState
+sensor_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("count", np.int32), ("radius", np.float32), ("position", np.float32, 2),
+                         ("rot", np.float32, 2), ("margin", np.float32), ("maskBits", np.uint32), ("body", np.int32), ("flags", np.int32),
+                         ("pad", np.int32, 2)])
+sensor_event_dtype = np.dtype([("sensor", np.int32), ("shape", np.int32), ("body", np.int32), ("sensorBody", np.int32)])
+sensor_state_dtype = np.dtype([("sensor", np.int32), ("body", np.int32), ("active", np.int32), ("inside", np.int32), ("entered", np.int32),
+                               ("left", np.int32), ("lowestShape", np.int32), ("pad", np.int32), ("position", np.float32, 2),
+                               ("rot", np.float32, 2), ("box", np.float32, 4)])
+SENSOR_SIZE, SENSOR_EVENT_SIZE, SENSOR_STATE_SIZE = sensor_dtype.itemsize, sensor_event_dtype.itemsize, sensor_state_dtype.itemsize
+assert SENSOR_SIZE == 112 and SENSOR_EVENT_SIZE == 16 and SENSOR_STATE_SIZE == 64
+
 # contact queries on the resident world (include/solver2d_amd.h: s2amd_world_collide_shape, s2amd_world_deepest_contact)
 # s2amdContactQuery, s2amdContactHit
 contact_query_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("normals", np.float32, (8, 2)), ("type", np.int32), ("count", np.int32),

@@ -1,0 +1,218 @@
+"""The sensor report without a GPU: the interface as declared and bound with the header's sizes and offsets, the statement
+(tests/sensor_report_ref.py) against the proximity queries' statement under the composed transform, the fixtures
+tests/golden/sensor_report/*.npz with the condition every scene must meet, the compiler's resource report of the new kernels, and the
+host side under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from solver2d_amd import hip, wire
+from tests import proximity_ref, sensor_report_ref as ref, sensor_report_world as sw, world_chain
+from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
+CALLS = ("s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states")
+f32 = np.float32
+
+
+def test_struct_sizes_and_offsets_match_the_header(tmp_path):
+    fields = {"s2amdSensor": wire.sensor_dtype, "s2amdSensorEvent": wire.sensor_event_dtype, "s2amdSensorState": wire.sensor_state_dtype}
+    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
+    want = []
+    for struct, dtype in fields.items():
+        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
+        want.append(dtype.itemsize)
+        for name in dtype.names:
+            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
+            want.append(dtype.fields[name][1])
+    lines.append("return 0;}")
+    src = tmp_path / "sz.c"
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "sz"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == want
+    assert (wire.SENSOR_SIZE, wire.SENSOR_EVENT_SIZE, wire.SENSOR_STATE_SIZE) == (112, 16, 64)
+
+
+def test_header_flags_and_bindings():
+    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
+    for call in CALLS:
+        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
+        assert call in hip.EXPORTS
+    for define in ("#define S2AMD_MAX_SENSORS 1024", "#define S2AMD_SENSOR_DISABLED 1", "#define S2AMD_SENSOR_SKIP_STATIC 2", "#define S2AMD_SENSOR_REPORT_INSIDE 1",
+                   "#define S2AMD_SENSOR_REPORT_EVENTS 2", "#define S2AMD_SENSOR_REPORT_STATES 4", "#define S2AMD_API_VERSION 5"):
+        assert define in header, define
+    assert (wire.MAX_SENSORS, wire.SENSOR_DISABLED, wire.SENSOR_SKIP_STATIC) == (1024, 1, 2)
+    assert (wire.SENSOR_REPORT_INSIDE, wire.SENSOR_REPORT_EVENTS, wire.SENSOR_REPORT_STATES, wire.SENSOR_REPORT_ALL) == (1, 2, 4, 7)
+    assert wire.API_VERSION == 5 and wire.SHAPE_REPORT_ALL == 7  # the other flag spaces and the API version are untouched
+    for method in ("world_set_sensors", "world_set_sensor_report", "world_sensor_inside", "world_sensor_events", "world_sensor_states"):
+        assert callable(getattr(hip.Solver, method))
+    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
+        for fast in (False, True):
+            lib = hip.load(fast=fast)
+            for call in CALLS:
+                assert getattr(lib, call).argtypes is not None, call
+
+
+def test_mul_transforms_is_the_reference_operation_order():
+    """s2MulTransforms restated: against float64 within rounding, and exactly where every product is exact"""
+    (x, y), (s, c) = ref.mul_transforms((1.0, 2.0), (0.0, 1.0), (0.5, -0.25), (1.0, 0.0))  # identity rotation times a quarter turn
+    assert (float(x), float(y), float(s), float(c)) == (1.5, 1.75, 1.0, 0.0)
+    (x, y), (s, c) = ref.mul_transforms((1.0, 2.0), (1.0, 0.0), (0.5, -0.25), (0.0, 1.0))  # a quarter turn: (x, y) -> (-y, x)
+    assert (float(x), float(y), float(s), float(c)) == (1.25, 2.5, 1.0, 0.0)
+    rng = np.random.RandomState(5)
+    for _ in range(50):
+        a, b = rng.rand() * 6.28, rng.rand() * 6.28
+        ap, bp = rng.rand(2) * 10 - 5, rng.rand(2) * 2 - 1
+        (x, y), (s, c) = ref.mul_transforms(f32(ap), (f32(np.sin(a)), f32(np.cos(a))), f32(bp), (f32(np.sin(b)), f32(np.cos(b))))
+        assert all(isinstance(v, np.float32) for v in (x, y, s, c))
+        assert abs(float(s) - np.sin(a + b)) < 1e-6 and abs(float(c) - np.cos(a + b)) < 1e-6
+        assert abs(float(x) - (np.cos(a) * bp[0] - np.sin(a) * bp[1] + ap[0])) < 1e-5 and abs(float(y) - (np.sin(a) * bp[0] + np.cos(a) * bp[1] + ap[1])) < 1e-5
+
+
+def test_poses_of_inactive_sensors_are_zero():
+    fx = sw.load_fixture("ball")
+    world, sensors = sw.fixture_world(fx), fx["sensors"]
+    poses = ref.poses(world, sensors)
+    assert poses["active"].tolist() == [1, 1, 1, 1, 0, 0] and poses["lowestShape"].tolist() == [-1] * 6
+    for i in (4, 5):  # DISABLED; on a free body slot
+        assert poses[i]["position"].tobytes() == bytes(8) and poses[i]["rot"].tobytes() == bytes(8) and poses[i]["box"].tobytes() == bytes(16)
+    assert poses[3]["position"].tolist() == world["origins"][1].tolist() and poses[3]["rot"].tolist() == [0.0, 1.0]
+    assert poses[0]["box"].tolist() == [f32(-0.3), f32(4.7), f32(0.3), f32(5.3)]
+
+
+@needs_reference
+@pytest.mark.parametrize("scene", sw.SCENES)
+def test_inside_lists_are_shapes_in_range_under_the_composed_transform(scene):
+    """The statement's lists equal tests/proximity_ref.shapes_in_range with {the composed transform, maxDistance = margin}, minus the
+    shapes the sensor's rule excludes, on the scene's first, fourth and last state of the chain"""
+    fx = sw.load_fixture(scene)
+    world, sensors, params = sw.fixture_world(fx), fx["sensors"], sw.params()
+    excluded_own = excluded_static = 0
+    for k in range(sw.STEPS + 1):
+        if k in (0, 4, sw.STEPS):
+            lists = ref.inside_lists(world, sensors)
+            for i, q in enumerate(sensors):
+                if not ref.is_active(world, q):
+                    assert lists[i] == []
+                    continue
+                offsets, shapes, _ = proximity_ref.shapes_in_range(world, np.array([ref.as_query(world, q)], dtype=wire.proximity_query_dtype))
+                body_of = world["shapes"]["body"]
+                own = [int(x) for x in shapes if body_of[x] == q["body"]]
+                static = [int(x) for x in shapes if (int(q["flags"]) & wire.SENSOR_SKIP_STATIC) and world["bodies"]["type"][body_of[x]] == wire.BODY_STATIC]
+                excluded_own += len(own)
+                excluded_static += len([x for x in static if x not in own])
+                assert lists[i] == [int(x) for x in shapes if int(x) not in own and int(x) not in static], (scene, k, i)
+        if k < sw.STEPS:
+            world_chain.oracle_world_step(params, world)
+    assert excluded_own >= 1, scene  # a sensor on a body whose own shape lies inside it
+    if scene == "pyramid":
+        assert excluded_static >= 1
+
+
+@needs_reference
+@pytest.mark.parametrize("scene", sw.SCENES)
+def test_recorded_fixtures_equal_the_statement(scene):
+    fx = sw.load_fixture(scene)
+    built = sw.build_fixture(scene)
+    assert sorted(built) == sorted(fx)
+    for key in built:
+        assert np.ascontiguousarray(built[key]).tobytes() == fx[key].tobytes(), (scene, key)
+
+
+@pytest.mark.parametrize("scene", sw.SCENES)
+def test_every_scene_meets_the_condition(scene):
+    """By the recorded statement alone: at least one entered and one left event, a non-empty inside list for a fixed and for an
+    attached sensor, a step with no event at all; the events summed over the steps reproduce the last lists from the first "before";
+    the states' counts are those of the lists."""
+    fx = sw.load_fixture(scene)
+    sw.assert_condition(fx, scene)
+    sensors = fx["sensors"]
+    assert (sensors["body"] < 0).any() and (sensors["body"] >= 0).any()
+    lists = [set(x) for x in sw.fixture_lists(fx, "before")]
+    for k in range(sw.STEPS):
+        for e in fx["left_%d" % k]:
+            lists[int(e["sensor"])].remove(int(e["shape"]))
+        for e in fx["entered_%d" % k]:
+            assert int(e["shape"]) not in lists[int(e["sensor"])]
+            lists[int(e["sensor"])].add(int(e["shape"]))
+            assert int(e["body"]) == int(fx["shapes"]["body"][e["shape"]]) and int(e["sensorBody"]) == int(sensors["body"][e["sensor"]])
+        now = sw.fixture_lists(fx, "inside", k)
+        assert [sorted(x) for x in lists] == now
+        states = fx["states_%d" % k]
+        assert states["inside"].tolist() == [len(x) for x in now] and states["lowestShape"].tolist() == [min(x) if x else -1 for x in now]
+        assert int(states["entered"].sum()) == len(fx["entered_%d" % k]) and int(states["left"].sum()) == len(fx["left_%d" % k])
+        for name in ("entered", "left"):
+            pairs = [(int(e["sensor"]), int(e["shape"])) for e in fx["%s_%d" % (name, k)]]
+            assert pairs == sorted(pairs)
+    if scene == "ball":
+        assert (sensors["flags"] & wire.SENSOR_DISABLED).any()
+        # the ball's own shape lies inside its pick-up radius and is never held
+        ball = int(np.flatnonzero(fx["shapes"]["body"] == 1)[0])
+        assert all(ball not in sw.fixture_lists(fx, "inside", k)[3] for k in range(sw.STEPS))
+    if scene == "pyramid":
+        # SKIP_STATIC: the post is held by the sensor without the flag only
+        post = len(fx["shapes"]) - 1
+        assert all(post in sw.fixture_lists(fx, "inside", k)[3] and post not in sw.fixture_lists(fx, "inside", k)[1] for k in range(sw.STEPS))
+
+
+def test_sweep_world_is_what_it_says():
+    for slots in (63, 257, 513):
+        world = sw.sweep_world(slots)
+        shapes, bodies = world["shapes"], world["bodies"]
+        live = shapes["type"] != wire.SHAPE_FREE
+        assert len(shapes) == slots and live[0] and (~live).sum() >= 5 and bodies["type"][-1] == wire.BODY_FREE and bodies["type"][0] == wire.BODY_STATIC
+        assert set(shapes["type"][live].tolist()) == {0, 1, 2, 3}
+        sensors = sw.sweep_sensors(world, 1024)
+        assert len(sensors) == 1024 and len({q.tobytes() for q in sensors}) == 7
+        assert (sensors["flags"] & wire.SENSOR_DISABLED).any() and (sensors["flags"] & wire.SENSOR_SKIP_STATIC).any()
+        assert np.isfinite(shapes["fatAABB"][live]).all() and (shapes["fatAABB"][live][:, 2] > shapes["fatAABB"][live][:, 0]).all()
+
+
+def test_kernels_use_no_scratch():
+    """hipcc's own report for sensor_report.hip (make resources-sensor-report), through tools/kernel_resources.py: every kernel of the
+    file is there, none has a private frame or spills, and 48 KiB of LDS a workgroup leave the mask pass three workgroups a CU."""
+    sys.path.insert(0, ROOT)
+    from tools import kernel_resources
+    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
+    subprocess.check_call(["make", "-s", "-C", csrc, "resources-sensor-report"])
+    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_sensor_report.txt"))
+    for kernel in ("sensorPoseKernel", "sensorMaskKernelILb0E", "sensorMaskKernelILb1E", "sensorPrefixKernel", "sensorOffsetsKernel", "sensorWriteKernel",
+                   "listTilePrefixKernel", "listOffsetsKernel", "listWriteKernel"):
+        found = [r for r in rows if kernel in r["mangled"]]
+        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
+        r = found[0]
+        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
+        assert r["Occupancy"] >= 3, r
+        if "sensorMaskKernel" in kernel:
+            assert r["VGPRs"] <= 128, r
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+def test_sensor_report_host_code_under_asan_and_ubsan(tmp_path):
+    """The setter with good and bad lists -> every flag combination 0..7 with listCapacity 0, 16 and ample -> every getter with
+    too-small, exact and ample heap buffers of exactly the size passed, lists in the block and rebuilt by the getter -> the list replaced
+    and cleared between steps -> uploads with other capacities, worlds without shape slots among them -> destroy, for 0, 1, 257 and
+    1,024 sensors, on the sanitizer build of tests/test_hostcheck.py (kernels never run there: the program writes the head through the
+    report state's head offset, and what is checked is that the host code touches only memory it owns)."""
+    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
+    build = os.path.join(HOSTCHECK, "_build")
+    exe = str(tmp_path / "sensor_report_main")
+    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
+                           "-x", "hip", os.path.join(HOSTCHECK, "sensor_report_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
+                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
+    env = dict(os.environ)
+    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
+    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
+    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0 and "SENSOR REPORT MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
