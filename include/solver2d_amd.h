@@ -1132,6 +1132,94 @@ typedef struct s2amdWorldEdit /* 32 bytes */
 } s2amdWorldEdit;
 int s2amd_world_edit(s2amdSolver* solver, const s2amdWorldEdit* edits, int32_t count, int32_t* skipped /* may be NULL */);
 
+/* (additive, API 5) Force fields: a write addressed by region instead of by slot -- "everything within 3 m of this point gets an impulse
+ * away from it", "whatever is inside this box feels wind", "the ball carries a magnet", "this pool slows what is in it".  A field is a
+ * region (a proxy with a reach, fixed in the world or attached to a body, as a sensor's) and a rule that turns every shape of a dynamic
+ * body within reach into one term: an APPLY_FORCE_TO_CENTER or an APPLY_LINEAR_IMPULSE of s2amd_world_edit on the shape's body.  Two
+ * entry points share their kernels: s2amd_world_apply_fields applies a list once, enqueued like an edit; s2amd_world_set_fields keeps a
+ * list that the head of every s2amd_world_step applies.  Nothing is downloaded and the structure is kept, as with an edit.  LIVE and
+ * xf(body) are the scene queries' definitions; D is the proximity queries' D(q, s) with transformA = the field's transform: empty cache,
+ * useRadii, the FLT_EPSILON branch included.
+ *   Active        the sensor report's rule: not S2AMD_FIELD_DISABLED, and body < 0 or (body < bodyCapacity and bodies[body].type !=
+ *                 S2AMD_BODY_FREE).  An inactive field yields no terms; its state has active = 0, transform and box +0, lowestShape = -1.
+ *   Transform T   the sensor report's: body < 0: {position, rot}; otherwise s2MulTransforms(xf(body), {position, rot}).  The centre
+ *                 is c = T.p.
+ *   Box           the sensor report's with `margin` read as `range`: the proximity queries' query box of {vertices, count, radius}
+ *                 under T with maxDistance = range.
+ *   Candidates    live; (categoryBits & maskBits) != 0; s2AABB_Overlaps(fatAABB, box); shape.body != field.body;
+ *                 bodies[shape.body].type == S2AMD_BODY_DYNAMIC.  No other pruning decides a result.
+ *   Term (f, s)   a candidate with D.distance <= range.  scale = 1.0f - D.distance / range (one correctly rounded divide, one
+ *                 subtract) when S2AMD_FIELD_LINEAR_FALLOFF is set and range > 0, else 1.0f; m = strength * scale (one multiply);
+ *                   RADIAL   g = s2MulSV(m, s2Normalize(s2Sub(D.pointB, c))), s2Normalize as src/math.c:41-52 with its zero-vector
+ *                            branch: a centre on pointB gives g = 0 and the term is still applied
+ *                   UNIFORM  g = s2MulSV(m, direction)
+ *                   DRAG     g = s2MulSV(-m, linearVelocity), read from the body record as the earlier terms of this call left it
+ *                 Without S2AMD_FIELD_AS_IMPULSE the term is APPLY_FORCE_TO_CENTER(shape.body, g); with it APPLY_LINEAR_IMPULSE(
+ *                 shape.body, g, point), point = D.pointB for RADIAL and bodies[shape.body].position for the other two kinds -- both
+ *                 exactly as s2amd_world_edit defines them.
+ *   Result        the resident `bodies` after the call are what applying every term one after another gives, ascending by field index
+ *                 and inside a field ascending by shape slot.  No term changes a pose, so every D, T and box is that of the world as
+ *                 the call found it.  Terms on different bodies commute; only the order of the terms on one body matters, to the bit.
+ *                 A body with no term keeps its bytes; a term of zero magnitude is still applied.  Every other array is untouched byte
+ *                 for byte.  All arithmetic is fp32 in the reference's operation order without contraction, in libs2amd.so and in
+ *                 libs2amd_fast.so alike; no float atomics take part: one lane sums a body's terms in the stated order.
+ *   States        one record per field in list order: terms = the number of the field's terms, lowestShape = the lowest shape slot
+ *                 among them or -1, the transform and the box used.  With states == NULL s2amd_world_apply_fields reads nothing back
+ *                 and does not wait; with a pointer it waits for the stream once.
+ *   Validation    on the host, before anything is enqueued or replaced: 0 <= count <= S2AMD_MAX_FIELDS and a non-NULL list when
+ *                 count > 0; per field the sensors' checks (1 <= count <= 8; vertices[0 .. count), radius, position and rot finite;
+ *                 radius >= 0; body < bodyCapacity of the resident world -- with no world resident, body is not bounded), kind in
+ *                 1..3, no flag bits beyond the four below, reserved == 0, strength, direction and range finite, range >= 0.  One bad
+ *                 record refuses the whole list with S2AMD_E_INVALID, and the world and the old list stand.  S2AMD_E_STATE without a
+ *                 resident world for s2amd_world_apply_fields and s2amd_world_field_states; s2amd_world_set_fields is accepted before
+ *                 any world and the list holds across uploads, as the sensors do (a field whose body is outside the new world's
+ *                 bodyCapacity is inactive there).
+ *   Ordering      s2amd_world_apply_fields is enqueued on the stream s2amd_world_step uses, like an edit; the caller may reuse
+ *                 `fields` as soon as it returns.  A non-empty persistent list is applied once per s2amd_world_step call, in front of
+ *                 stage 3 -- outside the loop that repeats a step the library has to run again, so a repeated step applies it once --
+ *                 and the effect is what s2amd_world_apply_fields(list) immediately before the step would give.  Forces are consumed by
+ *                 that step's stage 4.  s2amd_world_field_states returns the states of the last step's application (S2AMD_E_CAPACITY
+ *                 with *count filled when capacity is less): S2AMD_E_STATE if no step ran since the list was set or since the last
+ *                 upload, *count = 0 with an empty list.  With an empty list a step enqueues nothing and allocates nothing.  The first
+ *                 use of fields after an upload builds a body -> shapes list on the device (a stable radix sort; no host sort, no wait).
+ * The reference has no fields: the composition is ours; every distance is the reference's s2ShapeDistance and every term the
+ * reference's setter, bit for bit.  Not offered: torque (the reference has no setter for it); fields that act on kinematic or static
+ * bodies; sharded worlds; lists in device memory; the drop-in routed through this call; the device trees as an accelerator (a field
+ * looks at every shape of every dynamic body, and a body with hundreds of shapes is walked by one lane: correct, not fast). */
+#define S2AMD_MAX_FIELDS 1024
+#define S2AMD_FIELD_RADIAL 1  /* along s2Normalize(pointB - centre) */
+#define S2AMD_FIELD_UNIFORM 2 /* along `direction` */
+#define S2AMD_FIELD_DRAG 3	  /* against the body's linear velocity as it stands */
+#define S2AMD_FIELD_DISABLED 1
+#define S2AMD_FIELD_AS_IMPULSE 2	 /* the term is an APPLY_LINEAR_IMPULSE instead of an APPLY_FORCE_TO_CENTER */
+#define S2AMD_FIELD_LINEAR_FALLOFF 4 /* scale = 1 - distance / range instead of 1 */
+typedef struct s2amdField /* 128 bytes */
+{
+	float vertices[8][2]; /* the region's proxy in its own frame, as s2amdSensor's */
+	int32_t count;		  /* 1..8 */
+	float radius;		  /* >= 0 */
+	float position[2];	  /* the frame: in the world (body < 0) or relative to the body */
+	float rot[2];		  /* {s, c} */
+	float range;		  /* reach beyond the proxy: acts where D.distance <= range; >= 0, finite */
+	uint32_t maskBits;
+	int32_t body;		/* < 0: fixed in the world */
+	int32_t kind;		/* S2AMD_FIELD_RADIAL, _UNIFORM, _DRAG */
+	int32_t flags;		/* S2AMD_FIELD_DISABLED, _AS_IMPULSE, _LINEAR_FALLOFF */
+	float strength;		/* finite, either sign (a negative RADIAL pulls) */
+	float direction[2]; /* UNIFORM only; finite, not normalised by the library */
+	int32_t reserved;	/* 0 */
+	int32_t pad;		/* (fills the record to 128 bytes; not read) */
+} s2amdField;
+typedef struct s2amdFieldState /* 64 bytes */
+{
+	int32_t field, body, active, terms, lowestShape, pad[3];
+	float position[2], rot[2]; /* the world transform used */
+	float box[4];			   /* the candidate box used */
+} s2amdFieldState;
+int s2amd_world_apply_fields(s2amdSolver* solver, const s2amdField* fields, int32_t count, s2amdFieldState* states /* [count], may be NULL */);
+int s2amd_world_set_fields(s2amdSolver* solver, const s2amdField* fields, int32_t count); /* replaces the whole list; count 0 clears */
+int s2amd_world_field_states(s2amdSolver* solver, s2amdFieldState* out, int32_t capacity, int32_t* count);
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free

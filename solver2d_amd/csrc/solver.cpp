@@ -282,6 +282,7 @@ void s2amd_destroy(s2amdSolver* s)
 		b->release();
 	}
 	reportsRelease(s);
+	fieldsRelease(s);
 	treesFree(s);
 	if (s->hostError)
 	{

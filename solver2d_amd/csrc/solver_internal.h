@@ -587,6 +587,18 @@ struct SolverRest
 	int sensorListCapacity = 0;		   // entries of each of the three device lists a step writes
 	int sensorNowSet = 0;			   // which of the two ping-pong mask sets holds "now" of the last evaluation ("before" of the next)
 	int32_t hSensorReportHead[4] = {0, 0, 0, 0}; // {inside, entered, left, 0}: the totals over all sensors
+	// force fields (force_field.hip; s2amd_world_apply_fields, s2amd_world_set_fields, s2amd_world_field_states): no report -- a write in
+	// front of stage 3 -- but kept and released beside them
+	std::vector<s2amdField> hFields; // the persistent list as the caller set it: held across uploads
+	DevBuf dFieldList;				 // ... its device block {the list, the prepared records, the states}, written by the setter
+	DevBuf dFieldCall;				 // the same block for one s2amd_world_apply_fields call; grows on demand, kept between calls
+	DevBuf dFieldAdj;				 // the body -> shapes list {ranges, shapes ascending per body, the sort's keys and scratch} ...
+	bool fieldAdjValid = false;		 // ... built at the first field use after an upload (s2amd_world_upload clears this)
+	long fieldAdjBuilds = 0;		 // how often it was built, since s2amd_create
+	bool fieldStatesValid = false;	 // a step has applied the persistent list since it was set and since the last upload
+	char* hostFieldStage = nullptr;	 // the pinned copy of a one-shot call's list the device copy reads, and the event of that copy
+	size_t hostFieldStageBytes = 0;
+	hipEvent_t evFieldStaged = nullptr;
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -844,6 +856,10 @@ int metricsPrepare(s2amdSolver* s); // (restarts the recorder as well)
 int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int sensorReportPrepare(s2amdSolver* s);
 int sensorReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+// force_field.hip: the persistent list in front of stage 3 (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
+int fieldsStepEnqueue(s2amdSolver* s);
+void fieldsForgetWorld(s2amdSolver* s);
+void fieldsRelease(s2amdSolver* s);
 
 // report_host.cpp: the walks over the table ...
 void reportsForget(s2amdSolver* s);									 // no report is of the last step any more (a new upload)

@@ -534,6 +534,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	}
 	s->worldResident = false;
 	reportsForget(s);
+	fieldsForgetWorld(s); // (the body -> shapes list of the force fields belongs to the world it was built for: force_field.hip)
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
 	s->gatherIndexDirty = true;
@@ -731,6 +732,16 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	// behind it saw the bodies of the previous step (same AABBs, nothing enlarged): the solve is repeated on the
 	// multi-launch path, and so is the refit.
 	s->slotBytesFresh = false;
+	// the persistent force fields (force_field.hip; s2amd_world_set_fields), once per call: in front of stage 3 and outside the loop below
+	// that repeats a solve, whose dead hand-off leaves the wire arrays -- these writes among them -- as they were.  Nothing with no list.
+	if (!s->hFields.empty())
+	{
+		int rcFields = fieldsStepEnqueue(s);
+		if (rcFields)
+		{
+			return rcFields;
+		}
+	}
 	// stage 2 (src/world.c:130): the trees the last refit flagged are rebuilt -- after the pair query of this step's stage 1, which the
 	// caller has run (or the last step enqueued behind its stage 4), before this step's refit flags them again
 	launchTreeRebuild(s, st);

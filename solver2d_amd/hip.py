@@ -35,7 +35,7 @@ EXPORTS = [
     "s2amd_world_closest_shape", "s2amd_world_shapes_in_range",
     "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
     "s2amd_world_cast_shape", "s2amd_world_cast_shape_all",
-    "s2amd_world_edit",
+    "s2amd_world_edit", "s2amd_world_apply_fields", "s2amd_world_set_fields", "s2amd_world_field_states",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
@@ -137,6 +137,9 @@ def load(fast=False):
     L.s2amd_world_cast_shape.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_cast_shape_all.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_edit.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_apply_fields.argtypes = [vp, vp, i32, vp]
+    L.s2amd_world_set_fields.argtypes = [vp, vp, i32]
+    L.s2amd_world_field_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_set_sensors.argtypes = [vp, vp, i32]
     L.s2amd_world_set_sensor_report.argtypes = [vp, i32, i32]
     L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -580,6 +583,30 @@ class Solver:
         skipped = ctypes.c_int32(-1)
         self._ck(self._L.s2amd_world_edit(self._h, wire.as_ptr(edits), len(edits), ctypes.byref(skipped) if want_skipped else None))
         return skipped.value if want_skipped else None
+
+    # ---- force fields on the resident world (s2amd_world_apply_fields, s2amd_world_set_fields): writes addressed by region ----
+    def world_apply_fields(self, fields, want_states=True):
+        """Applies wire.field_dtype records (wire.field_*) to the resident bodies once, in list order, behind the last step and before
+        the next.  Returns one wire.field_state_dtype record per field; with want_states=False the call only enqueues, reads nothing
+        back and returns None."""
+        fields = np.ascontiguousarray(fields)
+        assert fields.dtype == wire.field_dtype
+        states = np.zeros(len(fields), dtype=wire.field_state_dtype) if want_states else None
+        self._ck(self._L.s2amd_world_apply_fields(self._h, wire.as_ptr(fields) if len(fields) else None, len(fields),
+                                                  wire.as_ptr(states) if want_states and len(fields) else None))
+        return states
+
+    def world_set_fields(self, fields):
+        """Replaces the whole persistent list (wire.field_dtype; an empty one clears it): every world_step applies it in front of its
+        stage 3.  The list holds across uploads."""
+        fields = np.ascontiguousarray(fields)
+        assert fields.dtype == wire.field_dtype
+        self._ck(self._L.s2amd_world_set_fields(self._h, wire.as_ptr(fields) if len(fields) else None, len(fields)))
+        self._world_fields = len(fields)
+
+    def world_field_states(self):
+        """wire.field_state_dtype records, one per field of the persistent list, of the last world_step's application."""
+        return self._world_list(self._L.s2amd_world_field_states, wire.field_state_dtype, getattr(self, "_world_fields", 0))
 
     # ---- the reports of the resident world: the three shapes their getters have ----
     def _world_list(self, fn, dtype, expected):

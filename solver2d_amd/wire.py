@@ -327,3 +327,44 @@ def edit_revolute_set_motor_speed(joint, speed):
 def edit_list(edits):
     """A list of the records above (or an array of them) as one contiguous wire.world_edit_dtype array."""
     return np.ascontiguousarray(np.array(list(edits), dtype=world_edit_dtype)) if len(edits) else np.zeros(0, dtype=world_edit_dtype)
+
+
+# force fields on the resident world (include/solver2d_amd.h: s2amd_world_apply_fields, s2amd_world_set_fields, s2amd_world_field_states)
+MAX_FIELDS = 1024
+FIELD_RADIAL, FIELD_UNIFORM, FIELD_DRAG = 1, 2, 3
+FIELD_DISABLED, FIELD_AS_IMPULSE, FIELD_LINEAR_FALLOFF = 1, 2, 4
+# s2amdField, s2amdFieldState
+field_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("count", np.int32), ("radius", np.float32), ("position", np.float32, 2),
+                        ("rot", np.float32, 2), ("range", np.float32), ("maskBits", np.uint32), ("body", np.int32), ("kind", np.int32),
+                        ("flags", np.int32), ("strength", np.float32), ("direction", np.float32, 2), ("reserved", np.int32), ("pad", np.int32)])
+field_state_dtype = np.dtype([("field", np.int32), ("body", np.int32), ("active", np.int32), ("terms", np.int32), ("lowestShape", np.int32),
+                              ("pad", np.int32, 3), ("position", np.float32, 2), ("rot", np.float32, 2), ("box", np.float32, 4)])
+FIELD_SIZE, FIELD_STATE_SIZE = field_dtype.itemsize, field_state_dtype.itemsize
+assert FIELD_SIZE == 128 and FIELD_STATE_SIZE == 64
+
+
+def field(kind, position, range_, strength, flags=0, body=-1, direction=(0.0, 0.0), vertices=((0.0, 0.0),), radius=0.0, rot=(0.0, 1.0),
+          mask=0xFFFFFFFF):
+    """One wire.field_dtype record: a region (by default a point) at `position` that reaches `range_` beyond its proxy."""
+    f = np.zeros(1, dtype=field_dtype)[0]
+    f["vertices"][:len(vertices)] = vertices
+    f["count"], f["radius"], f["position"], f["rot"], f["range"] = len(vertices), radius, position, rot, range_
+    f["maskBits"], f["body"], f["kind"], f["flags"], f["strength"], f["direction"] = mask, body, kind, flags, strength, direction
+    return f
+
+
+def field_radial(position, range_, strength, **kw):
+    return field(FIELD_RADIAL, position, range_, strength, **kw)
+
+
+def field_uniform(position, range_, strength, direction, **kw):
+    return field(FIELD_UNIFORM, position, range_, strength, direction=direction, **kw)
+
+
+def field_drag(position, range_, strength, **kw):
+    return field(FIELD_DRAG, position, range_, strength, **kw)
+
+
+def field_list(fields):
+    """A list of the records above (or an array of them) as one contiguous wire.field_dtype array."""
+    return np.ascontiguousarray(np.array(list(fields), dtype=field_dtype)) if len(fields) else np.zeros(0, dtype=field_dtype)
