@@ -24,6 +24,10 @@
 //                                    the lowest slot, whatever the launch geometry.
 //   contactDeepestKernel             one lane per query: the winner's manifold again and the record.
 //
+// The host side is query_host.h's ("The query facility"): deepest contact is a queryBest, collide shape a queryLists of
+// 80-byte records; contactKind names what is staged behind the upload -- the shape records and the frames, by contactStageKernel -- and
+// this file supplies the launches of its kernels.
+//
 // All arithmetic is fp32 in the reference's operation order (manifold_ops.h, gjk_ops.h); this file is compiled without contraction in
 // both libraries (Makefile).
 #include "solver_internal.h"
@@ -31,6 +35,7 @@
 #include "refit_ops.h" // (before gjk_ops.h: its transform type is the global one, the query files' own lives in their unnamed namespace)
 
 #include "query_list.h"
+#include "query_host.h"
 
 #define S2_NP_BLOCK S2_BLOCK
 #define S2_NP_SPECULATIVE (4.0f * S2_LINEAR_SLOP) // constants.h:8
@@ -38,7 +43,6 @@
 #include "manifold_ops.h"
 
 #include <cmath>
-#include <cstring>
 
 namespace
 {
@@ -46,7 +50,6 @@ namespace
 static_assert(sizeof(s2amdContactQuery) == 160 && sizeof(s2amdContactHit) == 80, "the query records");
 static_assert(sizeof(s2amdShape) == 196, "the shape record");
 
-#define S2_NO_CONTACT_KEY 0xffffffffffffffffull
 #define S2_CQ_LDS (4 * S2_NP_MAX_VERTS * S2_BLOCK) // vertsA, normsA, vertsB, normsB: one column per lane, 64 KiB
 
 // s_registers[query type][shape type].primary (src/contact.c:143-151) as 16 bits, bit = 4 * query type + shape type: capsule x
@@ -333,7 +336,7 @@ __global__ __launch_bounds__(S2_BLOCK) void contactDeepestKernel(const s2amdShap
 		return;
 	}
 	const unsigned long long key = keys[i];
-	const int slot = key == S2_NO_CONTACT_KEY ? -1 : (int)(uint32_t)(key & 0xffffffffull);
+	const int slot = keySlot(key);
 	recordOf(shapes, n, bodies, origins, nb, staged + i, frameOf(frames[i]), slot, lds, hits + i);
 }
 
@@ -348,19 +351,7 @@ __global__ __launch_bounds__(S2_BLOCK) void contactRecordsKernel(const s2amdShap
 	{
 		return;
 	}
-	int lo = 0, hi = count; // offsets[lo] <= e < offsets[hi]
-	while (hi - lo > 1)
-	{
-		const int mid = lo + (hi - lo) / 2;
-		if (offsets[mid] <= e)
-		{
-			lo = mid;
-		}
-		else
-		{
-			hi = mid;
-		}
-	}
+	const int lo = entryQuery(offsets, count, e);
 	recordOf(shapes, n, bodies, origins, nb, staged + lo, frameOf(frames[lo]), entries[e], lds, hits + e);
 }
 
@@ -369,8 +360,9 @@ bool finite2(const float* v)
 	return std::isfinite(v[0]) && std::isfinite(v[1]);
 }
 
-bool validQuery(const s2amdContactQuery& q)
+bool validQuery(const void* record)
 {
+	const s2amdContactQuery& q = *(const s2amdContactQuery*)record;
 	if (q.type != S2AMD_SHAPE_CAPSULE && q.type != S2AMD_SHAPE_CIRCLE && q.type != S2AMD_SHAPE_POLYGON && q.type != S2AMD_SHAPE_SEGMENT)
 	{
 		return false;
@@ -392,51 +384,38 @@ bool validQuery(const s2amdContactQuery& q)
 	return ok;
 }
 
-// what both calls check before anything is enqueued; *proceed is false when the call has already been answered
-int openCall(s2amdSolver* s, const s2amdContactQuery* queries, int32_t count, bool* proceed)
+// ---- the launches query_host.h's drivers ask for ----
+// staged behind the upload: the queries' shape records (staged[0]) and their frames (staged[1])
+void launchStage(const QueryCall& c)
 {
-	*proceed = false;
-	if (int rc = queryState(s))
-	{
-		return rc;
-	}
-	if (count == 0)
-	{
-		return S2AMD_OK;
-	}
-	if (count > S2_QUERY_MAX_COUNT)
-	{
-		return fail(S2AMD_E_INVALID, "more queries than one call takes: split the batch");
-	}
-	for (int32_t i = 0; i < count; ++i)
-	{
-		if (!validQuery(queries[i]))
-		{
-			return fail(S2AMD_E_INVALID, "contact query " + std::to_string(i) +
-											 " is invalid (a type outside the four, a polygon count outside 3..8, a NaN or infinite field, a negative radius)");
-		}
-	}
-	*proceed = true;
-	return S2AMD_OK;
+	contactStageKernel<<<gridFor((size_t)c.count), dim3(S2_BLOCK), 0, c.stream>>>((const s2amdContactQuery*)c.records, c.count, (s2amdShape*)c.staged[0], (float4*)c.staged[1]);
 }
 
-// where the staged queries of a call lie in dQuery: {the caller's records, their shape records, their frames}
-struct StagedAt
+template <bool LIST> void launchCandidates(const QueryCall& c, unsigned long long* out)
 {
-	size_t in, shapes, frames;
-};
-
-StagedAt layStaged(size_t* at, int32_t count)
-{
-	StagedAt a;
-	a.in = *at;
-	*at += roundUp((size_t)count * sizeof(s2amdContactQuery));
-	a.shapes = *at;
-	*at += roundUp((size_t)count * sizeof(s2amdShape));
-	a.frames = *at;
-	*at += roundUp((size_t)count * sizeof(float4));
-	return a;
+	contactCandidatesKernel<LIST><<<c.grid, dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.tiles, c.bodies, c.origins, c.nb, (const s2amdShape*)c.staged[0],
+																			(const float4*)c.staged[1], c.count, out);
 }
+
+void launchDeepest(const QueryCall& c, const unsigned long long* keys, void* hits)
+{
+	contactDeepestKernel<<<gridFor((size_t)c.count), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdShape*)c.staged[0],
+																					 (const float4*)c.staged[1], c.count, keys, (HitRecord*)hits);
+}
+
+void launchRecords(const QueryCall& c, const int* offsets, const int32_t* slots, int capacity, void* hits)
+{
+	contactRecordsKernel<<<gridFor((size_t)capacity), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdShape*)c.staged[0],
+																					  (const float4*)c.staged[1], c.count, offsets, slots, capacity, (HitRecord*)hits);
+}
+
+const QueryKind contactKind = {sizeof(s2amdContactQuery),
+							   "queries",
+							   validQuery,
+							   "contact query",
+							   "is invalid (a type outside the four, a polygon count outside 3..8, a NaN or infinite field, a negative radius)",
+							   {sizeof(s2amdShape), sizeof(float4)},
+							   launchStage};
 
 } // namespace
 
@@ -446,140 +425,13 @@ extern "C"
 
 int s2amd_world_deepest_contact(s2amdSolver* s, const s2amdContactQuery* queries, int32_t count, s2amdContactHit* hits)
 {
-	if (!s || count < 0 || (count > 0 && (!queries || !hits)))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	bool proceed;
-	if (int rc = openCall(s, queries, count, &proceed))
-	{
-		return rc;
-	}
-	if (!proceed)
-	{
-		return S2AMD_OK;
-	}
-	const int ns = s->shapeCapacity;
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	size_t at = 0;
-	const StagedAt in = layStaged(&at, count);
-	const size_t keysAt = at;
-	at += roundUp((size_t)count * sizeof(unsigned long long));
-	const size_t hitsAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdContactHit));
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	s2amdShape* staged = (s2amdShape*)(base + in.shapes);
-	float4* frames = (float4*)(base + in.frames);
-	unsigned long long* keys = (unsigned long long*)(base + keysAt);
-	HIP_TRY(hipMemcpyAsync(base + in.in, queries, (size_t)count * sizeof(s2amdContactQuery), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)count * sizeof(unsigned long long), st));
-	contactStageKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>((const s2amdContactQuery*)(base + in.in), count, staged, frames);
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	if (tiles > 0)
-	{
-		contactCandidatesKernel<false><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>(
-			(const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, s->bodyCapacity, staged, frames, count, keys);
-	}
-	contactDeepestKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																			 s->bodyCapacity, staged, frames, count, keys, (HitRecord*)(base + hitsAt));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(hits, base + hitsAt, (size_t)count * sizeof(s2amdContactHit), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	return S2AMD_OK;
+	return queryBest(s, contactKind, queries, count, hits, sizeof(s2amdContactHit), launchCandidates<false>, launchDeepest);
 }
 
-// upload, the staging, the mask pass, query_list.h's three, the records; the offsets come back, then the records they count
 int s2amd_world_collide_shape(s2amdSolver* s, const s2amdContactQuery* queries, int32_t count, int32_t* offsets, s2amdContactHit* hits, int32_t capacity, int32_t* total)
 {
-	if (!s || count < 0 || capacity < 0 || !total || (count > 0 && (!queries || !offsets)) || (capacity > 0 && !hits))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	bool proceed;
-	if (int rc = openCall(s, queries, count, &proceed))
-	{
-		return rc;
-	}
-	if (!proceed)
-	{
-		return S2AMD_OK;
-	}
-	const int ns = s->shapeCapacity;
-	if (ns <= 0)
-	{
-		std::memset(offsets, 0, ((size_t)count + 1) * sizeof(int32_t));
-		*total = 0;
-		return S2AMD_OK;
-	}
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	const size_t words = (size_t)count * tiles * 4;
-	if ((size_t)count * (size_t)ns > (size_t)INT32_MAX)
-	{
-		return fail(S2AMD_E_INVALID, "queries x shape slots beyond 2^31: split the batch");
-	}
-	// no list is longer than the shape slots, nor all together than the caller's capacity
-	const size_t entries = std::min((size_t)capacity, (size_t)count * (size_t)ns);
-	size_t at = 0;
-	const StagedAt in = layStaged(&at, count);
-	const size_t masksAt = at;
-	at += roundUp(words * sizeof(unsigned long long));
-	const size_t prefixAt = at;
-	at += roundUp((size_t)count * tiles * sizeof(int));
-	const size_t totalsAt = at;
-	at += roundUp((size_t)count * sizeof(int));
-	const size_t slotsAt = at;
-	at += roundUp(entries * sizeof(int32_t));
-	const size_t outAt = at; // {offsets[count + 1], padding to 16 bytes, records}
-	const size_t recordsIn = (((size_t)count + 1) * sizeof(int32_t) + 15) & ~size_t(15);
-	const size_t outBytes = recordsIn + entries * sizeof(s2amdContactHit);
-	at += roundUp(outBytes);
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	s2amdShape* staged = (s2amdShape*)(base + in.shapes);
-	float4* frames = (float4*)(base + in.frames);
-	HIP_TRY(hipMemcpyAsync(base + in.in, queries, (size_t)count * sizeof(s2amdContactQuery), hipMemcpyHostToDevice, st));
-	contactStageKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>((const s2amdContactQuery*)(base + in.in), count, staged, frames);
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	unsigned long long* masks = (unsigned long long*)(base + masksAt);
-	int* dOffsets = (int*)(base + outAt);
-	int32_t* dSlots = (int32_t*)(base + slotsAt);
-	contactCandidatesKernel<true><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>(
-		(const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, s->bodyCapacity, staged, frames, count, masks);
-	listTilePrefixKernel<<<dim3((unsigned)((count + 3) / 4)), dim3(S2_BLOCK), 0, st>>>(masks, count, tiles, (int*)(base + prefixAt), (int*)(base + totalsAt));
-	listOffsetsKernel<<<dim3(1), dim3(64), 0, st>>>((const int*)(base + totalsAt), count, dOffsets);
-	listWriteKernel<<<gridFor(words), dim3(S2_BLOCK), 0, st>>>(masks, words, tiles, (const int*)(base + prefixAt), dOffsets, dSlots, (int)entries);
-	if (entries > 0)
-	{
-		contactRecordsKernel<<<gridFor(entries), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																		   s->bodyCapacity, staged, frames, count, dOffsets, dSlots, (int)entries,
-																		   (HitRecord*)(base + outAt + recordsIn));
-	}
-	HIP_TRY(hipGetLastError());
-	// the offsets first: a record is 80 bytes, and only offsets[count] of the `entries` the caller has room for exist
-	HIP_TRY(hipMemcpyAsync(offsets, base + outAt, ((size_t)count + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	*total = offsets[count];
-	if (*total > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "collide-shape buffer too small");
-	}
-	if (*total > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(hits, base + outAt + recordsIn, (size_t)*total * sizeof(s2amdContactHit), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-	}
-	return S2AMD_OK;
+	const QueryPayload records = {sizeof(s2amdContactHit), "collide-shape buffer too small", launchRecords};
+	return queryLists(s, contactKind, queries, count, offsets, hits, nullptr, capacity, total, records, launchCandidates<true>);
 }
 
 } // extern "C"

@@ -18,9 +18,13 @@
 //                                     come from query_list.h's listTilePrefixKernel, listOffsetsKernel and listWriteKernel.
 //   proximityDistancesKernel          one lane per list entry: its query by bisection of the offsets, the distance again.
 //
+// The host side is query_host.h's ("The query facility"): closest shape is a queryBest, shapes in range a queryLists of slot
+// lists with the distances beside them where asked for; this file supplies proximityKind and the launches of its kernels.
+//
 // All arithmetic is fp32 in the reference's operation order (gjk_ops.h); this file is compiled without contraction in both libraries
 // (Makefile).
 #include "query_list.h"
+#include "query_host.h"
 
 #define S2_NP_BLOCK S2_BLOCK
 #define S2_NP_MAX_VERTS 8
@@ -28,14 +32,11 @@
 #include "proxy_ops.h"
 
 #include <cmath>
-#include <cstring>
 
 namespace
 {
 
 static_assert(sizeof(s2amdProximityQuery) == 96 && sizeof(s2amdProximityHit) == 32 && sizeof(s2amdProximityQuery) % 16 == 0, "the query records");
-
-#define S2_NO_SHAPE_KEY 0xffffffffffffffffull
 
 S2_DEV Xf queryFrame(const s2amdProximityQuery& q)
 {
@@ -162,11 +163,11 @@ __global__ __launch_bounds__(S2_BLOCK) void proximityFinishKernel(const s2amdSha
 	}
 	const s2amdProximityQuery* q = queries + i;
 	const unsigned long long key = keys[i];
-	const int slot = (int)(uint32_t)(key & 0xffffffffull);
+	const int slot = keySlot(key);
 	HitRecord rec;
 	rec.lo = make_float4(__int_as_float(-1), __int_as_float(-1), q->maxDistance, 0.0f);
 	rec.hi = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(0));
-	if (key != S2_NO_SHAPE_KEY && slot >= 0 && slot < n)
+	if (slot >= 0 && slot < n)
 	{
 		const LaneProxy s = loadProxy(shapes, slot, bodies, origins, nb);
 		if (s.live)
@@ -189,19 +190,7 @@ __global__ __launch_bounds__(S2_BLOCK) void proximityDistancesKernel(const s2amd
 	{
 		return;
 	}
-	int lo = 0, hi = count; // offsets[lo] <= e < offsets[hi]
-	while (hi - lo > 1)
-	{
-		const int mid = lo + (hi - lo) / 2;
-		if (offsets[mid] <= e)
-		{
-			lo = mid;
-		}
-		else
-		{
-			hi = mid;
-		}
-	}
+	const int lo = entryQuery(offsets, count, e);
 	const int slot = entries[e];
 	float distance = 0.0f;
 	if (slot >= 0 && slot < n)
@@ -215,8 +204,9 @@ __global__ __launch_bounds__(S2_BLOCK) void proximityDistancesKernel(const s2amd
 	distances[e] = distance;
 }
 
-bool validQuery(const s2amdProximityQuery& q)
+bool validQuery(const void* record)
 {
+	const s2amdProximityQuery& q = *(const s2amdProximityQuery*)record;
 	if (q.count < 1 || q.count > S2_NP_MAX_VERTS)
 	{
 		return false;
@@ -230,32 +220,26 @@ bool validQuery(const s2amdProximityQuery& q)
 	return finite && q.radius >= 0.0f && q.maxDistance >= 0.0f;
 }
 
-// what both calls check before anything is enqueued; *proceed is false when the call has already been answered
-int openCall(s2amdSolver* s, const s2amdProximityQuery* queries, int32_t count, bool* proceed)
+const QueryKind proximityKind = {sizeof(s2amdProximityQuery), "queries", validQuery, "proximity query",
+								 "is invalid (count outside 1..8, a NaN or infinite field, a negative radius or maxDistance)", {0, 0}, nullptr};
+
+// ---- the launches query_host.h's drivers ask for ----
+template <bool LIST> void launchCandidates(const QueryCall& c, unsigned long long* out)
 {
-	*proceed = false;
-	if (int rc = queryState(s))
-	{
-		return rc;
-	}
-	if (count == 0)
-	{
-		return S2AMD_OK;
-	}
-	if (count > S2_QUERY_MAX_COUNT)
-	{
-		return fail(S2AMD_E_INVALID, "more queries than one call takes: split the batch");
-	}
-	for (int32_t i = 0; i < count; ++i)
-	{
-		if (!validQuery(queries[i]))
-		{
-			return fail(S2AMD_E_INVALID, "proximity query " + std::to_string(i) +
-											 " is invalid (count outside 1..8, a NaN or infinite field, a negative radius or maxDistance)");
-		}
-	}
-	*proceed = true;
-	return S2AMD_OK;
+	proximityCandidatesKernel<LIST>
+		<<<c.grid, dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.tiles, c.bodies, c.origins, c.nb, (const s2amdProximityQuery*)c.records, c.count, out);
+}
+
+void launchFinish(const QueryCall& c, const unsigned long long* keys, void* hits)
+{
+	proximityFinishKernel<<<gridFor((size_t)c.count), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdProximityQuery*)c.records, c.count,
+																					  keys, (HitRecord*)hits);
+}
+
+void launchDistances(const QueryCall& c, const int* offsets, const int32_t* slots, int capacity, void* distances)
+{
+	proximityDistancesKernel<<<gridFor((size_t)capacity), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdProximityQuery*)c.records,
+																						  c.count, offsets, slots, capacity, (float*)distances);
 }
 
 } // namespace
@@ -266,139 +250,14 @@ extern "C"
 
 int s2amd_world_closest_shape(s2amdSolver* s, const s2amdProximityQuery* queries, int32_t count, s2amdProximityHit* hits)
 {
-	if (!s || count < 0 || (count > 0 && (!queries || !hits)))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	bool proceed;
-	if (int rc = openCall(s, queries, count, &proceed))
-	{
-		return rc;
-	}
-	if (!proceed)
-	{
-		return S2AMD_OK;
-	}
-	const int ns = s->shapeCapacity;
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	size_t at = 0;
-	const size_t inAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdProximityQuery));
-	const size_t keysAt = at;
-	at += roundUp((size_t)count * sizeof(unsigned long long));
-	const size_t hitsAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdProximityHit));
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	const s2amdProximityQuery* dQueries = (const s2amdProximityQuery*)(base + inAt);
-	unsigned long long* keys = (unsigned long long*)(base + keysAt);
-	HIP_TRY(hipMemcpyAsync(base + inAt, queries, (size_t)count * sizeof(s2amdProximityQuery), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)count * sizeof(unsigned long long), st));
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	if (tiles > 0)
-	{
-		proximityCandidatesKernel<false><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>(
-			(const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, s->bodyCapacity, dQueries, count, keys);
-	}
-	proximityFinishKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																			  s->bodyCapacity, dQueries, count, keys, (HitRecord*)(base + hitsAt));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(hits, base + hitsAt, (size_t)count * sizeof(s2amdProximityHit), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	return S2AMD_OK;
+	return queryBest(s, proximityKind, queries, count, hits, sizeof(s2amdProximityHit), launchCandidates<false>, launchFinish);
 }
 
-// upload, the mask pass, query_list.h's three, the distances where asked for, one copy back of {offsets, entries, distances}
 int s2amd_world_shapes_in_range(s2amdSolver* s, const s2amdProximityQuery* queries, int32_t count, int32_t* offsets, int32_t* shapes, float* distances, int32_t capacity,
 								int32_t* total)
 {
-	if (!s || count < 0 || capacity < 0 || !total || (count > 0 && (!queries || !offsets)) || (capacity > 0 && !shapes))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	bool proceed;
-	if (int rc = openCall(s, queries, count, &proceed))
-	{
-		return rc;
-	}
-	if (!proceed)
-	{
-		return S2AMD_OK;
-	}
-	const int ns = s->shapeCapacity;
-	if (ns <= 0)
-	{
-		std::memset(offsets, 0, ((size_t)count + 1) * sizeof(int32_t));
-		*total = 0;
-		return S2AMD_OK;
-	}
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	const size_t words = (size_t)count * tiles * 4;
-	if ((size_t)count * (size_t)ns > (size_t)INT32_MAX)
-	{
-		return fail(S2AMD_E_INVALID, "queries x shape slots beyond 2^31: split the batch");
-	}
-	// no list is longer than the shape slots, nor all together than the caller's capacity
-	const size_t entries = std::min((size_t)capacity, (size_t)count * (size_t)ns);
-	size_t at = 0;
-	const size_t inAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdProximityQuery));
-	const size_t masksAt = at;
-	at += roundUp(words * sizeof(unsigned long long));
-	const size_t prefixAt = at;
-	at += roundUp((size_t)count * tiles * sizeof(int));
-	const size_t totalsAt = at;
-	at += roundUp((size_t)count * sizeof(int));
-	const size_t outAt = at; // {offsets[count + 1], entries, their distances}
-	const size_t outWords = (size_t)count + 1 + entries + (distances ? entries : 0);
-	at += roundUp(outWords * sizeof(int32_t));
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	const s2amdProximityQuery* dQueries = (const s2amdProximityQuery*)(base + inAt);
-	HIP_TRY(hipMemcpyAsync(base + inAt, queries, (size_t)count * sizeof(s2amdProximityQuery), hipMemcpyHostToDevice, st));
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	unsigned long long* masks = (unsigned long long*)(base + masksAt);
-	int* dOffsets = (int*)(base + outAt);
-	int32_t* dEntries = dOffsets + count + 1;
-	proximityCandidatesKernel<true><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>(
-		(const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, s->bodyCapacity, dQueries, count, masks);
-	listTilePrefixKernel<<<dim3((unsigned)((count + 3) / 4)), dim3(S2_BLOCK), 0, st>>>(masks, count, tiles, (int*)(base + prefixAt), (int*)(base + totalsAt));
-	listOffsetsKernel<<<dim3(1), dim3(64), 0, st>>>((const int*)(base + totalsAt), count, dOffsets);
-	listWriteKernel<<<gridFor(words), dim3(S2_BLOCK), 0, st>>>(masks, words, tiles, (const int*)(base + prefixAt), dOffsets, dEntries, (int)entries);
-	if (distances && entries > 0)
-	{
-		proximityDistancesKernel<<<gridFor(entries), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																			   s->bodyCapacity, dQueries, count, dOffsets, dEntries, (int)entries, (float*)(dEntries + entries));
-	}
-	HIP_TRY(hipGetLastError());
-	s->hQueryStage.resize(outWords);
-	HIP_TRY(hipMemcpyAsync(s->hQueryStage.data(), base + outAt, outWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	std::memcpy(offsets, s->hQueryStage.data(), ((size_t)count + 1) * sizeof(int32_t));
-	*total = offsets[count];
-	if (*total > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "shapes-in-range buffer too small");
-	}
-	if (*total > 0)
-	{
-		std::memcpy(shapes, s->hQueryStage.data() + count + 1, (size_t)*total * sizeof(int32_t));
-		if (distances)
-		{
-			std::memcpy(distances, s->hQueryStage.data() + count + 1 + entries, (size_t)*total * sizeof(float));
-		}
-	}
-	return S2AMD_OK;
+	const QueryPayload slots = {0, "shapes-in-range buffer too small", launchDistances};
+	return queryLists(s, proximityKind, queries, count, offsets, shapes, distances, capacity, total, slots, launchCandidates<true>);
 }
 
 } // extern "C"

@@ -1,7 +1,9 @@
-// What the list-valued queries on the resident world share (scene_query.hip: point probes and box queries; proximity_query.hip: shapes
-// in range): the candidate rule's box test, the second half of the ballot-mask -> tile-prefix -> offsets -> write sequence that turns
-// per-wave hit masks into CSR lists ascending by slot, and the host-side checks every query call opens with.  The first half -- the mask
-// kernel -- is each file's own.  Everything is in an unnamed namespace: each file holds its own copy of the kernels under the same names.
+// What the queries on the resident world share on the device (scene_query.hip, proximity_query.hip, contact_query.hip, shape_cast.hip;
+// sensor_report.hip and force_field.hip use parts): the candidate rule's box test, the second half of the ballot-mask -> tile-prefix ->
+// offsets -> write sequence that turns per-wave hit masks into CSR lists ascending by slot, the no-hit key of the single-answer queries
+// with its decoding (keySlot), the query of a list entry (entryQuery), and two small host helpers (roundUp, queryState).  The first half
+// of the sequence -- the mask kernel -- is each file's own; the host side that drives it all is query_host.h.  Everything is in an unnamed
+// namespace: each file holds its own copy of the kernels under the same names.
 //
 //   masks[((query * tiles) + tile) * 4 + wave]   the wave's hits of the query, bit = lane; every word is written by the mask kernel
 //   listTilePrefixKernel  one wave per query: the exclusive prefix of the tiles' hit counts, and the query's total.
@@ -136,6 +138,35 @@ __global__ __launch_bounds__(S2_BLOCK) void listWriteKernel(const unsigned long 
 		}
 		at += 1;
 	}
+}
+
+// What the single-answer queries propose by a 64-bit integer atomic min: (an ordered key of the answer's figure) << 32 | slot, so the least
+// key is the least figure, ties to the lowest slot.  The keys start as the no-hit key: every bit set.
+#define S2_QUERY_NO_KEY 0xffffffffffffffffull
+
+// the winner's slot; -1: nothing proposed
+S2_DEV int keySlot(unsigned long long key)
+{
+	return key == S2_QUERY_NO_KEY ? -1 : (int)(uint32_t)(key & 0xffffffffull);
+}
+
+// the query of list entry e (0 <= e < offsets[count]): the last one whose offset is <= e
+S2_DEV int entryQuery(const int* offsets, int count, int e)
+{
+	int lo = 0, hi = count; // offsets[lo] <= e < offsets[hi]
+	while (hi - lo > 1)
+	{
+		const int mid = lo + (hi - lo) / 2;
+		if (offsets[mid] <= e)
+		{
+			lo = mid;
+		}
+		else
+		{
+			hi = mid;
+		}
+	}
+	return lo;
 }
 
 inline size_t roundUp(size_t bytes)

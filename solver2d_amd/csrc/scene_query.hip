@@ -14,27 +14,27 @@
 //                         atomic min.  The least key is the least fraction, ties to the lowest slot, whatever the launch geometry.
 //   rayFinishKernel       one lane per ray: the winner's exact test again (the same operations, so the same bits) and the 32-byte record.
 //   listMaskKernel        box queries and point probes: per (query, tile, wave) the 64-bit ballot of the hits.
-//   query_list.h          listTilePrefixKernel, listOffsetsKernel, listWriteKernel: the masks into CSR lists ascending by slot (shared
-//                         with proximity_query.hip).
+//   query_list.h          listTilePrefixKernel, listOffsetsKernel, listWriteKernel: the masks into CSR lists ascending by slot.
+//
+// The host side is query_host.h's ("The query facility"): the ray cast is a queryBest over rayKind, the two list calls a
+// queryLists of plain slot lists with no validator; this file supplies the kinds and the launches of its kernels.
 //
 // All arithmetic is fp32 in the reference's operation order (query_ops.h, gjk_ops.h); this file is compiled without contraction in
 // both libraries (Makefile).
 #include "query_list.h"
+#include "query_host.h"
 
 #define S2_NP_BLOCK S2_BLOCK
 #define S2_NP_MAX_VERTS 8
 #include "query_ops.h"
 
 #include <cmath>
-#include <cstring>
 
 namespace
 {
 
 static_assert(sizeof(s2amdRay) == 24 && sizeof(s2amdRayHit) == 32 && sizeof(s2amdPointProbe) == 12 && sizeof(s2amdBoxQuery) == 20, "the query records");
 static_assert(sizeof(s2amdShape) == 196, "the shape record");
-
-#define S2_NO_HIT_KEY 0xffffffffffffffffull
 
 // what a lane keeps of its shape slot
 struct LaneShape
@@ -211,11 +211,11 @@ __global__ __launch_bounds__(S2_BLOCK) void rayFinishKernel(const s2amdShape* sh
 	}
 	const s2amdRay r = rays[i];
 	const unsigned long long key = keys[i];
-	const int slot = (int)(uint32_t)(key & 0xffffffffull);
+	const int slot = keySlot(key);
 	HitRecord rec;
 	rec.lo = make_float4(__int_as_float(-1), __int_as_float(-1), r.maxFraction, 0.0f);
 	rec.hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	if (key != S2_NO_HIT_KEY && slot >= 0 && slot < n)
+	if (slot >= 0 && slot < n)
 	{
 		PolyRef polygon;
 		polygon.verts = verts + threadIdx.x, polygon.norms = norms + threadIdx.x;
@@ -327,90 +327,39 @@ __global__ __launch_bounds__(S2_BLOCK) void listMaskKernel(const s2amdShape* sha
 }
 
 // s2IsValidRay, src/geometry.c:15-20
-bool validRay(const s2amdRay& r)
+bool validRay(const void* record)
 {
+	const s2amdRay& r = *(const s2amdRay*)record;
 	const bool finite = std::isfinite(r.p1[0]) && std::isfinite(r.p1[1]) && std::isfinite(r.p2[0]) && std::isfinite(r.p2[1]) && std::isfinite(r.maxFraction);
 	return finite && 0.0f <= r.maxFraction && r.maxFraction < 100000.0f;
 }
 
-// box queries and point probes: upload, four launches, one copy back of {offsets, entries}
+const QueryKind rayKind = {sizeof(s2amdRay), "rays", validRay, "ray", "fails s2IsValidRay (a NaN or infinite end point, or maxFraction outside [0, 100000))", {0, 0}, nullptr};
+
+// ---- the launches query_host.h's drivers ask for ----
+void launchRayCandidates(const QueryCall& c, unsigned long long* keys)
+{
+	rayCandidatesKernel<<<c.grid, dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdRay*)c.records, c.count, keys);
+}
+
+void launchRayFinish(const QueryCall& c, const unsigned long long* keys, void* hits)
+{
+	rayFinishKernel<<<gridFor((size_t)c.count), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdRay*)c.records, c.count, keys,
+																				(HitRecord*)hits);
+}
+
+template <bool POINT> void launchMasks(const QueryCall& c, unsigned long long* masks)
+{
+	listMaskKernel<POINT><<<c.grid, dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.tiles, c.bodies, c.origins, c.nb, c.records, c.count, masks);
+}
+
+// box queries and point probes: nothing to validate, the lists are the shape slots as they are
 template <bool POINT>
 int listQuery(s2amdSolver* s, const void* queries, size_t stride, int32_t count, int32_t* offsets, int32_t* shapes, int32_t capacity, int32_t* total)
 {
-	if (!s || count < 0 || capacity < 0 || !total || (count > 0 && (!queries || !offsets)) || (capacity > 0 && !shapes))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	if (int rc = queryState(s))
-	{
-		return rc;
-	}
-	if (count == 0)
-	{
-		return S2AMD_OK;
-	}
-	if (count > S2_QUERY_MAX_COUNT)
-	{
-		return fail(S2AMD_E_INVALID, "more queries than one call takes: split the batch");
-	}
-	const int ns = s->shapeCapacity;
-	if (ns <= 0)
-	{
-		std::memset(offsets, 0, ((size_t)count + 1) * sizeof(int32_t));
-		*total = 0;
-		return S2AMD_OK;
-	}
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	const size_t words = (size_t)count * tiles * 4;
-	if ((size_t)count * (size_t)ns > (size_t)INT32_MAX)
-	{
-		return fail(S2AMD_E_INVALID, "queries x shape slots beyond 2^31: split the batch");
-	}
-	// no list is longer than the shape slots, nor all together than the caller's capacity
-	const size_t entries = std::min((size_t)capacity, (size_t)count * (size_t)ns);
-	size_t at = 0;
-	const size_t inAt = at;
-	at += roundUp((size_t)count * stride);
-	const size_t masksAt = at;
-	at += roundUp(words * sizeof(unsigned long long));
-	const size_t prefixAt = at;
-	at += roundUp((size_t)count * tiles * sizeof(int));
-	const size_t totalsAt = at;
-	at += roundUp((size_t)count * sizeof(int));
-	const size_t outAt = at; // {offsets[count + 1], entries}
-	const size_t outBytes = ((size_t)count + 1 + entries) * sizeof(int32_t);
-	at += roundUp(outBytes);
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	HIP_TRY(hipMemcpyAsync(base + inAt, queries, (size_t)count * stride, hipMemcpyHostToDevice, st));
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	unsigned long long* masks = (unsigned long long*)(base + masksAt);
-	int* dOffsets = (int*)(base + outAt);
-	listMaskKernel<POINT><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p,
-																							   (const float2*)s->dOrigins.p, s->bodyCapacity, base + inAt, count, masks);
-	listTilePrefixKernel<<<dim3((unsigned)((count + 3) / 4)), dim3(S2_BLOCK), 0, st>>>(masks, count, tiles, (int*)(base + prefixAt), (int*)(base + totalsAt));
-	listOffsetsKernel<<<dim3(1), dim3(64), 0, st>>>((const int*)(base + totalsAt), count, dOffsets);
-	listWriteKernel<<<gridFor(words), dim3(S2_BLOCK), 0, st>>>(masks, words, tiles, (const int*)(base + prefixAt), dOffsets, dOffsets + count + 1, (int)entries);
-	HIP_TRY(hipGetLastError());
-	s->hQueryStage.resize((size_t)count + 1 + entries);
-	HIP_TRY(hipMemcpyAsync(s->hQueryStage.data(), base + outAt, outBytes, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	std::memcpy(offsets, s->hQueryStage.data(), ((size_t)count + 1) * sizeof(int32_t));
-	*total = offsets[count];
-	if (*total > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, POINT ? "point-probe hit buffer too small" : "box-query hit buffer too small");
-	}
-	if (*total > 0)
-	{
-		std::memcpy(shapes, s->hQueryStage.data() + count + 1, (size_t)*total * sizeof(int32_t));
-	}
-	return S2AMD_OK;
+	const QueryKind kind = {stride, "queries", nullptr, nullptr, nullptr, {0, 0}, nullptr};
+	const QueryPayload slots = {0, POINT ? "point-probe hit buffer too small" : "box-query hit buffer too small", nullptr};
+	return queryLists(s, kind, queries, count, offsets, shapes, nullptr, capacity, total, slots, launchMasks<POINT>);
 }
 
 } // namespace
@@ -421,61 +370,7 @@ extern "C"
 
 int s2amd_world_ray_cast(s2amdSolver* s, const s2amdRay* rays, int32_t count, s2amdRayHit* hits)
 {
-	if (!s || count < 0 || (count > 0 && (!rays || !hits)))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	if (int rc = queryState(s))
-	{
-		return rc;
-	}
-	if (count == 0)
-	{
-		return S2AMD_OK;
-	}
-	if (count > S2_QUERY_MAX_COUNT)
-	{
-		return fail(S2AMD_E_INVALID, "more rays than one call takes: split the batch");
-	}
-	for (int32_t i = 0; i < count; ++i)
-	{
-		if (!validRay(rays[i]))
-		{
-			return fail(S2AMD_E_INVALID, "ray " + std::to_string(i) + " fails s2IsValidRay (a NaN or infinite end point, or maxFraction outside [0, 100000))");
-		}
-	}
-	const int ns = s->shapeCapacity;
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	size_t at = 0;
-	const size_t inAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdRay));
-	const size_t keysAt = at;
-	at += roundUp((size_t)count * sizeof(unsigned long long));
-	const size_t hitsAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdRayHit));
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	const s2amdRay* dRays = (const s2amdRay*)(base + inAt);
-	unsigned long long* keys = (unsigned long long*)(base + keysAt);
-	HIP_TRY(hipMemcpyAsync(base + inAt, rays, (size_t)count * sizeof(s2amdRay), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)count * sizeof(unsigned long long), st));
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	if (tiles > 0)
-	{
-		rayCandidatesKernel<<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p,
-																								 (const float2*)s->dOrigins.p, s->bodyCapacity, dRays, count, keys);
-	}
-	rayFinishKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																		s->bodyCapacity, dRays, count, keys, (HitRecord*)(base + hitsAt));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(hits, base + hitsAt, (size_t)count * sizeof(s2amdRayHit), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	return S2AMD_OK;
+	return queryBest(s, rayKind, rays, count, hits, sizeof(s2amdRayHit), launchRayCandidates, launchRayFinish);
 }
 
 int s2amd_world_point_probe(s2amdSolver* s, const s2amdPointProbe* probes, int32_t count, int32_t* offsets, int32_t* shapes, int32_t capacity, int32_t* total)

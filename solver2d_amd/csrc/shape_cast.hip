@@ -18,9 +18,13 @@
 //                                query_list.h's listTilePrefixKernel, listOffsetsKernel and listWriteKernel.
 //   castRecordsKernel            one lane per list entry: its cast by bisection of the offsets, the advancement again, the record.
 //
+// The host side is query_host.h's ("The query facility"): cast shape is a queryBest, cast shape all a queryLists of 48-byte
+// records; this file supplies castKind and the launches of its kernels.
+//
 // All arithmetic is fp32 in the reference's operation order (gjk_ops.h); this file is compiled without contraction in both libraries
 // (Makefile).
 #include "query_list.h"
+#include "query_host.h"
 
 #define S2_NP_BLOCK S2_BLOCK
 #define S2_NP_MAX_VERTS 8
@@ -28,14 +32,12 @@
 #include "proxy_ops.h"
 
 #include <cmath>
-#include <cstring>
 
 namespace
 {
 
 static_assert(sizeof(s2amdShapeCast) == 112 && sizeof(s2amdShapeCastHit) == 48 && sizeof(s2amdShapeCast) % 16 == 0, "the cast records");
 
-#define S2_NO_HIT_KEY 0xffffffffffffffffull
 #define S2_CAST_TARGET S2_LINEAR_SLOP
 #define S2_CAST_TOLERANCE (0.25f * S2_LINEAR_SLOP)
 #define S2_CAST_SPECULATIVE (4.0f * S2_LINEAR_SLOP) // constants.h:8
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(S2_BLOCK) void castFinishKernel(const s2amdShape* s
 		return;
 	}
 	const unsigned long long key = keys[i];
-	const int slot = key == S2_NO_HIT_KEY ? -1 : (int)(uint32_t)(key & 0xffffffffull);
+	const int slot = keySlot(key);
 	hits[i] = recordOf(shapes, n, bodies, origins, nb, casts + i, slot);
 }
 
@@ -253,24 +255,13 @@ __global__ __launch_bounds__(S2_BLOCK) void castRecordsKernel(const s2amdShape* 
 	{
 		return;
 	}
-	int lo = 0, hi = count; // offsets[lo] <= e < offsets[hi]
-	while (hi - lo > 1)
-	{
-		const int mid = lo + (hi - lo) / 2;
-		if (offsets[mid] <= e)
-		{
-			lo = mid;
-		}
-		else
-		{
-			hi = mid;
-		}
-	}
+	const int lo = entryQuery(offsets, count, e);
 	hits[e] = recordOf(shapes, n, bodies, origins, nb, casts + lo, entries[e]);
 }
 
-bool validCast(const s2amdShapeCast& c)
+bool validCast(const void* record)
 {
+	const s2amdShapeCast& c = *(const s2amdShapeCast*)record;
 	if (c.count < 1 || c.count > S2_NP_MAX_VERTS)
 	{
 		return false;
@@ -284,32 +275,25 @@ bool validCast(const s2amdShapeCast& c)
 	return finite && c.radius >= 0.0f && c.maxFraction >= 0.0f;
 }
 
-// what both calls check before anything is enqueued; *proceed is false when the call has already been answered
-int openCall(s2amdSolver* s, const s2amdShapeCast* casts, int32_t count, bool* proceed)
+const QueryKind castKind = {sizeof(s2amdShapeCast), "casts", validCast, "shape cast", "is invalid (count outside 1..8, a NaN or infinite field, a negative radius or maxFraction)",
+							{0, 0}, nullptr};
+
+// ---- the launches query_host.h's drivers ask for ----
+template <bool LIST> void launchCandidates(const QueryCall& c, unsigned long long* out)
 {
-	*proceed = false;
-	if (int rc = queryState(s))
-	{
-		return rc;
-	}
-	if (count == 0)
-	{
-		return S2AMD_OK;
-	}
-	if (count > S2_QUERY_MAX_COUNT)
-	{
-		return fail(S2AMD_E_INVALID, "more casts than one call takes: split the batch");
-	}
-	for (int32_t i = 0; i < count; ++i)
-	{
-		if (!validCast(casts[i]))
-		{
-			return fail(S2AMD_E_INVALID, "shape cast " + std::to_string(i) +
-											 " is invalid (count outside 1..8, a NaN or infinite field, a negative radius or maxFraction)");
-		}
-	}
-	*proceed = true;
-	return S2AMD_OK;
+	castCandidatesKernel<LIST><<<c.grid, dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.tiles, c.bodies, c.origins, c.nb, (const s2amdShapeCast*)c.records, c.count, out);
+}
+
+void launchFinish(const QueryCall& c, const unsigned long long* keys, void* hits)
+{
+	castFinishKernel<<<gridFor((size_t)c.count), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdShapeCast*)c.records, c.count, keys,
+																				 (HitRecord*)hits);
+}
+
+void launchRecords(const QueryCall& c, const int* offsets, const int32_t* slots, int capacity, void* hits)
+{
+	castRecordsKernel<<<gridFor((size_t)capacity), dim3(S2_BLOCK), 0, c.stream>>>(c.shapes, c.ns, c.bodies, c.origins, c.nb, (const s2amdShapeCast*)c.records, c.count, offsets,
+																				   slots, capacity, (HitRecord*)hits);
 }
 
 } // namespace
@@ -320,136 +304,13 @@ extern "C"
 
 int s2amd_world_cast_shape(s2amdSolver* s, const s2amdShapeCast* casts, int32_t count, s2amdShapeCastHit* hits)
 {
-	if (!s || count < 0 || (count > 0 && (!casts || !hits)))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	bool proceed;
-	if (int rc = openCall(s, casts, count, &proceed))
-	{
-		return rc;
-	}
-	if (!proceed)
-	{
-		return S2AMD_OK;
-	}
-	const int ns = s->shapeCapacity;
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	size_t at = 0;
-	const size_t inAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdShapeCast));
-	const size_t keysAt = at;
-	at += roundUp((size_t)count * sizeof(unsigned long long));
-	const size_t hitsAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdShapeCastHit));
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	const s2amdShapeCast* dCasts = (const s2amdShapeCast*)(base + inAt);
-	unsigned long long* keys = (unsigned long long*)(base + keysAt);
-	HIP_TRY(hipMemcpyAsync(base + inAt, casts, (size_t)count * sizeof(s2amdShapeCast), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)count * sizeof(unsigned long long), st));
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	if (tiles > 0)
-	{
-		castCandidatesKernel<false><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>(
-			(const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, s->bodyCapacity, dCasts, count, keys);
-	}
-	castFinishKernel<<<gridFor((size_t)count), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																		 s->bodyCapacity, dCasts, count, keys, (HitRecord*)(base + hitsAt));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(hits, base + hitsAt, (size_t)count * sizeof(s2amdShapeCastHit), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	return S2AMD_OK;
+	return queryBest(s, castKind, casts, count, hits, sizeof(s2amdShapeCastHit), launchCandidates<false>, launchFinish);
 }
 
-// upload, the mask pass, query_list.h's three, the records; the offsets come back, then the records they count
 int s2amd_world_cast_shape_all(s2amdSolver* s, const s2amdShapeCast* casts, int32_t count, int32_t* offsets, s2amdShapeCastHit* hits, int32_t capacity, int32_t* total)
 {
-	if (!s || count < 0 || capacity < 0 || !total || (count > 0 && (!casts || !offsets)) || (capacity > 0 && !hits))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	bool proceed;
-	if (int rc = openCall(s, casts, count, &proceed))
-	{
-		return rc;
-	}
-	if (!proceed)
-	{
-		return S2AMD_OK;
-	}
-	const int ns = s->shapeCapacity;
-	if (ns <= 0)
-	{
-		std::memset(offsets, 0, ((size_t)count + 1) * sizeof(int32_t));
-		*total = 0;
-		return S2AMD_OK;
-	}
-	const int tiles = (ns + S2_BLOCK - 1) / S2_BLOCK;
-	const size_t words = (size_t)count * tiles * 4;
-	if ((size_t)count * (size_t)ns > (size_t)INT32_MAX)
-	{
-		return fail(S2AMD_E_INVALID, "casts x shape slots beyond 2^31: split the batch");
-	}
-	// no list is longer than the shape slots, nor all together than the caller's capacity
-	const size_t entries = std::min((size_t)capacity, (size_t)count * (size_t)ns);
-	size_t at = 0;
-	const size_t inAt = at;
-	at += roundUp((size_t)count * sizeof(s2amdShapeCast));
-	const size_t masksAt = at;
-	at += roundUp(words * sizeof(unsigned long long));
-	const size_t prefixAt = at;
-	at += roundUp((size_t)count * tiles * sizeof(int));
-	const size_t totalsAt = at;
-	at += roundUp((size_t)count * sizeof(int));
-	const size_t slotsAt = at;
-	at += roundUp(entries * sizeof(int32_t));
-	const size_t outAt = at; // {offsets[count + 1], padding to 16 bytes, records}
-	const size_t recordsIn = (((size_t)count + 1) * sizeof(int32_t) + 15) & ~size_t(15);
-	at += roundUp(recordsIn + entries * sizeof(s2amdShapeCastHit));
-	HIP_TRY(hipSetDevice(s->device));
-	if (int rc = s->dQuery.ensure(at))
-	{
-		return rc;
-	}
-	char* base = (char*)s->dQuery.p;
-	hipStream_t st = s->stream;
-	const s2amdShapeCast* dCasts = (const s2amdShapeCast*)(base + inAt);
-	HIP_TRY(hipMemcpyAsync(base + inAt, casts, (size_t)count * sizeof(s2amdShapeCast), hipMemcpyHostToDevice, st));
-	const int chunks = (count + S2_QUERY_CHUNK - 1) / S2_QUERY_CHUNK;
-	unsigned long long* masks = (unsigned long long*)(base + masksAt);
-	int* dOffsets = (int*)(base + outAt);
-	int32_t* dSlots = (int32_t*)(base + slotsAt);
-	castCandidatesKernel<true><<<dim3((unsigned)tiles, (unsigned)chunks), dim3(S2_BLOCK), 0, st>>>(
-		(const s2amdShape*)s->dShapes.p, ns, tiles, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p, s->bodyCapacity, dCasts, count, masks);
-	listTilePrefixKernel<<<dim3((unsigned)((count + 3) / 4)), dim3(S2_BLOCK), 0, st>>>(masks, count, tiles, (int*)(base + prefixAt), (int*)(base + totalsAt));
-	listOffsetsKernel<<<dim3(1), dim3(64), 0, st>>>((const int*)(base + totalsAt), count, dOffsets);
-	listWriteKernel<<<gridFor(words), dim3(S2_BLOCK), 0, st>>>(masks, words, tiles, (const int*)(base + prefixAt), dOffsets, dSlots, (int)entries);
-	if (entries > 0)
-	{
-		castRecordsKernel<<<gridFor(entries), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, (const s2amdBody*)s->dBodies.p, (const float2*)s->dOrigins.p,
-																		s->bodyCapacity, dCasts, count, dOffsets, dSlots, (int)entries, (HitRecord*)(base + outAt + recordsIn));
-	}
-	HIP_TRY(hipGetLastError());
-	// the offsets first: a record is 48 bytes, and only offsets[count] of the `entries` the caller has room for exist
-	HIP_TRY(hipMemcpyAsync(offsets, base + outAt, ((size_t)count + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	*total = offsets[count];
-	if (*total > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "cast-shape buffer too small");
-	}
-	if (*total > 0)
-	{
-		HIP_TRY(hipMemcpyAsync(hits, base + outAt + recordsIn, (size_t)*total * sizeof(s2amdShapeCastHit), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-	}
-	return S2AMD_OK;
+	const QueryPayload records = {sizeof(s2amdShapeCastHit), "cast-shape buffer too small", launchRecords};
+	return queryLists(s, castKind, casts, count, offsets, hits, nullptr, capacity, total, records, launchCandidates<true>);
 }
 
 } // extern "C"

@@ -533,8 +533,8 @@ struct SolverRest
 	unsigned long long* hostPairLog = nullptr; // ... its pinned host copy (the host appends, the device reads)
 	bool pairLogDirty = false;
 	DevBuf dShapeBoxes;		// world chain: s2amd_world_download_boxes' staging
-	DevBuf dQuery;			// scene queries (scene_query.hip): the queries, the passes' scratch and the results of one call; grows on demand, kept between calls
-	std::vector<int32_t> hQueryStage; // ... where the list calls' {offsets, entries} land before they are split into the caller's two arrays
+	DevBuf dQuery;			// the queries on the resident world (query_host.h: scene_query.hip, proximity_query.hip, contact_query.hip, shape_cast.hip): the records, the passes' scratch and the results of one call, carved from offset 0; grows on demand, kept between calls (sensor_report.hip writes a list longer than its block's room here too, for the getter that asked)
+	std::vector<int32_t> hQueryStage; // ... where a slot-list call's {offsets, entries[, distances]} land before they are split into the caller's arrays
 	DevBuf dEdit;					  // world edits (world_edit.hip): the skip count, the staged list, the sort's keys and scratch of one call; grows on demand, kept between calls
 	char* hostEditStage = nullptr;	  // ... the pinned copy of the caller's list the device copy reads, and the event of that copy (the next call waits for it before it overwrites the stage)
 	size_t hostEditStageBytes = 0;

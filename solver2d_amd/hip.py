@@ -454,124 +454,84 @@ class Solver:
         return bodies, contacts, joints, shapes, pairs, origins, status
 
     # ---- scene queries on the resident world: the world as it stands now, nothing resident changes ----
-    def world_ray_cast(self, rays):
-        """Closest hit of every ray (wire.ray_dtype) -> wire.ray_hit_dtype[len(rays)]; shape == -1: no hit."""
-        rays = np.ascontiguousarray(rays)
-        assert rays.dtype == wire.ray_dtype
-        hits = np.zeros(len(rays), dtype=wire.ray_hit_dtype)
-        self._ck(self._L.s2amd_world_ray_cast(self._h, wire.as_ptr(rays), len(rays), wire.as_ptr(hits)))
+    def _world_best(self, fn, records, dtype, hit_dtype):
+        """One answer per record: hit_dtype[len(records)]."""
+        records = np.ascontiguousarray(records)
+        assert records.dtype == dtype
+        hits = np.zeros(len(records), dtype=hit_dtype)
+        self._ck(fn(self._h, wire.as_ptr(records), len(records), wire.as_ptr(hits)))
         return hits
 
-    def _world_csr(self, fn, queries, dtype, expected):
-        """(offsets, shapes) of a list query: asked again with the total the library states when it answers S2AMD_E_CAPACITY."""
-        queries = np.ascontiguousarray(queries)
-        assert queries.dtype == dtype
-        offsets = np.zeros(len(queries) + 1, dtype=np.int32)
+    def _world_lists(self, fn, records, dtype, payload_dtype, expected, distances=False):
+        """A list per record: (offsets[len + 1], payload); with distances=True fn takes a float array behind the payload, and the answer is
+        (offsets, payload, distances).  Asked again with the total the library states when it answers S2AMD_E_CAPACITY."""
+        records = np.ascontiguousarray(records)
+        assert records.dtype == dtype
+        offsets = np.zeros(len(records) + 1, dtype=np.int32)
         cap = max(int(expected), 1)
         while True:
-            shapes = np.zeros(cap, dtype=np.int32)
+            payload = np.zeros(cap, dtype=payload_dtype)
+            beside = np.zeros(cap, dtype=np.float32) if distances else None
             n = ctypes.c_int32()
-            rc = fn(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(shapes), cap, ctypes.byref(n))
-            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
-                cap = n.value
-                continue
-            self._ck(rc)
-            return offsets, shapes[: n.value].copy()
-
-    def world_point_probe(self, probes, expected=None):
-        """The shapes that contain each point (wire.point_probe_dtype): (offsets[len + 1], shapes), ascending by slot per probe."""
-        return self._world_csr(self._L.s2amd_world_point_probe, probes, wire.point_probe_dtype, expected or 4 * len(probes) + 64)
-
-    def world_query_boxes(self, boxes, expected=None):
-        """The shapes whose fat box overlaps each box (wire.box_query_dtype): (offsets[len + 1], shapes), ascending by slot per box."""
-        return self._world_csr(self._L.s2amd_world_query_boxes, boxes, wire.box_query_dtype, expected or 16 * len(boxes) + 64)
-
-    # ---- proximity queries on the resident world: s2ShapeDistance between a caller's proxy and the shapes near it ----
-    def world_closest_shape(self, queries):
-        """The in-range shape of least distance for every query (wire.proximity_query_dtype) -> wire.proximity_hit_dtype[len(queries)];
-        shape == -1: nothing within maxDistance."""
-        queries = np.ascontiguousarray(queries)
-        assert queries.dtype == wire.proximity_query_dtype
-        hits = np.zeros(len(queries), dtype=wire.proximity_hit_dtype)
-        self._ck(self._L.s2amd_world_closest_shape(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(hits)))
-        return hits
-
-    def world_shapes_in_range(self, queries, distances=False, expected=None):
-        """The shapes within maxDistance of each query: (offsets[len + 1], shapes), ascending by slot per query; with distances=True
-        (offsets, shapes, distances).  Asked again with the total the library states when it answers S2AMD_E_CAPACITY."""
-        queries = np.ascontiguousarray(queries)
-        assert queries.dtype == wire.proximity_query_dtype
-        offsets = np.zeros(len(queries) + 1, dtype=np.int32)
-        cap = max(int(expected or 8 * len(queries) + 64), 1)
-        while True:
-            shapes = np.zeros(cap, dtype=np.int32)
-            dist = np.zeros(cap, dtype=np.float32) if distances else None
-            n = ctypes.c_int32()
-            rc = self._L.s2amd_world_shapes_in_range(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(shapes),
-                                                     wire.as_ptr(dist) if distances else None, cap, ctypes.byref(n))
+            out = (wire.as_ptr(payload), wire.as_ptr(beside)) if distances else (wire.as_ptr(payload),)
+            rc = fn(self._h, wire.as_ptr(records), len(records), wire.as_ptr(offsets), *out, cap, ctypes.byref(n))
             if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
                 cap = n.value
                 continue
             self._ck(rc)
             if distances:
-                return offsets, shapes[: n.value].copy(), dist[: n.value].copy()
-            return offsets, shapes[: n.value].copy()
+                return offsets, payload[: n.value].copy(), beside[: n.value].copy()
+            return offsets, payload[: n.value].copy()
+
+    def world_ray_cast(self, rays):
+        """Closest hit of every ray (wire.ray_dtype) -> wire.ray_hit_dtype[len(rays)]; shape == -1: no hit."""
+        return self._world_best(self._L.s2amd_world_ray_cast, rays, wire.ray_dtype, wire.ray_hit_dtype)
+
+    def world_point_probe(self, probes, expected=None):
+        """The shapes that contain each point (wire.point_probe_dtype): (offsets[len + 1], shapes), ascending by slot per probe."""
+        return self._world_lists(self._L.s2amd_world_point_probe, probes, wire.point_probe_dtype, np.int32, expected or 4 * len(probes) + 64)
+
+    def world_query_boxes(self, boxes, expected=None):
+        """The shapes whose fat box overlaps each box (wire.box_query_dtype): (offsets[len + 1], shapes), ascending by slot per box."""
+        return self._world_lists(self._L.s2amd_world_query_boxes, boxes, wire.box_query_dtype, np.int32, expected or 16 * len(boxes) + 64)
+
+    # ---- proximity queries on the resident world: s2ShapeDistance between a caller's proxy and the shapes near it ----
+    def world_closest_shape(self, queries):
+        """The in-range shape of least distance for every query (wire.proximity_query_dtype) -> wire.proximity_hit_dtype[len(queries)];
+        shape == -1: nothing within maxDistance."""
+        return self._world_best(self._L.s2amd_world_closest_shape, queries, wire.proximity_query_dtype, wire.proximity_hit_dtype)
+
+    def world_shapes_in_range(self, queries, distances=False, expected=None):
+        """The shapes within maxDistance of each query: (offsets[len + 1], shapes), ascending by slot per query; with distances=True
+        (offsets, shapes, distances).  Asked again with the total the library states when it answers S2AMD_E_CAPACITY."""
+        fn = self._L.s2amd_world_shapes_in_range
+        if not distances:
+            fn = lambda h, q, count, offsets, shapes, cap, total: self._L.s2amd_world_shapes_in_range(h, q, count, offsets, shapes, None, cap, total)  # noqa: E731
+        return self._world_lists(fn, queries, wire.proximity_query_dtype, np.int32, expected or 8 * len(queries) + 64, distances=bool(distances))
 
     # ---- contact queries on the resident world: the reference's manifolds between a caller's shape and the shapes near it ----
     def world_deepest_contact(self, queries):
         """The hit of least separation for every query (wire.contact_query_dtype) -> wire.contact_hit_dtype[len(queries)];
         shape == -1: the query touches nothing."""
-        queries = np.ascontiguousarray(queries)
-        assert queries.dtype == wire.contact_query_dtype
-        hits = np.zeros(len(queries), dtype=wire.contact_hit_dtype)
-        self._ck(self._L.s2amd_world_deepest_contact(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(hits)))
-        return hits
+        return self._world_best(self._L.s2amd_world_deepest_contact, queries, wire.contact_query_dtype, wire.contact_hit_dtype)
 
     def world_collide_shape(self, queries, expected=None):
         """The manifolds of each query against the shapes it touches: (offsets[len + 1], hits), ascending by slot per query.  Asked again
         with the total the library states when it answers S2AMD_E_CAPACITY."""
-        queries = np.ascontiguousarray(queries)
-        assert queries.dtype == wire.contact_query_dtype
-        offsets = np.zeros(len(queries) + 1, dtype=np.int32)
-        cap = max(int(expected or 4 * len(queries) + 64), 1)
-        while True:
-            hits = np.zeros(cap, dtype=wire.contact_hit_dtype)
-            n = ctypes.c_int32()
-            rc = self._L.s2amd_world_collide_shape(self._h, wire.as_ptr(queries), len(queries), wire.as_ptr(offsets), wire.as_ptr(hits), cap,
-                                                   ctypes.byref(n))
-            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
-                cap = n.value
-                continue
-            self._ck(rc)
-            return offsets, hits[: n.value].copy()
+        return self._world_lists(self._L.s2amd_world_collide_shape, queries, wire.contact_query_dtype, wire.contact_hit_dtype, expected or 4 * len(queries) + 64,
+                                 distances=None)
 
     # ---- shape casts on the resident world: a caller's proxy swept along a vector, conservative advancement over s2ShapeDistance ----
     def world_cast_shape(self, casts):
         """The hit of least fraction for every cast (wire.shape_cast_dtype) -> wire.shape_cast_hit_dtype[len(casts)];
         shape == -1: the sweep reaches nothing up to maxFraction."""
-        casts = np.ascontiguousarray(casts)
-        assert casts.dtype == wire.shape_cast_dtype
-        hits = np.zeros(len(casts), dtype=wire.shape_cast_hit_dtype)
-        self._ck(self._L.s2amd_world_cast_shape(self._h, wire.as_ptr(casts), len(casts), wire.as_ptr(hits)))
-        return hits
+        return self._world_best(self._L.s2amd_world_cast_shape, casts, wire.shape_cast_dtype, wire.shape_cast_hit_dtype)
 
     def world_cast_shape_all(self, casts, expected=None):
         """Every shape each cast hits: (offsets[len + 1], hits), ascending by slot per cast.  Asked again with the total the library
         states when it answers S2AMD_E_CAPACITY."""
-        casts = np.ascontiguousarray(casts)
-        assert casts.dtype == wire.shape_cast_dtype
-        offsets = np.zeros(len(casts) + 1, dtype=np.int32)
-        cap = max(int(expected or 4 * len(casts) + 64), 1)
-        while True:
-            hits = np.zeros(cap, dtype=wire.shape_cast_hit_dtype)
-            n = ctypes.c_int32()
-            rc = self._L.s2amd_world_cast_shape_all(self._h, wire.as_ptr(casts), len(casts), wire.as_ptr(offsets), wire.as_ptr(hits), cap,
-                                                    ctypes.byref(n))
-            if rc == -5 and n.value > cap:  # S2AMD_E_CAPACITY
-                cap = n.value
-                continue
-            self._ck(rc)
-            return offsets, hits[: n.value].copy()
+        return self._world_lists(self._L.s2amd_world_cast_shape_all, casts, wire.shape_cast_dtype, wire.shape_cast_hit_dtype, expected or 4 * len(casts) + 64,
+                                 distances=None)
 
     # ---- world edits: the reference's eight per-frame setters applied to the resident records, the structure kept ----
     def world_edit(self, edits, want_skipped=True):

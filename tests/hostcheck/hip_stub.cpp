@@ -5,20 +5,133 @@
 // streams / events / graphs are inert handles, and kernels are never run: hipLaunchKernel returns success and does nothing --
 // with S2_HOSTCHECK_TRACE_LAUNCHES set it prints one line per launch first: "LAUNCH <kernel symbol> grid <x> block <x> lds <bytes>"
 // (which kernel the host picked and the dynamic LDS it asked for are host decisions: tests/test_wide_island_kinds_host.py).
+// While S2_HOSTCHECK_TRACE_CALLS is set (looked up at every call, so a program can switch it) the stub prints what a call sequence
+// is made of, one line each and no pointers, so that two runs -- or two versions of the host code -- print the same text
+// (tests/test_query_host.py):
+//   LAUNCH <kernel> grid <x> <y> block <x> lds <bytes>            hipLaunchKernel (the demangled name with its template arguments)
+//   COPY <kind> <bytes>                                           hipMemcpyAsync
+//   MEMSET <value> <bytes>                                        hipMemsetAsync
+//   SYNC                                                          hipStreamSynchronize
 // Results of a step are therefore meaningless; what is checked is that the host code touches only memory it owns.
 // The product never links this file.
 #include <hip/hip_runtime_api.h>
 
+#include <cxxabi.h>
 #include <dlfcn.h>
+#include <elf.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 static int s_dummy[16];
 // the configuration of the `kernel<<<...>>>` in flight (clang's host code pushes it, the kernel's stub pops it and calls hipLaunchKernel)
 static thread_local dim3 s_grid(1), s_block(1);
 static thread_local size_t s_shared = 0;
+
+static bool traceCalls()
+{
+	return getenv("S2_HOSTCHECK_TRACE_CALLS") != nullptr;
+}
+
+// The handle of a kernel in an unnamed namespace is a local symbol, which dladdr does not know: its name from the .symtab of the file
+// it was loaded from (under ASan the handle has a second, longer name: the shortest is the kernel's own).
+static const char* localSymbol(const char* file, const void* base, const void* fn)
+{
+	static std::string loaded;
+	static std::vector<char> image;
+	if (loaded != file)
+	{
+		loaded = file;
+		image.clear();
+		if (FILE* f = fopen(file, "rb"))
+		{
+			fseek(f, 0, SEEK_END);
+			const long size = ftell(f);
+			fseek(f, 0, SEEK_SET);
+			image.resize(size > 0 ? (size_t)size : 0);
+			if (fread(image.data(), 1, image.size(), f) != image.size())
+			{
+				image.clear();
+			}
+			fclose(f);
+		}
+	}
+	if (image.size() < sizeof(Elf64_Ehdr) || memcmp(image.data(), ELFMAG, SELFMAG) != 0)
+	{
+		return nullptr;
+	}
+	const Elf64_Ehdr* header = (const Elf64_Ehdr*)image.data();
+	const Elf64_Shdr* sections = (const Elf64_Shdr*)(image.data() + header->e_shoff);
+	const Elf64_Addr want = (Elf64_Addr)((const char*)fn - (const char*)base);
+	const char* best = nullptr;
+	for (int i = 0; i < header->e_shnum; ++i)
+	{
+		if (sections[i].sh_type != SHT_SYMTAB)
+		{
+			continue;
+		}
+		const Elf64_Sym* symbols = (const Elf64_Sym*)(image.data() + sections[i].sh_offset);
+		const char* names = image.data() + sections[sections[i].sh_link].sh_offset;
+		for (size_t k = 0; k < sections[i].sh_size / sizeof(Elf64_Sym); ++k)
+		{
+			const char* name = names + symbols[k].st_name;
+			if (symbols[k].st_value == want && ELF64_ST_TYPE(symbols[k].st_info) == STT_OBJECT && (best == nullptr || strlen(name) < strlen(best)))
+			{
+				best = name;
+			}
+		}
+	}
+	return best;
+}
+
+// a kernel's symbol as the trace names it: demangled, without "void ", the unnamed namespace and the parameter list
+static std::string kernelName(const char* symbol)
+{
+	if (symbol == nullptr)
+	{
+		return "?";
+	}
+	std::string name(symbol);
+	const size_t alias = name.find("__sanitized_padded_global");
+	if (alias != std::string::npos)
+	{
+		name.resize(alias);
+	}
+	int status = 0;
+	if (char* plain = abi::__cxa_demangle(name.c_str(), nullptr, nullptr, &status))
+	{
+		name = plain;
+		free(plain);
+	}
+	for (const char* drop : {"void ", "(anonymous namespace)::"})
+	{
+		for (size_t at = name.find(drop); at != std::string::npos; at = name.find(drop))
+		{
+			name.erase(at, strlen(drop));
+		}
+	}
+	return name.substr(0, name.find('('));
+}
+
+static const char* copyKind(hipMemcpyKind kind)
+{
+	switch (kind)
+	{
+		case hipMemcpyHostToHost:
+			return "HostToHost";
+		case hipMemcpyHostToDevice:
+			return "HostToDevice";
+		case hipMemcpyDeviceToHost:
+			return "DeviceToHost";
+		case hipMemcpyDeviceToDevice:
+			return "DeviceToDevice";
+		default:
+			return "Default";
+	}
+}
 
 extern "C" {
 
@@ -91,8 +204,13 @@ hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind)
 	}
 	return hipSuccess;
 }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t)
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t)
 {
+	if (traceCalls())
+	{
+		printf("COPY %s %zu\n", copyKind(kind), bytes);
+		fflush(stdout);
+	}
 	if (bytes)
 	{
 		memmove(dst, src, bytes);
@@ -109,6 +227,11 @@ hipError_t hipMemset(void* dst, int value, size_t bytes)
 }
 hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t)
 {
+	if (traceCalls())
+	{
+		printf("MEMSET %d %zu\n", value, bytes);
+		fflush(stdout);
+	}
 	if (bytes)
 	{
 		memset(dst, value, bytes);
@@ -127,7 +250,15 @@ hipError_t hipStreamCreate(hipStream_t* stream)
 	return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t)
+{
+	if (traceCalls())
+	{
+		printf("SYNC\n");
+		fflush(stdout);
+	}
+	return hipSuccess;
+}
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { return hipSuccess; }
 hipError_t hipMemcpyPeerAsync(void* dst, int, const void* src, int, size_t bytes, hipStream_t)
@@ -200,6 +331,17 @@ hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void**, size_t
 		// (under ASan a kernel's handle has a second symbol, <name>__sanitized_padded_global: print the kernel's own)
 		const char* alias = named ? strstr(info.dli_sname, "__sanitized_padded_global") : nullptr;
 		printf("LAUNCH %.*s grid %u block %u lds %zu\n", alias != nullptr ? (int)(alias - info.dli_sname) : 1 << 20, named ? info.dli_sname : "?", grid.x, block.x, shared);
+		fflush(stdout);
+	}
+	if (traceCalls())
+	{
+		Dl_info info;
+		const char* name = nullptr;
+		if (dladdr(fn, &info) != 0)
+		{
+			name = info.dli_sname != nullptr && info.dli_saddr == fn ? info.dli_sname : localSymbol(info.dli_fname, info.dli_fbase, fn);
+		}
+		printf("LAUNCH %s grid %u %u block %u lds %zu\n", kernelName(name).c_str(), grid.x, grid.y, block.x, shared);
 		fflush(stdout);
 	}
 	return hipSuccess;
