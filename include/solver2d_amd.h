@@ -1080,6 +1080,91 @@ int s2amd_world_cast_shape(s2amdSolver* solver, const s2amdShapeCast* casts, int
 int s2amd_world_cast_shape_all(s2amdSolver* solver, const s2amdShapeCast* casts, int32_t count, int32_t* offsets /* [count + 1] */,
 							   s2amdShapeCastHit* hits, int32_t capacity, int32_t* total);
 
+/* (additive, API 5) Move-and-slide: "this character wants to go by this displacement: where does it end up, against what did it slide, and
+ * what is left?" asked of the resident world for a batch of movers -- the loop a character controller builds on the shape casts above
+ * (cast, stop a skin short, clip the rest of the displacement to the plane met, cast again), kept on the device: one call, one host
+ * wait, however many bounces.  The reference has no mover; the composition is ours, as the shape casts' is: every distance is the
+ * reference's s2ShapeDistance and every advancement loop is C(q, s) above, unchanged.  The general terms are the scene queries': the
+ * world as it stands, enqueued behind whatever changed it last on the solver's stream, nothing resident written, no host wait added to a
+ * step, no device trees needed, S2AMD_E_STATE without a resident world, count == 0 succeeds and touches nothing, count at most the
+ * queries' batch limit (65535 * 256).  LIVE, PASSES, xf(body), the swept box, C(q, s), target, threshold and CAP are the shape casts'.
+ *   Validation    on the host, for every mover before anything is enqueued: the shape casts' checks of the proxy (1 <= count <= 8,
+ *                 vertices[0 .. count) finite), radius (finite, >= 0), position, rot and translation (finite);
+ *                 1 <= maxIterations <= 8; no flag bit beyond S2AMD_MOVER_STATIC_ONLY; reserved == 0; ignoreBody < the world's body
+ *                 slots (any negative value: none).  One failing mover makes the whole call return S2AMD_E_INVALID with every output
+ *                 untouched.  rot is not checked for normalisation.
+ *   GRAZE         1e-4f.  A displacement r GRAZES a normal N when s2Dot(r, N) >= -(GRAZE * s2Length(r)) -- one multiply and one negation,
+ *                 s2Length as math.h:169-172.  The tolerance is part of the statement, not a tuning knob: with strict sign tests the
+ *                 clipped displacement keeps a residue of one ulp against the normal of the next floor tile, and a box walking over
+ *                 unit boxes laid edge to edge reports a false corner within a few metres.
+ *   The loop      p = position, r = translation, no planes, advances = 0.  For b = 0 .. maxIterations - 1:
+ *                   1. c = {the proxy, p, rot, translation = r, maxFraction = 1.0f, maskBits}.
+ *                   2. The candidates are the cast's candidates for c, minus the shapes whose slot is in the plane list already, minus
+ *                      the shapes with shape.body == ignoreBody, minus -- under S2AMD_MOVER_STATIC_ONLY -- the shapes whose
+ *                      bodies[shape.body].type is not S2AMD_BODY_STATIC.
+ *                   3. A candidate BLOCKS when C(c, s) is a HIT (t, D, k), except when k == 0, N = s2Normalize(s2Sub(D.pointA,
+ *                      D.pointB)) is not the zero vector and r grazes N: the mover touches the shape where it stands and is leaving
+ *                      it or sliding along.
+ *                   4. The winner is the blocker of least t, ties to the lowest slot (the casts' 64-bit key).
+ *                   5. No blocker: p = s2Add(p, r), r = 0, status REACHED, iterations = b + 1, end.
+ *                   6. Otherwise p = s2MulAdd(p, t, r), rem = s2MulSV(1.0f - t, r), advances += k, and the plane {s, s.body, t,
+ *                      D.distance, D.pointB, N} is appended.
+ *                   7. N zero: r = rem, status OVERLAPPED, end.  The mover stands inside something: no normal says which way is out;
+ *                      s2amd_world_deepest_contact does.
+ *                   8. into = s2Dot(rem, N); into < 0: rem = s2MulSub(rem, into, N).
+ *                   9. r = rem.  rem fails to graze the normal of an earlier plane: status CORNERED, end (in two dimensions two planes
+ *                      that both bind leave no motion).
+ *                  10. rem is the zero vector: status BLOCKED, end.
+ *                 The loop running out: status OUT_OF_ITERATIONS.  Then iterations is the number of casts made, remaining = r,
+ *                 planeCount the number of planes, and planes[i * 8 + j] for j >= planeCount is zero bytes.
+ *   The skin      The shapes of recorded planes are no candidates any more.  That is sound: every shape is convex and r is kept within
+ *                 their half-planes.  A mover comes closer to a recorded plane than where it stopped (target, 0.005) only by the
+ *                 rounding of step 8, or by at most GRAZE times the distance travelled while it slides along one.  The next call
+ *                 restores the skin wherever its displacement has a component into the plane: its first cast stops at target again.
+ * All arithmetic is fp32 in the reference's operation order without contraction, with correctly rounded divide and square root, in
+ * libs2amd.so and in libs2amd_fast.so alike.  Not offered: rotation of the mover, pushing dynamic bodies, step-up and step-down, movers
+ * or answers in device memory, sharded worlds, the device trees as an accelerator. */
+#define S2AMD_MOVER_MAX_ITERATIONS 8
+#define S2AMD_MOVER_STATIC_ONLY 1		/* flags: only shapes on S2AMD_BODY_STATIC bodies are candidates */
+#define S2AMD_MOVER_REACHED 0			/* the last cast met nothing: the whole remaining displacement was spent */
+#define S2AMD_MOVER_BLOCKED 1			/* the clip left a zero displacement */
+#define S2AMD_MOVER_CORNERED 2			/* the clipped displacement heads into an earlier plane */
+#define S2AMD_MOVER_OVERLAPPED 3		/* the winner overlaps the mover where it stands: no normal, no move */
+#define S2AMD_MOVER_OUT_OF_ITERATIONS 4 /* maxIterations casts made and displacement left */
+typedef struct s2amdMover /* 128 bytes */
+{
+	float vertices[8][2];  /* the proxy, as s2amdShapeCast's */
+	int32_t count;		   /* 1..8 */
+	float radius;		   /* >= 0 */
+	float position[2];	   /* where the mover stands */
+	float rot[2];		   /* q {s, c}; the mover does not rotate; not checked for normalisation */
+	float translation[2];  /* the displacement wanted this call */
+	int32_t maxIterations; /* 1..8 casts */
+	uint32_t maskBits;
+	int32_t ignoreBody;	   /* shapes of this body slot are not candidates (the character's own body); < 0: none */
+	uint32_t flags;		   /* S2AMD_MOVER_STATIC_ONLY or 0 */
+	int32_t reserved[4];   /* 0 */
+} s2amdMover;
+typedef struct s2amdMoverResult /* 32 bytes */
+{
+	float position[2];	/* p: where the mover ends */
+	float remaining[2]; /* r: the displacement not spent */
+	int32_t status;		/* S2AMD_MOVER_* */
+	int32_t planeCount; /* planes recorded, 0..8 */
+	int32_t iterations; /* casts made, 1..maxIterations */
+	int32_t advances;	/* the sum of the winners' k */
+} s2amdMoverResult;
+typedef struct s2amdMoverPlane /* 32 bytes */
+{
+	int32_t shape, body;
+	float fraction;	 /* t: of the displacement that was left when the plane was met */
+	float distance;	 /* D.distance where the mover stopped */
+	float point[2];	 /* D.pointB: on the world shape */
+	float normal[2]; /* from the world shape towards the mover; zero when they overlap */
+} s2amdMoverPlane;
+int s2amd_world_move_shapes(s2amdSolver* solver, const s2amdMover* movers, int32_t count, s2amdMoverResult* results /* [count] */,
+							s2amdMoverPlane* planes /* [count * 8], may be NULL */);
+
 /* (additive, API 5) World edits: the reference's eight cheap setters an interactive program calls every frame -- a body dragged by the
  * mouse joint, a motor whose speed follows a controller, wind, a thrown ball, an explosion -- applied to the resident world where it
  * lies.  Nothing is downloaded, nothing uploaded again and the constraint-graph structure is kept: no colouring, strip table or tree

@@ -1,6 +1,7 @@
 // The host side that the eight queries on the resident world share (scene_query.hip, proximity_query.hip, contact_query.hip,
-// shape_cast.hip; DESIGN.md: "The query facility"): how a call opens, the carver over the solver's query block, and the two drivers --
-// queryBest, one answer per query, and queryLists, a list per query.  A query file supplies its kind (record size, the nouns of its error
+// shape_cast.hip; DESIGN.md: "The query facility") and move-and-slide (mover_query.hip): how a call opens, the carver over the solver's query
+// block, and the three drivers -- queryBest, one answer per query, queryLists, a list per query, and queryRounds, one answer per query found
+// in several rounds of casts.  A query file supplies its kind (record size, the nouns of its error
 // texts, its validator, what it stages on the device) and small functions that launch its own kernels with their own argument lists; its
 // extern "C" bodies are one call into this header each.  Included after query_list.h, whose kernels queryLists launches: everything is in
 // an unnamed namespace, so each file drives its own copy of them.
@@ -280,6 +281,81 @@ inline int queryLists(s2amdSolver* s, const QueryKind& kind, const void* records
 			std::memcpy(beside, s->hQueryStage.data() + count + 1 + entries, (size_t)*total * sizeof(float));
 		}
 	}
+	return S2AMD_OK;
+}
+
+// what a call in rounds is made of, beside its kind (whose two staged arrays are the state the rounds work on, filled by kind.stage)
+struct QueryRounds
+{
+	bool (*fits)(const s2amdSolver*, const void*); // one record against the resident world, after kind.valid has passed them all
+	const char* fitsRule;						   // "<singular> <index> <fitsRule>"
+	int (*rounds)(const void* records, int32_t count);
+	size_t answerBytes, detailBytes; // per query: the answer, and the details behind it that the caller may decline (a null array)
+	void (*candidates)(const QueryCall&, unsigned long long* keys);
+	void (*advance)(const QueryCall&, unsigned long long* keys, void* answers, void* details);
+};
+
+// One answer per query that takes several casts to find, each from where the last one ended: {records, staged, keys, answers, details}
+// in the block; the upload, the keys to the no-hit key, the answers and details to zero bytes, the stage kernel, then `rounds` times the
+// candidates pass (not launched on a world without shape slots) and the advance pass, which consumes the keys and leaves them the no-hit
+// key again -- no host wait in between.  One copy back and one wait: the answers straight into the caller's array when it declines the
+// details, otherwise both into hQueryStage, split on the host.
+inline int queryRounds(s2amdSolver* s, const QueryKind& kind, const void* records, int32_t count, void* answers, void* details, const QueryRounds& passes)
+{
+	bool proceed;
+	if (int rc = queryOpen(s, queryBestArguments(s, records, count, answers), kind, records, count, &proceed))
+	{
+		return rc;
+	}
+	if (!proceed)
+	{
+		return S2AMD_OK;
+	}
+	for (int32_t i = 0; i < count; ++i)
+	{
+		if (!passes.fits(s, (const char*)records + (size_t)i * kind.stride))
+		{
+			return fail(S2AMD_E_INVALID, std::string(kind.singular) + " " + std::to_string(i) + " " + passes.fitsRule);
+		}
+	}
+	const size_t answersBytes = (size_t)count * passes.answerBytes, outBytes = answersBytes + (size_t)count * passes.detailBytes;
+	size_t at = 0;
+	const QueryInput in = queryTakeInput(at, kind, count);
+	const size_t keysAt = queryTake(at, (size_t)count * sizeof(unsigned long long));
+	const size_t outAt = queryTake(at, outBytes);
+	HIP_TRY(hipSetDevice(s->device));
+	if (int rc = s->dQuery.ensure(at))
+	{
+		return rc;
+	}
+	char* base = (char*)s->dQuery.p;
+	const QueryCall call = queryCallOn(s, kind, in, count);
+	unsigned long long* keys = (unsigned long long*)(base + keysAt);
+	HIP_TRY(hipMemcpyAsync(base + in.records, records, (size_t)count * kind.stride, hipMemcpyHostToDevice, call.stream));
+	HIP_TRY(hipMemsetAsync(keys, 0xff, (size_t)count * sizeof(unsigned long long), call.stream));
+	HIP_TRY(hipMemsetAsync(base + outAt, 0, outBytes, call.stream));
+	kind.stage(call);
+	const int rounds = passes.rounds(records, count);
+	for (int round = 0; round < rounds; ++round)
+	{
+		if (call.tiles > 0)
+		{
+			passes.candidates(call, keys);
+		}
+		passes.advance(call, keys, base + outAt, base + outAt + answersBytes);
+	}
+	HIP_TRY(hipGetLastError());
+	if (details == nullptr)
+	{
+		HIP_TRY(hipMemcpyAsync(answers, base + outAt, answersBytes, hipMemcpyDeviceToHost, call.stream));
+		HIP_TRY(hipStreamSynchronize(call.stream));
+		return S2AMD_OK;
+	}
+	s->hQueryStage.resize((outBytes + sizeof(int32_t) - 1) / sizeof(int32_t));
+	HIP_TRY(hipMemcpyAsync(s->hQueryStage.data(), base + outAt, outBytes, hipMemcpyDeviceToHost, call.stream));
+	HIP_TRY(hipStreamSynchronize(call.stream));
+	std::memcpy(answers, s->hQueryStage.data(), answersBytes);
+	std::memcpy(details, (const char*)s->hQueryStage.data() + answersBytes, outBytes - answersBytes);
 	return S2AMD_OK;
 }
 

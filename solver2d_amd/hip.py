@@ -34,7 +34,7 @@ EXPORTS = [
     "s2amd_world_ray_cast", "s2amd_world_point_probe", "s2amd_world_query_boxes",
     "s2amd_world_closest_shape", "s2amd_world_shapes_in_range",
     "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
-    "s2amd_world_cast_shape", "s2amd_world_cast_shape_all",
+    "s2amd_world_cast_shape", "s2amd_world_cast_shape_all", "s2amd_world_move_shapes",
     "s2amd_world_edit", "s2amd_world_apply_fields", "s2amd_world_set_fields", "s2amd_world_field_states",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
@@ -136,6 +136,7 @@ def load(fast=False):
     L.s2amd_world_deepest_contact.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_cast_shape.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_cast_shape_all.argtypes = [vp, vp, i32, vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_move_shapes.argtypes = [vp, vp, i32, vp, vp]
     L.s2amd_world_edit.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_apply_fields.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_set_fields.argtypes = [vp, vp, i32]
@@ -532,6 +533,17 @@ class Solver:
         states when it answers S2AMD_E_CAPACITY."""
         return self._world_lists(self._L.s2amd_world_cast_shape_all, casts, wire.shape_cast_dtype, wire.shape_cast_hit_dtype, expected or 4 * len(casts) + 64,
                                  distances=None)
+
+    # ---- move-and-slide on the resident world: cast, stop a skin short, clip to the plane met, cast again -- all on the device ----
+    def world_move_shapes(self, movers, planes=True):
+        """Where every mover (wire.mover_dtype) ends and what it slid against -> (wire.mover_result_dtype[len(movers)],
+        wire.mover_plane_dtype[len(movers), 8]); with planes=False the library is given no plane array and the answer is the results."""
+        movers = np.ascontiguousarray(movers)
+        assert movers.dtype == wire.mover_dtype
+        results = np.zeros(len(movers), dtype=wire.mover_result_dtype)
+        out = np.zeros((len(movers), wire.MOVER_MAX_ITERATIONS), dtype=wire.mover_plane_dtype) if planes else None
+        self._ck(self._L.s2amd_world_move_shapes(self._h, wire.as_ptr(movers), len(movers), wire.as_ptr(results), wire.as_ptr(out) if planes else None))
+        return (results, out) if planes else results
 
     # ---- world edits: the reference's eight per-frame setters applied to the resident records, the structure kept ----
     def world_edit(self, edits, want_skipped=True):

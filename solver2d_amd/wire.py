@@ -275,6 +275,19 @@ shape_cast_hit_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("frac
 SHAPE_CAST_SIZE, SHAPE_CAST_HIT_SIZE = shape_cast_dtype.itemsize, shape_cast_hit_dtype.itemsize
 assert SHAPE_CAST_SIZE == 112 and SHAPE_CAST_HIT_SIZE == 48
 
+# move-and-slide on the resident world (include/solver2d_amd.h: s2amd_world_move_shapes): s2amdMover, s2amdMoverResult, s2amdMoverPlane
+mover_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("count", np.int32), ("radius", np.float32), ("position", np.float32, 2),
+                        ("rot", np.float32, 2), ("translation", np.float32, 2), ("maxIterations", np.int32), ("maskBits", np.uint32),
+                        ("ignoreBody", np.int32), ("flags", np.uint32), ("reserved", np.int32, 4)])
+mover_result_dtype = np.dtype([("position", np.float32, 2), ("remaining", np.float32, 2), ("status", np.int32), ("planeCount", np.int32),
+                               ("iterations", np.int32), ("advances", np.int32)])
+mover_plane_dtype = np.dtype([("shape", np.int32), ("body", np.int32), ("fraction", np.float32), ("distance", np.float32),
+                              ("point", np.float32, 2), ("normal", np.float32, 2)])
+MOVER_SIZE, MOVER_RESULT_SIZE, MOVER_PLANE_SIZE = mover_dtype.itemsize, mover_result_dtype.itemsize, mover_plane_dtype.itemsize
+assert MOVER_SIZE == 128 and MOVER_RESULT_SIZE == 32 and MOVER_PLANE_SIZE == 32
+MOVER_MAX_ITERATIONS, MOVER_STATIC_ONLY = 8, 1
+MOVER_REACHED, MOVER_BLOCKED, MOVER_CORNERED, MOVER_OVERLAPPED, MOVER_OUT_OF_ITERATIONS = 0, 1, 2, 3, 4
+
 # world edits on the resident world (include/solver2d_amd.h: s2amd_world_edit): s2amdWorldEdit and the S2AMD_EDIT_* kinds
 world_edit_dtype = np.dtype([("kind", np.int32), ("target", np.int32), ("flag", np.int32), ("reserved", np.int32), ("v", np.float32, 4)])
 WORLD_EDIT_SIZE = world_edit_dtype.itemsize
