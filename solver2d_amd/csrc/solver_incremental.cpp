@@ -867,7 +867,7 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 		if (!removeEntry(s, p, ch.slot))
 		{
 			// (an entry in an LDS group's tables, unless strips hold it: SolverRest::groupPatienceNow)
-			s->dirtyByGroups = inc.positionOfSlot[(size_t)ch.slot] == -2 && (ownedByLdsGroup(s, s->hContactA[(size_t)ch.slot]) || ownedByLdsGroup(s, s->hContactB[(size_t)ch.slot]));
+			s->dirtyByGroups = s->dirtyByGroups || (inc.positionOfSlot[(size_t)ch.slot] == -2 && (ownedByLdsGroup(s, s->hContactA[(size_t)ch.slot]) || ownedByLdsGroup(s, s->hContactB[(size_t)ch.slot])));
 			return giveUp("old entry of the slot not removable");
 		}
 		if (ch.a < 0)
@@ -895,7 +895,7 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 				unwatchSlot(s, ch.slot);
 				continue;
 			}
-			s->dirtyByGroups = ownedByLdsGroup(s, ch.a) || ownedByLdsGroup(s, ch.b);
+			s->dirtyByGroups = s->dirtyByGroups || ownedByLdsGroup(s, ch.a) || ownedByLdsGroup(s, ch.b);
 			return giveUp("body owned by a group or strip");
 		}
 		inc.placedInGlobalPart = true;

@@ -251,3 +251,128 @@ def wreck_world(seed, base):
     pairs["shapeA"][len(w["pairs"]):] = -1
     pairs["shapeB"][len(w["pairs"]):] = -1
     return {"bodies": bodies, "contacts": contacts, "joints": w["joints"], "shapes": shapes, "pairs": pairs, "origins": origins}
+
+
+def churn_world(pieces, balls, ball_radius=0.6):
+    """Several synthetic.pyramid_world pieces in one world, with wreck_world's heavy balls and spare slots: the worlds of
+    tests/test_gpu_group_patience.py.
+    pieces: (base, x, y) per pyramid, the offset of its ground's centre line (whole numbers keep the fp32 sums exact); body,
+    shape, pair and contact indices are offset piece by piece, every proxyKey is (shape index << 4) | body type as in
+    wreck_world, and each ground is as wide as its pyramid plus 5 m a side (pyramid_world's grounds for many pyramids), so
+    that no box ever meets a neighbour's ground.
+    balls: (piece, delay, speed) per ball, a circle of wreck_world's density: it comes down on the middle of the top box of
+    that piece and starts so high that gravity has brought it to the speculative distance after `delay` steps, with `speed`
+    m/s downwards (its manifold has points one step later) -- a push a pile takes without a box leaving its place, so the
+    graph is quiet again once the last ball has landed.  The ball must start above where it lands.
+    Returns the world and, per ball, its body index."""
+    from solver2d_amd import synthetic
+    cache = {}
+    parts = {k: [] for k in WORLD_KEYS}
+    nb = nc = 0
+    tops = []
+    for base, x, y in pieces:
+        if base not in cache:
+            cache[base] = synthetic.pyramid_world(base)
+        w = copy_world(cache[base])
+        off = np.array([x, y], dtype=np.float32)
+        w["bodies"]["position"] = (w["bodies"]["position"] + off).astype(np.float32)
+        w["origins"] = (w["origins"] + off).astype(np.float32)
+        w["contacts"]["bodyA"] += nb
+        w["contacts"]["bodyB"] += nb
+        w["pairs"]["shapeA"] += nb  # (one shape per body, same index)
+        w["pairs"]["shapeB"] += nb
+        for i in range(len(w["shapes"])):
+            b = w["bodies"][i]
+            static = b["type"] == wire.BODY_STATIC
+            synthetic._box_shape(w["shapes"][i], nb + i, b["type"], 0.5 * base + 5.0 if static else 0.5, 1.0 if static else 0.5,
+                                 b["position"][0], b["position"][1], nb + i)
+        top = int(np.argmax(w["bodies"]["position"][:, 1]))
+        tops.append((nb + top, float(w["bodies"]["position"][top, 0]), float(w["bodies"]["position"][top, 1]) + 0.5))
+        for k in WORLD_KEYS:
+            parts[k].append(w[k])
+        nb += len(w["bodies"])
+        nc += len(w["contacts"])
+    bodies = np.concatenate(parts["bodies"] + [np.zeros(len(balls), dtype=wire.body_dtype)])
+    shapes = np.concatenate(parts["shapes"] + [np.zeros(len(balls), dtype=wire.shape_dtype)])
+    origins = np.concatenate(parts["origins"] + [np.zeros((len(balls), 2), dtype=np.float32)])
+    dt, gravity = 1.0 / 60.0, -10.0
+    r = np.float32(ball_radius)
+    ball_ids = []
+    for k, (piece, delay, speed) in enumerate(balls):
+        i = nb + k
+        _, x, top = tops[piece]
+        # back from the touch: `delay` steps of v += g dt, y += v dt end at the top box with -speed
+        v0 = -speed - gravity * dt * delay
+        drop = sum((v0 + gravity * dt * (n + 1)) * dt for n in range(delay))
+        assert drop < 0.0, "ball %d would start inside the pile" % k
+        yb = top + float(r) + float(synthetic.SPECULATIVE_DISTANCE) - drop
+        mass = np.float32(20.0 * np.pi * r * r)
+        synthetic._dynamic_body(bodies[i], x, yb, mass, np.float32(0.5 * mass * r * r))
+        bodies[i]["linearVelocity"] = (0.0, v0)
+        sh = shapes[i]
+        sh["body"], sh["type"] = i, wire.SHAPE_CIRCLE
+        sh["categoryBits"], sh["maskBits"] = 1, 0xFFFFFFFF
+        sh["proxyKey"] = (i << 4) | wire.BODY_DYNAMIC
+        sh["radius"] = r
+        m = np.float32(synthetic.AABB_MARGIN)
+        px, py = bodies[i]["position"]
+        sh["aabb"] = (px - r, py - r, px + r, py + r)
+        sh["fatAABB"] = (px - r - m, py - r - m, px + r + m, py + r + m)
+        sh["enlarged"] = 1
+        origins[i] = (px, py)
+        ball_ids.append(i)
+    extra = 4 * nc // 3 + 256
+    contacts = np.concatenate(parts["contacts"] + [np.zeros(extra, dtype=wire.contact_dtype)])
+    contacts["constraintIndex"][nc:] = -1
+    pairs = np.concatenate(parts["pairs"] + [np.zeros(extra, dtype=wire.pair_state_dtype)])
+    pairs["shapeA"][nc:] = -1
+    pairs["shapeB"][nc:] = -1
+    world = {"bodies": bodies, "contacts": contacts, "joints": np.zeros(0, dtype=wire.joint_dtype), "shapes": shapes, "pairs": pairs,
+             "origins": origins}
+    return world, ball_ids
+
+
+# The balls of the two churn worlds, (piece, delay, speed), and what the structure policy makes of them (solver_internal.h:
+# noteGraphChanged; a contact created on a body that an LDS group or resident island holds is only watched until its manifold
+# has points, one created elsewhere takes a place at once):
+#   the first is created after the first structure build and touches in step 6, while that structure is younger than 8
+#   steps: the groups die young, the patience rises;
+#   the next three touch in steps 9, 12 and 15, their contacts created in steps 5, 7 and 10, while the groups are away or
+#   about to go: one that takes a place in the global part makes the wait begin again (the groups were seen back in step 11
+#   under the soft solvers, in step 14 on the op interpreter);
+#   the last is created in step 16, when the groups are back, and touches in step 20: the groups go once more, and come back
+#   a full patience after that touch -- the last change of the graph, since nothing here leaves its place.
+# Balls of radius 0.15 (1.4 kg on boxes of 1 kg): what a base-10 pyramid takes without a manifold anywhere in it losing or
+# gaining its points afterwards under all five solvers the GPU tests run (PGS_NGS_Block and XPBD let a pile under a ball of
+# radius 0.3 flicker within 20 steps, PGS_Soft under one of radius 0.6; measured on the oracle chain in pool order).
+CHURN_BALLS = ((3, 5, 3.0), (17, 8, 2.0), (12, 11, 2.0), (8, 14, 2.0), (15, 19, 3.0))
+CHURN_BALL_RADIUS = 0.15
+
+
+def debris_world(count=120):
+    """`count` base-10 pyramids (55 boxes, 145 manifolds each) on a lattice 32 wide, nothing bigger: 17,400 active constraints
+    at 120, 8,700 at 60 (below S2_GROUP_PATIENCE_MIN_POSITIONS).  Balls on five of the pyramids."""
+    pieces = [(10, 30.0 * (k % 32), 30.0 * (k // 32)) for k in range(count)]
+    return churn_world(pieces, CHURN_BALLS, CHURN_BALL_RADIUS)
+
+
+def pile_and_debris_world(small=14):
+    """One base-100 pyramid (5,050 boxes in one island: strips) with `small` base-10 pyramids in a row beside it: 14,950 +
+    145 per small one active constraints.  The balls land on small pyramids only (piece 0 is the pile)."""
+    pieces = [(100, 0.0, 0.0)] + [(10, 90.0 + 30.0 * k, 0.0) for k in range(small)]
+    targets = (2, 5, 8, 11, 14)
+    assert small >= max(targets)
+    return churn_world(pieces, tuple((t, d, v) for t, (_, d, v) in zip(targets, CHURN_BALLS)), CHURN_BALL_RADIUS)
+
+
+def island_census(world):
+    """What solver2d_amd/islands.py finds in a world: the active sweep positions (manifolds with points + joints), and bodies
+    and constraints per island that has a constraint at all (a ball in flight is an island too, but nothing to group)."""
+    from solver2d_amd import islands
+    b, c, j = world["bodies"], world["contacts"], world["joints"]
+    island, n = islands.find_islands(b, c, j)
+    ci, ji = islands.constraint_islands(b, c, j, island)
+    per_body = np.bincount(island[island >= 0], minlength=n)
+    per_constraint = np.bincount(ci[ci >= 0], minlength=n) + np.bincount(ji[ji >= 0], minlength=n)
+    held = per_constraint > 0
+    return {"positions": int((c["pointCount"] > 0).sum()) + int((j["type"] >= 0).sum()), "bodies": per_body[held], "constraints": per_constraint[held]}
