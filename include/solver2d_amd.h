@@ -950,6 +950,83 @@ int s2amd_world_sensor_events(s2amdSolver* solver, s2amdSensorEvent* entered, in
 							  int32_t leftCapacity, int32_t* leftCount);
 int s2amd_world_sensor_states(s2amdSolver* solver, s2amdSensorState* out, int32_t capacity, int32_t* count);
 
+/* (additive, API 5) Ray sensors: "what does this ray see now, and did that change during the step?" -- a range finder or a lidar fan on
+ * a robot, a suspension ray under a wheel, a ground probe under a character, a line of sight between two bodies.  A list of up to
+ * S2AMD_MAX_RAY_SENSORS rays, each fixed in the world or mounted on a body, is cast on the resident arrays behind stage 4 of every
+ * s2amd_world_step (a step the library repeats internally reports once), after the other six reports; the report owns its "before"
+ * state on the device.  It replaces, per step, a pose read-back (s2amd_world_download_step), the host's own s2TransformPoint on both
+ * ends and a s2amd_world_ray_cast call.  With no flag set a step enqueues nothing for the rays; the step gains no host wait, the
+ * getters wait.  LIVE, xf(body) and PASSES are the scene queries' definitions; every answer is an order-free statement:
+ *   Validation    on the host, in s2amd_world_set_ray_sensors, before anything is changed: 0 <= count <= S2AMD_MAX_RAY_SENSORS; per ray
+ *                 s2IsValidRay (src/geometry.c:15-20) on the local {p1, p2, maxFraction}; no flag bits beyond the two below; body <
+ *                 bodyCapacity of the resident world (with no world resident, body is not bounded).  One bad record refuses the whole
+ *                 list with S2AMD_E_INVALID, and the old list stands.  The list holds across uploads; a ray whose body is outside the new
+ *                 world's bodyCapacity is inactive there.
+ *   World ray     body < 0: the ends as given.  Otherwise P = s2TransformPoint(xf(body), p) (include/solver2d/math.h:350-356) on both
+ *                 ends.  maxFraction is unchanged.
+ *   Active        not S2AMD_RAY_SENSOR_DISABLED; body < 0 or (body < bodyCapacity and bodies[body].type != S2AMD_BODY_FREE); and the
+ *                 world ray satisfies s2IsValidRay -- a body with a non-finite pose switches its rays off, it does not poison the answers.
+ *   Answer        s2amd_world_ray_cast's statement for {P1, P2, maxFraction, maskBits} -- the same segment box, "no other pruning
+ *                 decides a result", the least fraction as float values with ties to the lowest slot, point from the world-space ends,
+ *                 normal = s2RotateVector(rot, output.normal) -- with two further exclusions from the candidates: for a mounted ray
+ *                 (body >= 0) the shapes with shape.body == ray.body, so that it never hits its own body; with
+ *                 S2AMD_RAY_SENSOR_SKIP_STATIC the shapes with bodies[shape.body].type == S2AMD_BODY_STATIC.
+ *   STATES        s2amd_world_ray_states: one record per ray in list order.  A miss has shape = hitBody = -1, fraction = maxFraction,
+ *                 point and normal +0.  An inactive ray has the same, plus active = 0 and p1, p2 +0.  body is the ray's own.
+ *                 shapeBefore is filled whatever other flags are set.
+ *   RANGES        s2amd_world_ray_ranges: one float per ray in list order, the state's fraction -- the observation vector.
+ *                 s2amd_world_export_ray_ranges copies the same bytes into a caller's device buffer (s2amd_device_alloc or any
+ *                 allocation of the solver's device) behind the step on the solver's stream, device to device, and returns when the
+ *                 copy is done, as s2amd_export_poses; capacity counts floats.
+ *   EVENTS        s2amd_world_ray_events: the rays with shapeNow != shapeBefore, ascending by ray; bodyNow = the hit shape's body or
+ *                 -1.  Hit to miss, miss to hit and shape to shape are all events.  A ray that turned inactive counts as a miss.
+ *   "Before"      the same rule evaluated at s2amd_world_upload, when the report is turned on, and whenever
+ *                 s2amd_world_set_ray_sensors succeeds on a resident world: the caller's own acts raise no events.  Each of these voids
+ *                 the last step's report, as with the sensors: the getters answer S2AMD_E_STATE until the next step.
+ *   Errors        those of the other reports: S2AMD_E_STATE without a resident world, when the getter's flag was not set before the
+ *                 last step, or when no step has run since; S2AMD_E_CAPACITY with *count filled and nothing consumed; unknown flag bits
+ *                 give S2AMD_E_INVALID.
+ *   Memory        196 bytes per ray (the list 48, the posed ray 48, the key 8, the state 64, the range 4, "before" and "now" 8, one
+ *                 event 16), 32 bytes per group of 64 rays (its box) and per 256 rays (their ballots), each piece rounded up to 256
+ *                 bytes: 3.1 MiB for 16,384 rays.  s2amd_world_set_ray_sensors on a resident world with the report on waits for the
+ *                 stream once (the list is copied to the device before the call returns).
+ * The reference has no ray sensors: the composition is ours; every cast is the reference's s2RayCast<type> bit for bit.  All arithmetic is
+ * fp32 in the reference's operation order without contraction, in libs2amd.so and in libs2amd_fast.so alike.  Not offered: all-hits
+ * or sorted results, rays in device memory, sharded worlds, forces applied along a ray. */
+#define S2AMD_MAX_RAY_SENSORS 16384
+#define S2AMD_RAY_SENSOR_DISABLED 1	   /* sees nothing, raises no events */
+#define S2AMD_RAY_SENSOR_SKIP_STATIC 2 /* shapes on static bodies are not candidates */
+typedef struct s2amdRaySensor /* 48 bytes */
+{
+	float p1[2], p2[2]; /* in the world (body < 0) or in the body's frame */
+	float maxFraction;
+	uint32_t maskBits;
+	int32_t body;  /* < 0: fixed in the world */
+	int32_t flags; /* S2AMD_RAY_SENSOR_* */
+	int32_t pad[4];
+} s2amdRaySensor;
+int s2amd_world_set_ray_sensors(s2amdSolver* solver, const s2amdRaySensor* rays, int32_t count); /* replaces the whole list; count 0 clears */
+#define S2AMD_RAY_REPORT_STATES 1
+#define S2AMD_RAY_REPORT_RANGES 2
+#define S2AMD_RAY_REPORT_EVENTS 4
+int s2amd_world_set_ray_report(s2amdSolver* solver, int32_t flags);
+typedef struct s2amdRayState /* 64 bytes */
+{
+	int32_t ray, body, active, shape, hitBody, shapeBefore;
+	float fraction;
+	float p1[2], p2[2]; /* the world ray used */
+	float point[2], normal[2];
+	int32_t pad;
+} s2amdRayState;
+typedef struct s2amdRayEvent /* 16 bytes */
+{
+	int32_t ray, shapeBefore, shapeNow, bodyNow;
+} s2amdRayEvent;
+int s2amd_world_ray_states(s2amdSolver* solver, s2amdRayState* out, int32_t capacity, int32_t* count);
+int s2amd_world_ray_ranges(s2amdSolver* solver, float* out, int32_t capacity, int32_t* count);
+int s2amd_world_export_ray_ranges(s2amdSolver* solver, void* deviceRanges, int32_t capacity); /* device-to-device, as s2amd_export_poses */
+int s2amd_world_ray_events(s2amdSolver* solver, s2amdRayEvent* out, int32_t capacity, int32_t* count);
+
 /* (additive, API 5) Contact queries: "if this shape stood here, what would it touch, where, and how deep?" asked of the resident world
  * -- a character controller, a ghost or trigger shape, spawn placement with push-out, a "will this fit" test.  The reference answers it
  * with its nine manifold functions s2Collide* (include/solver2d/manifold.h:56-85), dispatched by s_registers (src/contact.c:139-151);

@@ -587,6 +587,11 @@ struct SolverRest
 	int sensorListCapacity = 0;		   // entries of each of the three device lists a step writes
 	int sensorNowSet = 0;			   // which of the two ping-pong mask sets holds "now" of the last evaluation ("before" of the next)
 	int32_t hSensorReportHead[4] = {0, 0, 0, 0}; // {inside, entered, left, 0}: the totals over all sensors
+	// ray report (ray_report.hip; s2amd_world_set_ray_sensors, s2amd_world_set_ray_report: S2AMD_RAY_REPORT_*): the seventh of a step
+	ReportState rayReport;
+	std::vector<s2amdRaySensor> hRaySensors; // the list as the caller set it: held across uploads, copied into the block by every prepare
+	int rayNowSet = 0;						 // which of the two ping-pong hit-shape arrays holds "now" of the last evaluation ("before" of the next)
+	int32_t hRayReportHead[4] = {0, 0, 0, 0}; // {events, 0, 0, 0}
 	// force fields (force_field.hip; s2amd_world_apply_fields, s2amd_world_set_fields, s2amd_world_field_states): no report -- a write in
 	// front of stage 3 -- but kept and released beside them
 	std::vector<s2amdField> hFields; // the persistent list as the caller set it: held across uploads
@@ -839,7 +844,7 @@ int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
 // The reports behind s2amd_world_step.  Each file keeps its layout, kernels, prepare and enqueue; report_host.cpp holds the table of
-// the six in step order and what their host sides share.
+// the seven in step order and what their host sides share.
 //   <x>Prepare   the report's device block for the resident world and its "before" state from the arrays just uploaded
 //   <x>Enqueue   the step's passes on the step's stream, behind stage 4 of the attempt that stands (never part of the captured graph)
 int contactReportPrepare(s2amdSolver* s);
@@ -856,6 +861,8 @@ int metricsPrepare(s2amdSolver* s); // (restarts the recorder as well)
 int metricsEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int sensorReportPrepare(s2amdSolver* s);
 int sensorReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+int rayReportPrepare(s2amdSolver* s);
+int rayReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 // force_field.hip: the persistent list in front of stage 3 (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
 int fieldsStepEnqueue(s2amdSolver* s);
 void fieldsForgetWorld(s2amdSolver* s);

@@ -37,6 +37,8 @@ EXPORTS = [
     "s2amd_world_cast_shape", "s2amd_world_cast_shape_all", "s2amd_world_move_shapes",
     "s2amd_world_edit", "s2amd_world_apply_fields", "s2amd_world_set_fields", "s2amd_world_field_states",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
+    "s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
+    "s2amd_world_ray_events",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -146,6 +148,12 @@ def load(fast=False):
     L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_sensor_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32), vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_sensor_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_set_ray_sensors.argtypes = [vp, vp, i32]
+    L.s2amd_world_set_ray_report.argtypes = [vp, i32]
+    L.s2amd_world_ray_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_ray_ranges.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_export_ray_ranges.argtypes = [vp, vp, i32]
+    L.s2amd_world_ray_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -772,6 +780,34 @@ class Solver:
     def world_sensor_states(self, expected=None):
         """wire.sensor_state_dtype records, one per sensor in list order, after the last world_step."""
         return self._world_list(self._L.s2amd_world_sensor_states, wire.sensor_state_dtype, expected or getattr(self, "_world_sensors", 0))
+
+    # ---- ray report of the resident world (s2amd_world_set_ray_sensors, s2amd_world_set_ray_report): states, ranges, events ----
+    def world_set_ray_sensors(self, rays):
+        """Replaces the whole list of ray sensors (wire.ray_sensor_dtype; an empty one clears it).  The list holds across uploads."""
+        rays = np.ascontiguousarray(rays)
+        assert rays.dtype == wire.ray_sensor_dtype
+        self._ck(self._L.s2amd_world_set_ray_sensors(self._h, wire.as_ptr(rays) if len(rays) else None, len(rays)))
+        self._world_rays = len(rays)
+
+    def world_set_ray_report(self, flags):
+        """wire.RAY_REPORT_* bits: what every world_step from the next one on casts on the device (0: nothing, the default)."""
+        self._ck(self._L.s2amd_world_set_ray_report(self._h, int(flags)))
+
+    def world_ray_states(self, expected=None):
+        """wire.ray_state_dtype records, one per ray in list order, after the last world_step."""
+        return self._world_list(self._L.s2amd_world_ray_states, wire.ray_state_dtype, expected or getattr(self, "_world_rays", 0))
+
+    def world_ray_ranges(self, expected=None):
+        """float32[rays]: the hit fraction (maxFraction on a miss) of every ray in list order, after the last world_step."""
+        return self._world_list(self._L.s2amd_world_ray_ranges, np.float32, expected or getattr(self, "_world_rays", 0))
+
+    def world_export_ray_ranges(self, device_ptr, capacity):
+        """world_ray_ranges' bytes into a device buffer (device_alloc, or a torch tensor's data_ptr()) of `capacity` floats."""
+        self._ck(self._L.s2amd_world_export_ray_ranges(self._h, ctypes.c_void_p(int(device_ptr)), int(capacity)))
+
+    def world_ray_events(self, expected=64):
+        """wire.ray_event_dtype records of the rays whose hit shape changed in the last world_step, ascending by ray."""
+        return self._world_list(self._L.s2amd_world_ray_events, wire.ray_event_dtype, expected)
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

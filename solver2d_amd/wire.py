@@ -255,6 +255,21 @@ sensor_state_dtype = np.dtype([("sensor", np.int32), ("body", np.int32), ("activ
 SENSOR_SIZE, SENSOR_EVENT_SIZE, SENSOR_STATE_SIZE = sensor_dtype.itemsize, sensor_event_dtype.itemsize, sensor_state_dtype.itemsize
 assert SENSOR_SIZE == 112 and SENSOR_EVENT_SIZE == 16 and SENSOR_STATE_SIZE == 64
 
+# ray report of the resident world (include/solver2d_amd.h: s2amd_world_set_ray_sensors, s2amd_world_set_ray_report)
+MAX_RAY_SENSORS = 16384
+RAY_SENSOR_DISABLED, RAY_SENSOR_SKIP_STATIC = 1, 2
+RAY_REPORT_STATES, RAY_REPORT_RANGES, RAY_REPORT_EVENTS = 1, 2, 4
+RAY_REPORT_ALL = RAY_REPORT_STATES | RAY_REPORT_RANGES | RAY_REPORT_EVENTS
+# s2amdRaySensor, s2amdRayState, s2amdRayEvent
+ray_sensor_dtype = np.dtype([("p1", np.float32, 2), ("p2", np.float32, 2), ("maxFraction", np.float32), ("maskBits", np.uint32), ("body", np.int32),
+                             ("flags", np.int32), ("pad", np.int32, 4)])
+ray_state_dtype = np.dtype([("ray", np.int32), ("body", np.int32), ("active", np.int32), ("shape", np.int32), ("hitBody", np.int32),
+                            ("shapeBefore", np.int32), ("fraction", np.float32), ("p1", np.float32, 2), ("p2", np.float32, 2),
+                            ("point", np.float32, 2), ("normal", np.float32, 2), ("pad", np.int32)])
+ray_event_dtype = np.dtype([("ray", np.int32), ("shapeBefore", np.int32), ("shapeNow", np.int32), ("bodyNow", np.int32)])
+RAY_SENSOR_SIZE, RAY_STATE_SIZE, RAY_EVENT_SIZE = ray_sensor_dtype.itemsize, ray_state_dtype.itemsize, ray_event_dtype.itemsize
+assert RAY_SENSOR_SIZE == 48 and RAY_STATE_SIZE == 64 and RAY_EVENT_SIZE == 16
+
 # contact queries on the resident world (include/solver2d_amd.h: s2amd_world_collide_shape, s2amd_world_deepest_contact)
 # s2amdContactQuery, s2amdContactHit
 contact_query_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("normals", np.float32, (8, 2)), ("type", np.int32), ("count", np.int32),
