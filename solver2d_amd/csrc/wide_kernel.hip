@@ -36,6 +36,29 @@
 #ifndef S2_WIDE_HOIST_PREP
 #define S2_WIDE_HOIST_PREP 1
 #endif
+// How the decodes of a resident record (indices, LDS addresses, the negated normal and masses) are kept inside the step loop, where LLVM
+// would otherwise hoist them and pay in scratch.  0: an empty asm statement on the record's registers at the top of every op (opaqueWide):
+// no instruction; 1: XOR with an opaque zero at every use, seven issue slots per chain, five per prep and warm start -- the form to
+// measure against: `make variant NAME=salt EXTRA=-DS2_WIDE_SALT=1`
+#ifndef S2_WIDE_SALT
+#define S2_WIDE_SALT 0
+#endif
+// 1: prepWide hands the chain each point's mass and impulse scale (it holds the condition as a flag: two selects); 0: it hands on a bit per
+// point and chainWide unpacks it and looks the scales up itself -- eleven more issue slots and an LDS read in every chain.
+// `make variant NAME=softbit EXTRA=-DS2_WIDE_SCALES_IN_PREP=0`
+#ifndef S2_WIDE_SCALES_IN_PREP
+#define S2_WIDE_SCALES_IN_PREP 1
+#endif
+// 1: chainWide computes the last friction application in front of its two write-bit branches; 0: the compiler sinks it into them and
+// builds the {invMass, invMass} operands with moves there.  `make variant NAME=tailsunk EXTRA=-DS2_WIDE_TAIL_FIRST=0`
+#ifndef S2_WIDE_TAIL_FIRST
+#define S2_WIDE_TAIL_FIRST 1
+#endif
+// 1: chainWide reads a body's velocity record {v.x, v.y, w, 0} whole (ds_read_b128), so that {w, .} is an aligned register pair the packed
+// multiply broadcasts from; 0: as three dwords (ds_read_b96), w copied into a pair of its own first.  `make variant NAME=vel96 EXTRA=-DS2_WIDE_VEL128=0`
+#ifndef S2_WIDE_VEL128
+#define S2_WIDE_VEL128 1
+#endif
 #define S2_WIDE_THREADS 512
 #define S2_WIDE_INTERIOR 256  // a colour batch of a strip has at most 256 constraints: interior round i runs on half i & 1 of the workgroup
 #define S2_WIDE_ROUNDS_PER_HALF (S2_STRIP_ROUNDS / 2) // ... so a lane holds three interior records
@@ -93,6 +116,11 @@ template <int KIND> S2_DEV WideRegs loadWide(const ContactView& c, int k, int ia
 }
 
 S2_DEV V2 asV2(f2 v) { return v2(v.x, v.y); }
+// The record as far as the compiler knows rewritten in place: what it decodes from these registers stays behind this statement.
+S2_DEV void opaqueWide(WideRegs& p)
+{
+	asm volatile("" : "+v"(p.idx), "+v"(p.n), "+v"(p.p1[0]), "+v"(p.p1[1]), "+v"(p.p2[0]), "+v"(p.p2[1]));
+}
 // s2WarmStartContacts (solve_common.c:276-330): strip_kernel.hip warmSoftRegs
 // The warm start and the prep on 2-vectors both measured SLOWER (178 / 171 vs 131 us per launch: their even-aligned
 // register pairs push resident constraint registers into scratch on the hand-off path -- 84 spilled VGPRs instead of ~30);
@@ -175,17 +203,21 @@ struct WidePrep
 	// per-component sign and its 2-vector algebra packs without moves
 	f2 pA[2], pB[2];
 	float bias[2];
-	uint32_t soft; // bit j: point j takes the soft mass / impulse scales
+	// what the chain scales the normal mass and the old impulse with -- one of the two forms, the other is never written or read:
+	float massScale[2], impulseScale[2]; // SC: the soft scales of the point, or 1 and 0 (selected by the prep: it holds the condition as a flag)
+	uint32_t soft;						 // !SC: bit j: point j takes the soft scales (the chain unpacks the bit and looks them up)
 };
+constexpr bool wideScalesInPrep = S2_WIDE_SCALES_IN_PREP != 0;
 
-template <int KIND, int POINTS, bool LL = false>
+template <int KIND, int POINTS, bool LL = false, bool SC = wideScalesInPrep>
 S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lcoef, float inv_h, int useBias, uint32_t salt, const float4* arms = nullptr, const float4* locals = nullptr)
 {
 	const uint32_t idx = p.idx ^ salt;
 	const int ia = (int)(idx & 0x1fffu), ib = (int)((idx >> 13) & 0x1fffu);
 	const int pointCount = (int)((idx >> 26) & 3u);
 	const float4 dqA = ldq[ia], dqB = ldq[ib];
-	const float biasCoefficient = lcoef[(idx >> 30) & 1u].x;
+	const float4 sf = lcoef[(idx >> 30) & 1u]; // (!SC: .x only)
+	const float biasCoefficient = sf.x;
 	const V2 normal = v2(fromBits(asBits(p.n.x) ^ salt), p.n.y);
 	const V2 dcA = v2(dqA.x, dqA.y), dcB = v2(dqB.x, dqB.y);
 	Rot qA, qB;
@@ -197,6 +229,7 @@ S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lco
 	{
 		pre.pA[j] = pre.pB[j] = f2{0.0f, 0.0f};
 		pre.bias[j] = 0.0f;
+		pre.massScale[j] = 1.0f, pre.impulseScale[j] = 0.0f;
 		if (POINTS == 2 || j < pointCount)
 		{
 			V2 lAj, lBj;
@@ -228,7 +261,14 @@ S2_DEV WidePrep prepWide(const WideRegs& p, const float4* ldq, const float4* lco
 			const bool soft = !speculative && useBias != 0;
 			const float softBias = S2_MAXF(biasCoefficient * s, KIND == SOFT_TGS ? -S2_MAX_BAUMGARTE_VELOCITY : -0.5f * S2_MAX_BAUMGARTE_VELOCITY);
 			pre.bias[j] = speculative ? s * inv_h : (soft ? softBias : 0.0f);
-			pre.soft |= soft ? 1u << j : 0u;
+			if constexpr (SC)
+			{
+				pre.massScale[j] = soft ? sf.y : 1.0f, pre.impulseScale[j] = soft ? sf.z : 0.0f;
+			}
+			else
+			{
+				pre.soft |= soft ? 1u << j : 0u;
+			}
 		}
 	}
 	return pre;
@@ -245,14 +285,19 @@ S2_DEV float crossP(f2 perpR, f2 P) // cross(r, P) = r.x P.y - r.y P.x = perp(r)
 	return m.y + m.x;
 }
 
-template <int POINTS> S2_DEV void chainWide(WideRegs& p, const WidePrep& pre, float4* lvel, const float2* lmass, const float4* lcoef, uint32_t salt)
+// (LEAN: with the two forms above where they are switched on -- all but the variants that gain a frame from them: wideStepKernel, TIGHT)
+template <int POINTS, bool SC = wideScalesInPrep, bool LEAN = true> S2_DEV void chainWide(WideRegs& p, const WidePrep& pre, float4* lvel, const float2* lmass, const float4* lcoef, uint32_t salt)
 {
 	const uint32_t idx = p.idx ^ salt;
 	const int ia = (int)(idx & 0x1fffu), ib = (int)((idx >> 13) & 0x1fffu);
 	const int pointCount = (int)((idx >> 26) & 3u);
 	const float4 velA = lvel[ia], velB = lvel[ib];
+	if constexpr (LEAN && S2_WIDE_VEL128 != 0)
+	{
+		asm volatile("" ::"v"(velA.w), "v"(velB.w)); // (no instruction: the fourth dword counts as read)
+	}
 	const float2 massA = lmass[ia], massB = lmass[ib];
-	const float4 sf = lcoef[(idx >> 30) & 1u];
+	const float4 sf = SC ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : lcoef[(idx >> 30) & 1u];
 	const f2 n = f2{fromBits(asBits(p.n.x) ^ salt), p.n.y};
 	const f2 t = f2{n.y, -n.x}; // rightPerp
 	const f2 mA2 = f2{massA.x, massA.x}, mB2 = f2{massB.x, massB.x};
@@ -268,8 +313,8 @@ template <int POINTS> S2_DEV void chainWide(WideRegs& p, const WidePrep& pre, fl
 		{
 			const f2 pA = pre.pA[j], pB = pre.pB[j];
 			const bool soft = (pre.soft >> j) & 1u;
-			const float massScale = soft ? sf.y : 1.0f;
-			const float impulseScale = soft ? sf.z : 0.0f;
+			const float massScale = SC ? pre.massScale[j] : (soft ? sf.y : 1.0f);
+			const float impulseScale = SC ? pre.impulseScale[j] : (soft ? sf.z : 0.0f);
 
 			// add(v, crossSV(w, r)) = v + w perp(r); sub(vrB, vrA); dot with the normal
 			const f2 vrB = vB + f2{wB, wB} * pB;
@@ -313,6 +358,12 @@ template <int POINTS> S2_DEV void chainWide(WideRegs& p, const WidePrep& pre, fl
 			wB += iB * crossP(pB, P);
 			p.imp[j] = f2{nImp[j], newImpulse};
 		}
+	}
+	if constexpr (LEAN && S2_WIDE_TAIL_FIRST != 0)
+	{
+		// the last friction application in front of the write-bit branches, not sunk into them: there its {m, m} operands are built with
+		// moves, here they are operand selects of the packed multiply like everywhere else in the chain (no instruction)
+		asm volatile("" : "+v"(vA), "+v"(wA), "+v"(vB), "+v"(wB));
 	}
 
 	if ((idx & (1u << 28)) != 0)
@@ -726,6 +777,11 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 	// (RK: the records a lane keeps -- s2Solve_PGS_Soft's with their anchors in LDS; RKP: the records of parked rounds, whole in LDS)
 	constexpr int RK = KIND == SOFT_PGS ? S2_WIDE_PGS_ARMS : KIND;
 	constexpr int RKP = KIND;
+	// (the <4, 2> and <3, 2, 2, 2> layouts beside the overflow workgroup keep the instruction streams they had -- the XORed zero of S2_WIDE_SALT,
+	// the chain's own look-up of the soft scales, the sunk tail, three-dword velocity reads: opaque records or the nine more live registers of
+	// three preps cost <4, 2> a 36-byte frame there, the whole velocity records cost s2Solve_PGS_Soft's <3, 2, 2, 2> a spilled register)
+	constexpr bool TIGHT = OVERFLOW && (RPH == 4 || IL > 0);
+	constexpr bool SC = wideScalesInPrep && !TIGHT;
 	// resident records whose local anchors wait in LDS instead of registers (warmWide / prepWide: LL): the last LA of the RPH interior
 	// + SR seam records a lane holds -- s2Solve_TGS_Soft's variants beyond the <3, 2> layout
 	constexpr int NRES = RPH + SR;
@@ -1249,10 +1305,28 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 	for (int oi = 0; oi < opCount && !bad; ++oi)
 	{
 		const Op op = lops[oi];
-		// an opaque zero produced inside the step loop: without it the compiler hoists the decoding of every round's indices
-		// (and the LDS addresses made from them) out of that loop and pays for it in scratch spills
-		uint32_t salt;
-		asm volatile("s_mov_b32 %0, 0" : "=s"(salt));
+		// without this the compiler hoists the decoding of every round's indices (and the LDS addresses made from them) out of the
+		// step loop and pays for it in scratch spills: the records made opaque here, at no instruction (S2_WIDE_SALT: or an opaque zero
+		// XORed in at every use)
+		constexpr bool SALT = S2_WIDE_SALT != 0 || TIGHT;
+		uint32_t salt = 0u; // (a constant where SALT is off: it folds away at every use)
+		if constexpr (SALT)
+		{
+			asm volatile("s_mov_b32 %0, 0" : "=s"(salt));
+		}
+		else
+		{
+#pragma unroll
+			for (int s = 0; s < RPH; ++s)
+			{
+				opaqueWide(rA[s]);
+			}
+#pragma unroll
+			for (int i = 0; i < SR; ++i)
+			{
+				opaqueWide(rB[i]);
+			}
+		}
 		if (op.code == OP_INTEGRATE_VEL)
 		{
 			if (BODYWARM && oi + 1 < opCount && lops[oi + 1].code == OP_WARM)
@@ -1422,11 +1496,11 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 					const Op next = lops[oi + 1];
 					if (0 >= LL0)
 					{
-						pre = prepWide<RK, POINTS, true>(rA[0], ldq, lcoef, next.inv_h, next.useBias, salt, nullptr, localsOf(0));
+						pre = prepWide<RK, POINTS, true, SC>(rA[0], ldq, lcoef, next.inv_h, next.useBias, salt, nullptr, localsOf(0));
 					}
 					else
 					{
-						pre = prepWide<RK, POINTS>(rA[0], ldq, lcoef, next.inv_h, next.useBias, salt, larms);
+						pre = prepWide<RK, POINTS, false, SC>(rA[0], ldq, lcoef, next.inv_h, next.useBias, salt, larms);
 					}
 				}
 			};
@@ -1526,11 +1600,11 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 			{
 				if (0 >= LL0)
 				{
-					pre = prepWide<RK, POINTS, true>(rA[0], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(0));
+					pre = prepWide<RK, POINTS, true, SC>(rA[0], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(0));
 				}
 				else
 				{
-					pre = prepWide<RK, POINTS>(rA[0], ldq, lcoef, op.inv_h, op.useBias, salt, larms);
+					pre = prepWide<RK, POINTS, false, SC>(rA[0], ldq, lcoef, op.inv_h, op.useBias, salt, larms);
 				}
 			}
 			// (the parked rounds ROUNDS .. RA-1 take part in the same schedule: their records come out of LDS for the prep and again for the chain)
@@ -1545,14 +1619,14 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 						{
 							if (kOfSlot(i >> 1) >= 0)
 							{
-								chainWide<POINTS>(rA[i >> 1 < RPH ? i >> 1 : 0], pre, lvel, lmass, lcoef, salt);
+								chainWide<POINTS, SC, !TIGHT>(rA[i >> 1 < RPH ? i >> 1 : 0], pre, lvel, lmass, lcoef, salt);
 							}
 						}
 						else if (kOfParked(i - ROUNDS < IL ? i - ROUNDS : 0) >= 0)
 						{
 							float4* slot = lparkedI + (i - ROUNDS) * S2_WIDE_PARKED_RECORDS * iw;
 							WideRegs p = unparkWide(slot, iw);
-							chainWide<POINTS>(p, pre, lvel, lmass, lcoef, salt);
+							chainWide<POINTS, SC, !TIGHT>(p, pre, lvel, lmass, lcoef, salt);
 							slot[5 * iw] = make_float4(p.imp[0].x, p.imp[0].y, p.imp[1].x, p.imp[1].y);
 						}
 					}
@@ -1564,17 +1638,17 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 							{
 								if (((i + 1) >> 1) >= LL0)
 								{
-									pre = prepWide<RK, POINTS, true>(rA[(i + 1) >> 1 < RPH ? (i + 1) >> 1 : 0], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf((i + 1) >> 1));
+									pre = prepWide<RK, POINTS, true, SC>(rA[(i + 1) >> 1 < RPH ? (i + 1) >> 1 : 0], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf((i + 1) >> 1));
 								}
 								else
 								{
-									pre = prepWide<RK, POINTS>(rA[(i + 1) >> 1 < RPH ? (i + 1) >> 1 : 0], ldq, lcoef, op.inv_h, op.useBias, salt, larms + 2 * ((i + 1) >> 1) * S2_WIDE_THREADS);
+									pre = prepWide<RK, POINTS, false, SC>(rA[(i + 1) >> 1 < RPH ? (i + 1) >> 1 : 0], ldq, lcoef, op.inv_h, op.useBias, salt, larms + 2 * ((i + 1) >> 1) * S2_WIDE_THREADS);
 								}
 							}
 						}
 						else if (kOfParked(i + 1 - ROUNDS < IL ? i + 1 - ROUNDS : 0) >= 0)
 						{
-							pre = prepWide<RKP, POINTS>(unparkWide(lparkedI + (i + 1 - ROUNDS) * S2_WIDE_PARKED_RECORDS * iw, iw), ldq, lcoef, op.inv_h, op.useBias, salt);
+							pre = prepWide<RKP, POINTS, false, SC>(unparkWide(lparkedI + (i + 1 - ROUNDS) * S2_WIDE_PARKED_RECORDS * iw, iw), ldq, lcoef, op.inv_h, op.useBias, salt);
 						}
 					}
 					__syncthreads();
@@ -1612,11 +1686,11 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 				{
 					if (RPH + i >= LL0)
 					{
-						preB[i] = prepWide<RK, POINTS, true>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(RPH + i));
+						preB[i] = prepWide<RK, POINTS, true, SC>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(RPH + i));
 					}
 					else
 					{
-						preB[i] = prepWide<RK, POINTS>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, larms + 2 * (RPH + i) * S2_WIDE_THREADS);
+						preB[i] = prepWide<RK, POINTS, false, SC>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, larms + 2 * (RPH + i) * S2_WIDE_THREADS);
 					}
 				}
 			}
@@ -1651,18 +1725,18 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 						{
 							if (i >= 2)
 							{
-								const WidePrep late = (RPH + i >= LL0) ? prepWide<RK, POINTS, true>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(RPH + i))
-																	   : prepWide<RK, POINTS>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, larms + 2 * (RPH + i) * S2_WIDE_THREADS);
-								chainWide<POINTS>(rB[i], late, lvel, lmass, lcoef, salt);
+								const WidePrep late = (RPH + i >= LL0) ? prepWide<RK, POINTS, true, SC>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, nullptr, localsOf(RPH + i))
+																	   : prepWide<RK, POINTS, false, SC>(rB[i], ldq, lcoef, op.inv_h, op.useBias, salt, larms + 2 * (RPH + i) * S2_WIDE_THREADS);
+								chainWide<POINTS, SC, !TIGHT>(rB[i], late, lvel, lmass, lcoef, salt);
 							}
 							else
 							{
-								chainWide<POINTS>(rB[i], preB[i < 2 ? i : 0], lvel, lmass, lcoef, salt);
+								chainWide<POINTS, SC, !TIGHT>(rB[i], preB[i < 2 ? i : 0], lvel, lmass, lcoef, salt);
 							}
 						}
 						else
 						{
-							chainWide<POINTS>(rB[i], preB[i], lvel, lmass, lcoef, salt);
+							chainWide<POINTS, SC, !TIGHT>(rB[i], preB[i], lvel, lmass, lcoef, salt);
 						}
 					}
 					__syncthreads();
@@ -1681,8 +1755,8 @@ template <int POINTS, int RPH, int SR, int SL = 0, int IL = 0, int MODE = 0, int
 					{
 						float4* slot = lparked + (i - SR) * S2_WIDE_PARKED_RECORDS * sw;
 						WideRegs p = unparkWide(slot, sw);
-						const WidePrep late = prepWide<RKP, POINTS>(p, ldq, lcoef, op.inv_h, op.useBias, salt);
-						chainWide<POINTS>(p, late, lvel, lmass, lcoef, salt);
+						const WidePrep late = prepWide<RKP, POINTS, false, SC>(p, ldq, lcoef, op.inv_h, op.useBias, salt);
+						chainWide<POINTS, SC, !TIGHT>(p, late, lvel, lmass, lcoef, salt);
 						slot[5 * sw] = make_float4(p.imp[0].x, p.imp[0].y, p.imp[1].x, p.imp[1].y);
 					}
 					__syncthreads();
@@ -2232,8 +2306,17 @@ __global__ __launch_bounds__(S2_WIDE_THREADS) void wideIslandKernel(ContactView 
 	for (int oi = 0; oi < opCount; ++oi)
 	{
 		const Op op = lops[oi];
+#if S2_WIDE_SALT
 		uint32_t salt;
 		asm volatile("s_mov_b32 %0, 0" : "=s"(salt));
+#else
+		constexpr uint32_t salt = 0u; // (wideStepKernel: the records opaque at the top of every op instead)
+#pragma unroll
+		for (int i = 0; i < ROUNDS; ++i)
+		{
+			opaqueWide(rA[i]);
+		}
+#endif
 		if (op.code == OP_INTEGRATE_VEL)
 		{
 #pragma unroll
