@@ -1027,6 +1027,96 @@ int s2amd_world_ray_ranges(s2amdSolver* solver, float* out, int32_t capacity, in
 int s2amd_world_export_ray_ranges(s2amdSolver* solver, void* deviceRanges, int32_t capacity); /* device-to-device, as s2amd_export_poses */
 int s2amd_world_ray_events(s2amdSolver* solver, s2amdRayEvent* out, int32_t capacity, int32_t* count);
 
+/* (additive, API 5) Occupancy grids: "what does the world look like around here, as an image?" -- an egocentric occupancy map around a
+ * vehicle, a local cost map under a character, a coarse minimap for a culling or AI pass.  A list of up to S2AMD_MAX_GRID_SENSORS
+ * grids, each fixed in the world or mounted on a body, is rasterised on the resident arrays behind stage 4 of every s2amd_world_step (a
+ * step the library repeats internally reports once), after the other seven reports.  It replaces, per step, a pose read-back
+ * (s2amd_world_download_step), width x height cell centres computed on the host, one s2amd_world_point_probe call and a fold of its CSR
+ * list into an image.  With no flag set a step enqueues nothing for the grids; the step gains no host wait, the getters wait; nothing
+ * resident is written.  LIVE, xf(body) and PASSES are the scene queries' definitions; every answer is an order-free statement:
+ *   Validation    on the host, in s2amd_world_set_grid_sensors, before anything is changed: 0 <= count <= S2AMD_MAX_GRID_SENSORS; per
+ *                 grid 1 <= width, height <= S2AMD_MAX_GRID_SIDE; position, rot and cellSize finite, cellSize > 0; no flag bits beyond
+ *                 the two below; body < bodyCapacity of the resident world (with no world resident, body is not bounded); and over the
+ *                 list sum(width * height) <= S2AMD_MAX_GRID_CELLS.  One bad record refuses the whole list with S2AMD_E_INVALID, and
+ *                 the old list stands.  rot is not checked for normalisation.  The list holds across uploads; a grid whose body is
+ *                 outside the new world's bodyCapacity is inactive there.
+ *   Cell order    firstCell[g] is the exclusive prefix sum of width * height in list order; cell (i, j) of grid g, i along the
+ *                 frame's x and j along its y, is at firstCell[g] + j * width + i.  Every per-cell array has exactly
+ *                 sum(width * height) entries, those of inactive grids included.
+ *   Frame         body < 0: G = {position, rot}.  Otherwise G = s2MulTransforms(xf(body), {position, rot})
+ *                 (include/solver2d/math.h:368-374), in the operation order the sensor report's paragraph spells out.
+ *   Cell point    l.x = (((float)i + 0.5f) - 0.5f * (float)width) * cellSize, l.y the same with j and height (everything in front of
+ *                 the one multiply is exact for these integers: the grid is centred on its frame); P = s2TransformPoint(G, l)
+ *                 (math.h:350-356).
+ *   Active        not S2AMD_GRID_SENSOR_DISABLED; body < 0 or (body < bodyCapacity and bodies[body].type != S2AMD_BODY_FREE); and the P
+ *                 of the four corner cells are finite -- a body with a non-finite pose switches its grids off.
+ *   Box           the componentwise min and max of the four corner cells' P.  It contains every cell's P: each coordinate of P is a
+ *                 composition of correctly rounded operations, each weakly monotone in i and in j, so its extremes over the grid lie at
+ *                 corners.  This is why the grid-level cull below decides no result.
+ *   Candidates    of a grid: the LIVE shapes with (categoryBits & maskBits) != 0 and s2AABB_Overlaps(fatAABB, box); for a mounted grid
+ *                 (body >= 0) not those with shape.body == grid.body, so that a grid never sees its own body; with
+ *                 S2AMD_GRID_SENSOR_SKIP_STATIC not those with bodies[shape.body].type == S2AMD_BODY_STATIC.
+ *   Hit           of a cell: a candidate with s2AABB_Overlaps(fatAABB, {P, P}) that passes s2PointInCircle / Capsule / Polygon
+ *                 (s2InvTransformPoint(xf(shape.body), P), geometry) -- s2amd_world_point_probe's statement for {P, maskBits} minus the
+ *                 two exclusions.  Segments never hit.
+ *   CATEGORIES    s2amd_world_grid_categories: per cell the OR of categoryBits over the cell's hits.
+ *   SHAPES        s2amd_world_grid_shapes: per cell the lowest hit slot, or -1.
+ *   OCCUPANCY     s2amd_world_grid_occupancy: per cell 1.0f if there is a hit, else +0.0f -- the observation image.
+ *                 s2amd_world_export_grid_occupancy copies the same bytes into a caller's device buffer (s2amd_device_alloc or any
+ *                 allocation of the solver's device) behind the step on the solver's stream, device to device, and returns when the
+ *                 copy is done, as s2amd_world_export_ray_ranges; capacity counts floats.  Cells of an inactive grid read 0, -1, +0.
+ *   STATES        s2amd_world_grid_states: one record per grid in list order.  occupied is the number of cells with a hit,
+ *                 lowestShape the least SHAPES value >= 0 over the grid or -1, candidates the number of the grid's candidates; the
+ *                 three are filled whatever other flags are set.  An inactive grid has active = 0, frame and box +0, occupied =
+ *                 candidates = 0, lowestShape = -1; it keeps firstCell and cells.
+ *   Lifetime      the report keeps nothing from step to step: there is no "before" and there are no events.  s2amd_world_upload,
+ *                 turning the report on, and a s2amd_world_set_grid_sensors that succeeds on a resident world each void the last
+ *                 step's report: the getters answer S2AMD_E_STATE until the next step.
+ *   Errors        those of the other reports: S2AMD_E_STATE without a resident world, when the getter's flag was not set before the
+ *                 last step, or when no step has run since; S2AMD_E_CAPACITY with *count filled and nothing written; unknown flag bits
+ *                 give S2AMD_E_INVALID.
+ *   Memory        192 bytes per grid (the list 64, the posed grid 64, the state 64) plus 8 bytes per grid and 64 shape slots (the
+ *                 candidate mask, shape slots rounded up to 256), 12 bytes per cell (the three arrays) and 16 bytes per tile of 64
+ *                 cells, each piece rounded up to 256 bytes: 14.9 MiB for 1,048,576 cells in 1,024 grids over 20,101 shape slots.
+ *                 s2amd_world_set_grid_sensors on a resident world with the report on waits for the stream once (the list is copied
+ *                 to the device before the call returns).
+ * The reference has no occupancy grids: the composition is ours; every cell test is the reference's s2PointIn<type> bit for bit.  All
+ * arithmetic is fp32 in the reference's operation order without contraction, in libs2amd.so and in libs2amd_fast.so alike.  Not
+ * offered: events, distances per cell, grids or cell arrays in device memory other than the occupancy export, sharded worlds, a
+ * one-shot call (s2amd_world_point_probe is the one-shot). */
+#define S2AMD_MAX_GRID_SENSORS 1024
+#define S2AMD_MAX_GRID_SIDE 256		 /* width and height, each 1..256 */
+#define S2AMD_MAX_GRID_CELLS 1048576 /* over the whole list */
+#define S2AMD_GRID_SENSOR_DISABLED 1	/* every cell reads empty */
+#define S2AMD_GRID_SENSOR_SKIP_STATIC 2 /* shapes on static bodies are not candidates */
+typedef struct s2amdGridSensor /* 64 bytes */
+{
+	float position[2], rot[2]; /* the grid's frame ({s, c}), in the world (body < 0) or relative to the body; the grid is centred on it */
+	float cellSize;			   /* > 0, finite */
+	int32_t width, height;	   /* cells along the frame's x and y */
+	uint32_t maskBits;
+	int32_t body;  /* < 0: fixed in the world */
+	int32_t flags; /* S2AMD_GRID_SENSOR_* */
+	int32_t pad[6];
+} s2amdGridSensor;
+int s2amd_world_set_grid_sensors(s2amdSolver* solver, const s2amdGridSensor* grids, int32_t count); /* replaces the whole list; count 0 clears */
+#define S2AMD_GRID_REPORT_CATEGORIES 1
+#define S2AMD_GRID_REPORT_SHAPES 2
+#define S2AMD_GRID_REPORT_OCCUPANCY 4
+#define S2AMD_GRID_REPORT_STATES 8
+int s2amd_world_set_grid_report(s2amdSolver* solver, int32_t flags);
+typedef struct s2amdGridState /* 64 bytes */
+{
+	int32_t grid, body, active, firstCell, cells, occupied, lowestShape, candidates;
+	float position[2], rot[2]; /* the world frame used */
+	float box[4];			   /* the candidate box used */
+} s2amdGridState;
+int s2amd_world_grid_categories(s2amdSolver* solver, uint32_t* out, int32_t capacity, int32_t* count); /* one word per cell */
+int s2amd_world_grid_shapes(s2amdSolver* solver, int32_t* out, int32_t capacity, int32_t* count);
+int s2amd_world_grid_occupancy(s2amdSolver* solver, float* out, int32_t capacity, int32_t* count);
+int s2amd_world_export_grid_occupancy(s2amdSolver* solver, void* deviceCells, int32_t capacity); /* device-to-device, as s2amd_world_export_ray_ranges */
+int s2amd_world_grid_states(s2amdSolver* solver, s2amdGridState* out, int32_t capacity, int32_t* count);
+
 /* (additive, API 5) Contact queries: "if this shape stood here, what would it touch, where, and how deep?" asked of the resident world
  * -- a character controller, a ghost or trigger shape, spawn placement with push-out, a "will this fit" test.  The reference answers it
  * with its nine manifold functions s2Collide* (include/solver2d/manifold.h:56-85), dispatched by s_registers (src/contact.c:139-151);

@@ -592,6 +592,12 @@ struct SolverRest
 	std::vector<s2amdRaySensor> hRaySensors; // the list as the caller set it: held across uploads, copied into the block by every prepare
 	int rayNowSet = 0;						 // which of the two ping-pong hit-shape arrays holds "now" of the last evaluation ("before" of the next)
 	int32_t hRayReportHead[4] = {0, 0, 0, 0}; // {events, 0, 0, 0}
+	// grid report (grid_report.hip; s2amd_world_set_grid_sensors, s2amd_world_set_grid_report: S2AMD_GRID_REPORT_*): the eighth of a step
+	ReportState gridReport;
+	std::vector<s2amdGridSensor> hGridSensors; // the list as the caller set it (pad[0]: the grid's firstCell): held across uploads, copied into the block by every prepare
+	std::vector<int32_t> hGridTiles;		   // ... and its table of 64-cell tiles, four words each {grid, i0, j0, first}, an 8 x 8 block of cells: no tile lies across two grids
+	size_t gridCells = 0;					   // the sum of width * height over the list
+	int32_t hGridReportHead[4] = {0, 0, 0, 0}; // {cells, grids, 0, 0}: known on the host when the step is enqueued
 	// force fields (force_field.hip; s2amd_world_apply_fields, s2amd_world_set_fields, s2amd_world_field_states): no report -- a write in
 	// front of stage 3 -- but kept and released beside them
 	std::vector<s2amdField> hFields; // the persistent list as the caller set it: held across uploads
@@ -863,6 +869,8 @@ int sensorReportPrepare(s2amdSolver* s);
 int sensorReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int rayReportPrepare(s2amdSolver* s);
 int rayReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+int gridReportPrepare(s2amdSolver* s);
+int gridReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 // force_field.hip: the persistent list in front of stage 3 (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
 int fieldsStepEnqueue(s2amdSolver* s);
 void fieldsForgetWorld(s2amdSolver* s);

@@ -39,6 +39,8 @@ EXPORTS = [
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
     "s2amd_world_ray_events",
+    "s2amd_world_set_grid_sensors", "s2amd_world_set_grid_report", "s2amd_world_grid_categories", "s2amd_world_grid_shapes", "s2amd_world_grid_occupancy",
+    "s2amd_world_export_grid_occupancy", "s2amd_world_grid_states",
     "s2amd_get_strip_owners", "s2amd_get_resident_kernel", "s2amd_variant_family_count", "s2amd_get_variant_family", "s2amd_get_variant_entry",
     "s2amd_sharded_create", "s2amd_sharded_destroy", "s2amd_sharded_shard_count", "s2amd_sharded_solver", "s2amd_sharded_upload", "s2amd_sharded_step",
     "s2amd_sharded_download", "s2amd_sharded_read_bodies", "s2amd_sharded_reshard", "s2amd_sharded_get_partition",
@@ -154,6 +156,13 @@ def load(fast=False):
     L.s2amd_world_ray_ranges.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_export_ray_ranges.argtypes = [vp, vp, i32]
     L.s2amd_world_ray_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_set_grid_sensors.argtypes = [vp, vp, i32]
+    L.s2amd_world_set_grid_report.argtypes = [vp, i32]
+    L.s2amd_world_grid_categories.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_grid_shapes.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_grid_occupancy.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_export_grid_occupancy.argtypes = [vp, vp, i32]
+    L.s2amd_world_grid_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_device_alloc.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
     L.s2amd_device_free.argtypes = [vp, vp]
     L.s2amd_device_read.argtypes = [vp, vp, vp, ctypes.c_uint64]
@@ -808,6 +817,39 @@ class Solver:
     def world_ray_events(self, expected=64):
         """wire.ray_event_dtype records of the rays whose hit shape changed in the last world_step, ascending by ray."""
         return self._world_list(self._L.s2amd_world_ray_events, wire.ray_event_dtype, expected)
+
+    # ---- grid report of the resident world (s2amd_world_set_grid_sensors, s2amd_world_set_grid_report): per-cell images, states ----
+    def world_set_grid_sensors(self, grids):
+        """Replaces the whole list of occupancy grids (wire.grid_sensor_dtype; an empty one clears it).  The list holds across uploads."""
+        grids = np.ascontiguousarray(grids)
+        assert grids.dtype == wire.grid_sensor_dtype
+        self._ck(self._L.s2amd_world_set_grid_sensors(self._h, wire.as_ptr(grids) if len(grids) else None, len(grids)))
+        self._world_grids = len(grids)
+        self._world_grid_cells = int((grids["width"].astype(np.int64) * grids["height"]).sum())
+
+    def world_set_grid_report(self, flags):
+        """wire.GRID_REPORT_* bits: what every world_step from the next one on rasterises on the device (0: nothing, the default)."""
+        self._ck(self._L.s2amd_world_set_grid_report(self._h, int(flags)))
+
+    def world_grid_categories(self, expected=None):
+        """uint32[cells]: the OR of categoryBits over each cell's hits, grids in list order, cell (i, j) at firstCell + j * width + i."""
+        return self._world_list(self._L.s2amd_world_grid_categories, np.uint32, expected or getattr(self, "_world_grid_cells", 0))
+
+    def world_grid_shapes(self, expected=None):
+        """int32[cells]: the lowest hit slot of each cell, or -1."""
+        return self._world_list(self._L.s2amd_world_grid_shapes, np.int32, expected or getattr(self, "_world_grid_cells", 0))
+
+    def world_grid_occupancy(self, expected=None):
+        """float32[cells]: 1.0 where a cell has a hit, else 0.0."""
+        return self._world_list(self._L.s2amd_world_grid_occupancy, np.float32, expected or getattr(self, "_world_grid_cells", 0))
+
+    def world_export_grid_occupancy(self, device_ptr, capacity):
+        """world_grid_occupancy's bytes into a device buffer (device_alloc, or a torch tensor's data_ptr()) of `capacity` floats."""
+        self._ck(self._L.s2amd_world_export_grid_occupancy(self._h, ctypes.c_void_p(int(device_ptr)), int(capacity)))
+
+    def world_grid_states(self, expected=None):
+        """wire.grid_state_dtype records, one per grid in list order, after the last world_step."""
+        return self._world_list(self._L.s2amd_world_grid_states, wire.grid_state_dtype, expected or getattr(self, "_world_grids", 0))
 
     def find_islands(self, bodies, contacts, joints):
         """(island_of_body int32[nb], island_count): connected components over the movable bodies, on the device."""

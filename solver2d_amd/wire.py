@@ -270,6 +270,20 @@ ray_event_dtype = np.dtype([("ray", np.int32), ("shapeBefore", np.int32), ("shap
 RAY_SENSOR_SIZE, RAY_STATE_SIZE, RAY_EVENT_SIZE = ray_sensor_dtype.itemsize, ray_state_dtype.itemsize, ray_event_dtype.itemsize
 assert RAY_SENSOR_SIZE == 48 and RAY_STATE_SIZE == 64 and RAY_EVENT_SIZE == 16
 
+# grid report of the resident world (include/solver2d_amd.h: s2amd_world_set_grid_sensors, s2amd_world_set_grid_report)
+MAX_GRID_SENSORS, MAX_GRID_SIDE, MAX_GRID_CELLS = 1024, 256, 1048576
+GRID_SENSOR_DISABLED, GRID_SENSOR_SKIP_STATIC = 1, 2
+GRID_REPORT_CATEGORIES, GRID_REPORT_SHAPES, GRID_REPORT_OCCUPANCY, GRID_REPORT_STATES = 1, 2, 4, 8
+GRID_REPORT_ALL = GRID_REPORT_CATEGORIES | GRID_REPORT_SHAPES | GRID_REPORT_OCCUPANCY | GRID_REPORT_STATES
+# s2amdGridSensor, s2amdGridState
+grid_sensor_dtype = np.dtype([("position", np.float32, 2), ("rot", np.float32, 2), ("cellSize", np.float32), ("width", np.int32), ("height", np.int32),
+                              ("maskBits", np.uint32), ("body", np.int32), ("flags", np.int32), ("pad", np.int32, 6)])
+grid_state_dtype = np.dtype([("grid", np.int32), ("body", np.int32), ("active", np.int32), ("firstCell", np.int32), ("cells", np.int32),
+                             ("occupied", np.int32), ("lowestShape", np.int32), ("candidates", np.int32), ("position", np.float32, 2),
+                             ("rot", np.float32, 2), ("box", np.float32, 4)])
+GRID_SENSOR_SIZE, GRID_STATE_SIZE = grid_sensor_dtype.itemsize, grid_state_dtype.itemsize
+assert GRID_SENSOR_SIZE == 64 and GRID_STATE_SIZE == 64
+
 # contact queries on the resident world (include/solver2d_amd.h: s2amd_world_collide_shape, s2amd_world_deepest_contact)
 # s2amdContactQuery, s2amdContactHit
 contact_query_dtype = np.dtype([("vertices", np.float32, (8, 2)), ("normals", np.float32, (8, 2)), ("type", np.int32), ("count", np.int32),
