@@ -1364,7 +1364,8 @@ int s2amd_world_move_shapes(s2amdSolver* solver, const s2amdMover* movers, int32
  *                 With skipped == NULL the call only enqueues and reads nothing back; with a pointer it reads back one int.  The caller
  *                 may reuse `edits` as soon as the call returns.  Forces are consumed by the next step's stage 4, as the reference's are.
  * Not offered: s2Body_SetTransform (the reference declares it and never defines it; it would also move boxes and trees); mass, type or
- * damping edits; creating or destroying anything; sharded worlds; edit lists in device memory; the drop-in's setters routed through
+ * damping edits; creating or destroying anything; sharded worlds; edit lists in device memory (values that live in device memory reach
+ * these edits through the actuators below: s2amd_world_set_actuators, s2amd_world_import_actions); the drop-in's setters routed through
  * this call. */
 #define S2AMD_EDIT_BODY_SET_LINEAR_VELOCITY 1	/* v[0..1]                      src/body.c:337-342 */
 #define S2AMD_EDIT_BODY_SET_ANGULAR_VELOCITY 2	/* v[0]                         src/body.c:344-350 */
@@ -1436,7 +1437,8 @@ int s2amd_world_edit(s2amdSolver* solver, const s2amdWorldEdit* edits, int32_t c
  *                 use of fields after an upload builds a body -> shapes list on the device (a stable radix sort; no host sort, no wait).
  * The reference has no fields: the composition is ours; every distance is the reference's s2ShapeDistance and every term the
  * reference's setter, bit for bit.  Not offered: torque (the reference has no setter for it); fields that act on kinematic or static
- * bodies; sharded worlds; lists in device memory; the drop-in routed through this call; the device trees as an accelerator (a field
+ * bodies; sharded worlds; lists in device memory (forces whose values live in device memory are the actuators' below:
+ * s2amd_world_set_actuators, s2amd_world_import_actions); the drop-in routed through this call; the device trees as an accelerator (a field
  * looks at every shape of every dynamic body, and a body with hundreds of shapes is walked by one lane: correct, not fast). */
 #define S2AMD_MAX_FIELDS 1024
 #define S2AMD_FIELD_RADIAL 1  /* along s2Normalize(pointB - centre) */
@@ -1472,6 +1474,99 @@ int s2amd_world_apply_fields(s2amdSolver* solver, const s2amdField* fields, int3
 int s2amd_world_set_fields(s2amdSolver* solver, const s2amdField* fields, int32_t count); /* replaces the whole list; count 0 clears */
 int s2amd_world_field_states(s2amdSolver* solver, s2amdFieldState* out, int32_t capacity, int32_t* count);
 
+/* (additive, API 5) Actuators: the write half of a control loop that stays on the device.  A persistent list of actuators maps channels
+ * of an ACTION VECTOR that lives in device memory onto s2amd_world_edit's edits, in front of every s2amd_world_step: a policy network's
+ * output, a PD controller's set points or a scripted platform's velocities arrive device to device (s2amd_world_import_actions), the
+ * observations leave device to device (s2amd_world_export_ray_ranges, s2amd_world_export_grid_occupancy, s2amd_export_poses), and a step
+ * with actuators gains no host wait.  Nothing is downloaded and the structure is kept, as with an edit.
+ *   Action buffer the library owns one float[channels] in device memory, zeroed whenever the list is replaced; values hold until they
+ *                 are overwritten (zero-order hold), across steps and uploads.  s2amd_world_set_actions copies host values into
+ *                 [first, first + count) through pinned memory: the caller may reuse its array on return.  s2amd_world_import_actions
+ *                 copies them from device memory, as s2amd_export_poses in reverse.  Both are enqueued on the stream s2amd_world_step
+ *                 uses and do not wait.  The SOURCE of s2amd_world_import_actions must be complete when the call is made: a caller that
+ *                 fills it on a stream of its own synchronises that stream first (the library's stream does not wait for any other).
+ *   Command       for each component i < width of the kind: a_i = actions[channel + i]; t = gain * a_i (one multiply); t = t + bias (one
+ *                 add); u_i = t < lower ? lower : (t > upper ? upper : t).  fp32 without contraction, in libs2amd.so and in
+ *                 libs2amd_fast.so alike.
+ *   Kinds         1 BODY_FORCE            width 2  APPLY_FORCE_TO_CENTER(target, {u0, u1})
+ *                 2 BODY_THRUST           width 1  APPLY_FORCE_TO_CENTER(target, s2MulSV(u0, s2RotateVector(rot(target), axis)))
+ *                 3 BODY_LINEAR_VELOCITY  width 2  SET_LINEAR_VELOCITY(target, {u0, u1})
+ *                 4 BODY_ANGULAR_VELOCITY width 1  SET_ANGULAR_VELOCITY(target, u0)
+ *                 5 REVOLUTE_MOTOR_SPEED  width 1  REVOLUTE_SET_MOTOR_SPEED(target, u0)
+ *                 6 REVOLUTE_SERVO        width 1  angle = s2RelativeAngle(rot(bodyB), rot(bodyA)) - referenceAngle (the joint report's
+ *                                                  formula and its atan2; a body outside the body array counts as unrotated);
+ *                                                  v = kp * (u0 - angle); speed = v < -maxSpeed ? -maxSpeed : (v > maxSpeed ? maxSpeed : v);
+ *                                                  REVOLUTE_SET_MOTOR_SPEED(target, speed)
+ *                 7 MOUSE_TARGET          width 2  MOUSE_SET_TARGET(target, {u0, u1})
+ *                 `target` is a body slot for kinds 1-4 and a joint slot for kinds 5-7.
+ *   Status        decided in this order.  DISABLED: S2AMD_ACTUATOR_DISABLED is set.  SKIPPED: the target is outside the resident
+ *                 capacities, a free body slot, a free joint slot or a joint of the other type -- only the device knows, as with edits.
+ *                 NONFINITE: some a_i has all exponent bits set (a NaN or an infinity) -- a policy that diverges must not poison the
+ *                 world.  APPLIED: everything else.  Only an APPLIED actuator yields a term.
+ *   Result        the resident `bodies` and `joints` after the pass are what s2amd_world_edit gives for the terms of the APPLIED
+ *                 actuators in list order, each term exactly the edit of that name.  No term changes a pose, so every rot and angle
+ *                 read is that of the world as the pass found it; terms on different targets commute, and only the order of the terms
+ *                 on one target matters, to the bit.  Every other array is untouched byte for byte.
+ *   When          a non-empty list is applied once per s2amd_world_step call, in front of the persistent force fields (a DRAG field
+ *                 sees the velocity an actuator set), in front of stage 3 and outside the loop that repeats a solve.  The list and the
+ *                 buffer hold across uploads; an actuator whose target is outside the new capacities is SKIPPED.  With no list a step
+ *                 enqueues nothing and allocates nothing.
+ *   States        one record per actuator in list order, of the last step's pass: `action` as read (+0 when DISABLED), `command` = u,
+ *                 `output` = the term's v[0..1] (the servo's output[0] is the speed), `angle` = the servo's measured angle; command,
+ *                 output and angle are +0 unless APPLIED, and every component beyond the kind's width is +0.
+ *                 s2amd_world_actuator_counts gives the number of actuators per status in one 16-byte read.  Both getters wait for the
+ *                 stream; the step does not.  S2AMD_E_STATE if no step ran since the list was set or since the last upload;
+ *                 S2AMD_E_CAPACITY with *count filled when the buffer is too small; *count = 0 (and zero counts) with an empty list.
+ *   Validation    on the host, before anything is replaced: 0 <= count <= S2AMD_MAX_ACTUATORS; with count > 0 a non-NULL list and
+ *                 1 <= channels <= S2AMD_MAX_ACTION_CHANNELS; per record kind in 1..7, target >= 0 (and below the resident body or
+ *                 joint capacity when a world is resident), channel >= 0 and channel + width <= channels, no flag bits beyond
+ *                 DISABLED, reserved all 0, gain, bias, axis and kp finite, lower <= upper and neither a NaN (infinities are allowed),
+ *                 maxSpeed >= 0 and not a NaN.  One bad record refuses the whole list with S2AMD_E_INVALID, and the old list and the
+ *                 buffer stand.  The two writers return S2AMD_E_INVALID for a NULL pointer with count > 0, a negative first or count or
+ *                 a range past `channels`, and S2AMD_E_STATE with no list set.  The setter and the writers need no resident world.
+ *   Cost          the list is static, so its grouping by target is made once, in the setter: a step launches one kernel when all
+ *                 targets are distinct and two when some target occurs twice.  No sort, no float atomics, no host wait in the step.
+ * The reference has no actuators: the composition is ours, every term the reference's setter, bit for bit.  Not offered: torque (the
+ * reference has no setter for it); impulses; actuator lists themselves in device memory; sharded worlds; the drop-in routed through
+ * this; PD on anything but a revolute angle. */
+#define S2AMD_MAX_ACTUATORS 16384
+#define S2AMD_MAX_ACTION_CHANNELS 65536
+#define S2AMD_ACTUATOR_BODY_FORCE 1
+#define S2AMD_ACTUATOR_BODY_THRUST 2
+#define S2AMD_ACTUATOR_BODY_LINEAR_VELOCITY 3
+#define S2AMD_ACTUATOR_BODY_ANGULAR_VELOCITY 4
+#define S2AMD_ACTUATOR_REVOLUTE_MOTOR_SPEED 5
+#define S2AMD_ACTUATOR_REVOLUTE_SERVO 6
+#define S2AMD_ACTUATOR_MOUSE_TARGET 7
+#define S2AMD_ACTUATOR_DISABLED 1
+#define S2AMD_ACTUATOR_STATUS_APPLIED 0
+#define S2AMD_ACTUATOR_STATUS_DISABLED 1
+#define S2AMD_ACTUATOR_STATUS_SKIPPED 2
+#define S2AMD_ACTUATOR_STATUS_NONFINITE 3
+typedef struct s2amdActuator /* 64 bytes */
+{
+	int32_t kind;	 /* S2AMD_ACTUATOR_BODY_FORCE .. _MOUSE_TARGET */
+	int32_t target;	 /* body slot (kinds 1-4) or joint slot (kinds 5-7) */
+	int32_t channel; /* the first of the kind's `width` channels */
+	int32_t flags;	 /* S2AMD_ACTUATOR_DISABLED */
+	float gain, bias, lower, upper; /* u = clamp(gain * a + bias, lower, upper) */
+	float axis[2];	 /* BODY_THRUST: the direction in the body's frame; not normalised by the library */
+	float kp, maxSpeed; /* REVOLUTE_SERVO */
+	int32_t reserved[4]; /* 0 */
+} s2amdActuator;
+typedef struct s2amdActuatorState /* 48 bytes */
+{
+	int32_t actuator, target, status, pad;
+	float action[2], command[2], output[2];
+	float angle;
+	int32_t pad2;
+} s2amdActuatorState;
+int s2amd_world_set_actuators(s2amdSolver* solver, const s2amdActuator* list, int32_t count, int32_t channels); /* replaces the list; count 0 clears */
+int s2amd_world_set_actions(s2amdSolver* solver, const float* hostValues, int32_t first, int32_t count);	   /* host -> the library's action buffer */
+int s2amd_world_import_actions(s2amdSolver* solver, const void* deviceValues, int32_t first, int32_t count); /* device -> the same, as s2amd_export_poses in reverse */
+int s2amd_world_actuator_states(s2amdSolver* solver, s2amdActuatorState* out, int32_t capacity, int32_t* count);
+int s2amd_world_actuator_counts(s2amdSolver* solver, int32_t counts[4]); /* actuators per status {APPLIED, DISABLED, SKIPPED, NONFINITE} */
+
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts
  * (pointCount > 0) and revolute joints; every other live non-static body is an island of its own; static and free
@@ -1499,12 +1594,15 @@ int s2amd_export_bodies_async(s2amdSolver* solver, void* deviceRecords, int32_t 
 int s2amd_export_wait(s2amdSolver* solver, int32_t slot);
 
 /* Device buffers for callers that have no device allocator of their own (a host language behind cgo / JNI / ctypes): the
- * destination of s2amd_export_poses and the source of s2amd_device_read.  Owned by the caller, freed with
+ * destination of s2amd_export_poses, the source of s2amd_device_read and the destination of s2amd_device_write.  Owned by the caller, freed with
  * s2amd_device_free (or never: s2amd_destroy does not track them). */
 int s2amd_device_alloc(s2amdSolver* solver, uint64_t bytes, void** devicePtr);
 int s2amd_device_free(s2amdSolver* solver, void* devicePtr);
 /* Copies `bytes` from device memory to host memory behind everything enqueued on the solver's stream; returns when done. */
 int s2amd_device_read(s2amdSolver* solver, void* hostDst, const void* deviceSrc, uint64_t bytes);
+/* (API 5) The mirror: copies `bytes` from host memory to device memory behind everything enqueued on the solver's stream; returns when
+ * done, so the caller may reuse hostSrc.  How a caller without a device allocator fills the source of s2amd_world_import_actions. */
+int s2amd_device_write(s2amdSolver* solver, void* deviceDst, const void* hostSrc, uint64_t bytes);
 
 /* ---- introspection (tests, bench) ---- */
 /* Execution order of the last step: order[k] = contact-array index of the k-th constraint in

@@ -1,7 +1,8 @@
 // The body setters' arithmetic (s2Body_SetLinearVelocity, _SetAngularVelocity, _ApplyForceToCenter, _ApplyLinearImpulse,
-// src/body.c:337-370) on a wire record whose edited fields a lane keeps in registers: what s2amd_world_edit (world_edit.hip) and the
-// force fields (force_field.hip) share, so that a field's term IS the edit of the same name.  Everything is in an unnamed namespace:
-// each file holds its own copy.
+// src/body.c:337-370) and the joint setters' (s2MouseJoint_SetTarget, src/mouse_joint.c:18-29; s2RevoluteJoint_EnableLimit, _EnableMotor,
+// _SetMotorSpeed, src/revolute_joint.c:890-927) on a wire record whose edited fields a lane keeps in registers: what s2amd_world_edit
+// (world_edit.hip), the force fields (force_field.hip) and the actuators (actuators.hip) share, so that a field's or an actuator's term
+// IS the edit of the same name.  Everything is in an unnamed namespace: each file holds its own copy.
 #pragma once
 
 #include "solver_internal.h"
@@ -86,6 +87,98 @@ __device__ inline void applyBodyEdit(const s2amdWorldEdit& e, const BodyFixed& k
 		f.w = f.w + k.invI * (rx * e.v[1] - ry * e.v[0]);
 		f.written |= S2_EDIT_W_LINEAR | S2_EDIT_W_ANGULAR;
 	}
+}
+
+// ---- the joint half: kinds 5-8 ----
+static_assert(sizeof(s2amdJoint) == 92, "the wire record");
+
+#define S2_EDIT_FIRST_JOINT_KIND S2AMD_EDIT_MOUSE_SET_TARGET
+
+// which fields of a joint record an edit (or a walk) has written
+#define S2_EDIT_W_MOTOR 1
+#define S2_EDIT_W_LIMIT 2
+#define S2_EDIT_W_SPEED 4
+#define S2_EDIT_W_TARGET 8
+
+struct JointFields
+{
+	int enableMotor, enableLimit;
+	float motorSpeed, tx, ty;
+	int written;
+};
+
+__device__ inline s2amdWorldEdit loadEdit(const s2amdWorldEdit* edits, size_t i)
+{
+	// (32 bytes, 32-byte aligned: two 16-byte loads)
+	const int4 a = ((const int4*)edits)[2 * i];
+	const float4 b = ((const float4*)edits)[2 * i + 1];
+	s2amdWorldEdit e;
+	e.kind = a.x, e.target = a.y, e.flag = a.z, e.reserved = a.w;
+	e.v[0] = b.x, e.v[1] = b.y, e.v[2] = b.z, e.v[3] = b.w;
+	return e;
+}
+
+__device__ inline void loadJoint(const s2amdJoint* j, JointFields& f)
+{
+	f.enableMotor = j->enableMotor, f.enableLimit = j->enableLimit;
+	f.motorSpeed = j->motorSpeed;
+	f.tx = j->targetA[0], f.ty = j->targetA[1];
+	f.written = 0;
+}
+
+__device__ inline void storeJoint(s2amdJoint* j, const JointFields& f)
+{
+	if ((f.written & S2_EDIT_W_MOTOR) != 0)
+	{
+		j->enableMotor = f.enableMotor;
+	}
+	if ((f.written & S2_EDIT_W_LIMIT) != 0)
+	{
+		j->enableLimit = f.enableLimit;
+	}
+	if ((f.written & S2_EDIT_W_SPEED) != 0)
+	{
+		j->motorSpeed = f.motorSpeed;
+	}
+	if ((f.written & S2_EDIT_W_TARGET) != 0)
+	{
+		j->targetA[0] = f.tx, j->targetA[1] = f.ty;
+	}
+}
+
+// one joint edit (kinds 5-8) on a slot of type `type`; false: the joint is free or of the other type, nothing is written
+__device__ inline bool applyJointEdit(const s2amdWorldEdit& e, int type, JointFields& f)
+{
+	if (e.kind == S2AMD_EDIT_MOUSE_SET_TARGET)
+	{
+		if (type != S2AMD_JOINT_MOUSE)
+		{
+			return false;
+		}
+		f.tx = e.v[0], f.ty = e.v[1]; // mouse_joint.c:28
+		f.written |= S2_EDIT_W_TARGET;
+		return true;
+	}
+	if (type != S2AMD_JOINT_REVOLUTE)
+	{
+		return false;
+	}
+	if (e.kind == S2AMD_EDIT_REVOLUTE_ENABLE_LIMIT)
+	{
+		f.enableLimit = e.flag != 0 ? 1 : 0; // revolute_joint.c:900
+		f.written |= S2_EDIT_W_LIMIT;
+	}
+	else if (e.kind == S2AMD_EDIT_REVOLUTE_ENABLE_MOTOR)
+	{
+		f.enableMotor = e.flag != 0 ? 1 : 0; // revolute_joint.c:913
+		f.written |= S2_EDIT_W_MOTOR;
+	}
+	else
+	{
+		f.motorSpeed = e.v[0]; // revolute_joint.c:926
+		f.written |= S2_EDIT_W_SPEED;
+	}
+	return true;
 }
 
 } // namespace

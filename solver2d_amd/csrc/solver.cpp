@@ -283,6 +283,7 @@ void s2amd_destroy(s2amdSolver* s)
 	}
 	reportsRelease(s);
 	fieldsRelease(s);
+	actuatorsRelease(s);
 	treesFree(s);
 	if (s->hostError)
 	{
@@ -921,6 +922,21 @@ int s2amd_device_read(s2amdSolver* s, void* hostDst, const void* deviceSrc, uint
 	if (bytes > 0)
 	{
 		HIP_TRY(hipMemcpyAsync(hostDst, deviceSrc, (size_t)bytes, hipMemcpyDeviceToHost, s->stream));
+	}
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	return S2AMD_OK;
+}
+
+int s2amd_device_write(s2amdSolver* s, void* deviceDst, const void* hostSrc, uint64_t bytes)
+{
+	if (!s || (bytes > 0 && (!deviceDst || !hostSrc)))
+	{
+		return fail(S2AMD_E_INVALID, "null argument");
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	if (bytes > 0)
+	{
+		HIP_TRY(hipMemcpyAsync(deviceDst, hostSrc, (size_t)bytes, hipMemcpyHostToDevice, s->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(s->stream));
 	return S2AMD_OK;

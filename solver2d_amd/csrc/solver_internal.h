@@ -610,6 +610,17 @@ struct SolverRest
 	char* hostFieldStage = nullptr;	 // the pinned copy of a one-shot call's list the device copy reads, and the event of that copy
 	size_t hostFieldStageBytes = 0;
 	hipEvent_t evFieldStaged = nullptr;
+	// actuators (actuators.hip; s2amd_world_set_actuators, s2amd_world_set_actions, s2amd_world_import_actions): a write in front of the
+	// persistent fields, kept and released beside them
+	std::vector<s2amdActuator> hActuators; // the persistent list as the caller set it: held across uploads
+	int actuatorChannels = 0;			   // floats of the action buffer (0 with no list)
+	bool actuatorsRepeated = false;		   // some target occurs twice: the step runs the walk kernel behind the term kernel
+	DevBuf dActuators;					   // {two sets of status counts, the list, the order by target, the terms, the states, the action buffer}, written by the setter
+	long actuatorPasses = 0;			   // passes since the list was set: pass k counts into set k & 1 and clears the other
+	bool actuatorStatesValid = false;	   // a step has applied the list since it was set and since the last upload
+	float* hostActionStage = nullptr;	   // the pinned copy of s2amd_world_set_actions' values the device copy reads, and the event of that copy
+	size_t hostActionStageBytes = 0;
+	hipEvent_t evActionStaged = nullptr;
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -875,6 +886,10 @@ int gridReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int fieldsStepEnqueue(s2amdSolver* s);
 void fieldsForgetWorld(s2amdSolver* s);
 void fieldsRelease(s2amdSolver* s);
+// actuators.hip: the persistent list in front of the fields (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
+int actuatorsStepEnqueue(s2amdSolver* s);
+void actuatorsForgetWorld(s2amdSolver* s);
+void actuatorsRelease(s2amdSolver* s);
 
 // report_host.cpp: the walks over the table ...
 void reportsForget(s2amdSolver* s);									 // no report is of the last step any more (a new upload)

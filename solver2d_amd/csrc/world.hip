@@ -534,6 +534,7 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 	}
 	s->worldResident = false;
 	reportsForget(s);
+	actuatorsForgetWorld(s); // (the actuators' states are of a pass over the world that leaves: actuators.hip)
 	fieldsForgetWorld(s); // (the body -> shapes list of the force fields belongs to the world it was built for: force_field.hip)
 	s->pairKeysValid = false;
 	s->pairQueryUsed = false, s->pairCacheValid = false;
@@ -732,6 +733,15 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 	// behind it saw the bodies of the previous step (same AABBs, nothing enlarged): the solve is repeated on the
 	// multi-launch path, and so is the refit.
 	s->slotBytesFresh = false;
+	// the actuators (actuators.hip; s2amd_world_set_actuators), once per call and in front of the fields, which see what they set.  Nothing with no list.
+	if (!s->hActuators.empty())
+	{
+		int rcActuators = actuatorsStepEnqueue(s);
+		if (rcActuators)
+		{
+			return rcActuators;
+		}
+	}
 	// the persistent force fields (force_field.hip; s2amd_world_set_fields), once per call: in front of stage 3 and outside the loop below
 	// that repeats a solve, whose dead hand-off leaves the wire arrays -- these writes among them -- as they were.  Nothing with no list.
 	if (!s->hFields.empty())

@@ -36,6 +36,8 @@ EXPORTS = [
     "s2amd_world_collide_shape", "s2amd_world_deepest_contact",
     "s2amd_world_cast_shape", "s2amd_world_cast_shape_all", "s2amd_world_move_shapes",
     "s2amd_world_edit", "s2amd_world_apply_fields", "s2amd_world_set_fields", "s2amd_world_field_states",
+    "s2amd_world_set_actuators", "s2amd_world_set_actions", "s2amd_world_import_actions", "s2amd_world_actuator_states", "s2amd_world_actuator_counts",
+    "s2amd_device_write",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
     "s2amd_world_ray_events",
@@ -145,6 +147,12 @@ def load(fast=False):
     L.s2amd_world_apply_fields.argtypes = [vp, vp, i32, vp]
     L.s2amd_world_set_fields.argtypes = [vp, vp, i32]
     L.s2amd_world_field_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_set_actuators.argtypes = [vp, vp, i32, i32]
+    L.s2amd_world_set_actions.argtypes = [vp, vp, i32, i32]
+    L.s2amd_world_import_actions.argtypes = [vp, vp, i32, i32]
+    L.s2amd_world_actuator_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_actuator_counts.argtypes = [vp, vp]
+    L.s2amd_device_write.argtypes = [vp, vp, vp, ctypes.c_uint64]
     L.s2amd_world_set_sensors.argtypes = [vp, vp, i32]
     L.s2amd_world_set_sensor_report.argtypes = [vp, i32, i32]
     L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -369,6 +377,11 @@ class Solver:
         self._ck(self._L.s2amd_device_read(self._h, wire.as_ptr(out.reshape(-1)), ctypes.c_void_p(int(ptr)), out.nbytes))
         return out
 
+    def device_write(self, ptr, values):
+        """The bytes of a numpy array into device memory at `ptr` (device_alloc, or any device pointer), behind the solver's stream."""
+        values = np.ascontiguousarray(values)
+        self._ck(self._L.s2amd_device_write(self._h, ctypes.c_void_p(int(ptr)), wire.as_ptr(values.reshape(-1)), values.nbytes))
+
     def measure_dominant(self, params, repeats=20):
         """(us per launch, launches per sweep, constraints per launch) of the dominant kernel; see
         s2amd_measure_dominant."""
@@ -572,6 +585,35 @@ class Solver:
         skipped = ctypes.c_int32(-1)
         self._ck(self._L.s2amd_world_edit(self._h, wire.as_ptr(edits), len(edits), ctypes.byref(skipped) if want_skipped else None))
         return skipped.value if want_skipped else None
+
+    # ---- actuators on the resident world (s2amd_world_set_actuators, ...): channels of a device-side action vector drive every step ----
+    def world_set_actuators(self, actuators, channels):
+        """Replaces the whole persistent list (wire.actuator_dtype; an empty one clears it) and zeroes the action buffer of `channels`
+        floats: every world_step applies the list in front of the persistent fields."""
+        actuators = np.ascontiguousarray(actuators)
+        assert actuators.dtype == wire.actuator_dtype
+        self._ck(self._L.s2amd_world_set_actuators(self._h, wire.as_ptr(actuators) if len(actuators) else None, len(actuators), int(channels)))
+        self._world_actuators = len(actuators)
+
+    def world_set_actions(self, values, first=0):
+        """Host values into channels [first, first + len(values)) of the action buffer; enqueued, no wait."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        self._ck(self._L.s2amd_world_set_actions(self._h, wire.as_ptr(values) if len(values) else None, int(first), len(values)))
+
+    def world_import_actions(self, device_ptr, count, first=0):
+        """`count` floats from device memory (device_alloc, or a torch tensor's data_ptr() whose producer stream has been synchronised)
+        into channels [first, first + count) of the action buffer; enqueued, no wait."""
+        self._ck(self._L.s2amd_world_import_actions(self._h, ctypes.c_void_p(int(device_ptr)), int(first), int(count)))
+
+    def world_actuator_states(self):
+        """wire.actuator_state_dtype records, one per actuator of the list, of the last world_step's pass."""
+        return self._world_list(self._L.s2amd_world_actuator_states, wire.actuator_state_dtype, getattr(self, "_world_actuators", 0))
+
+    def world_actuator_counts(self):
+        """int32[4]: actuators per status {APPLIED, DISABLED, SKIPPED, NONFINITE} of the last world_step's pass."""
+        counts = np.zeros(4, dtype=np.int32)
+        self._ck(self._L.s2amd_world_actuator_counts(self._h, wire.as_ptr(counts)))
+        return counts
 
     # ---- force fields on the resident world (s2amd_world_apply_fields, s2amd_world_set_fields): writes addressed by region ----
     def world_apply_fields(self, fields, want_states=True):

@@ -410,3 +410,33 @@ def field_drag(position, range_, strength, **kw):
 def field_list(fields):
     """A list of the records above (or an array of them) as one contiguous wire.field_dtype array."""
     return np.ascontiguousarray(np.array(list(fields), dtype=field_dtype)) if len(fields) else np.zeros(0, dtype=field_dtype)
+
+
+# actuators on the resident world (include/solver2d_amd.h: s2amd_world_set_actuators, s2amd_world_set_actions, s2amd_world_import_actions)
+MAX_ACTUATORS, MAX_ACTION_CHANNELS = 16384, 65536
+ACTUATOR_BODY_FORCE, ACTUATOR_BODY_THRUST, ACTUATOR_BODY_LINEAR_VELOCITY, ACTUATOR_BODY_ANGULAR_VELOCITY = 1, 2, 3, 4
+ACTUATOR_REVOLUTE_MOTOR_SPEED, ACTUATOR_REVOLUTE_SERVO, ACTUATOR_MOUSE_TARGET = 5, 6, 7
+ACTUATOR_WIDTH = {1: 2, 2: 1, 3: 2, 4: 1, 5: 1, 6: 1, 7: 2}
+ACTUATOR_DISABLED = 1
+ACTUATOR_STATUS_APPLIED, ACTUATOR_STATUS_DISABLED, ACTUATOR_STATUS_SKIPPED, ACTUATOR_STATUS_NONFINITE = 0, 1, 2, 3
+# s2amdActuator, s2amdActuatorState
+actuator_dtype = np.dtype([("kind", np.int32), ("target", np.int32), ("channel", np.int32), ("flags", np.int32), ("gain", np.float32),
+                           ("bias", np.float32), ("lower", np.float32), ("upper", np.float32), ("axis", np.float32, 2), ("kp", np.float32),
+                           ("maxSpeed", np.float32), ("reserved", np.int32, 4)])
+actuator_state_dtype = np.dtype([("actuator", np.int32), ("target", np.int32), ("status", np.int32), ("pad", np.int32), ("action", np.float32, 2),
+                                 ("command", np.float32, 2), ("output", np.float32, 2), ("angle", np.float32), ("pad2", np.int32)])
+ACTUATOR_SIZE, ACTUATOR_STATE_SIZE = actuator_dtype.itemsize, actuator_state_dtype.itemsize
+assert ACTUATOR_SIZE == 64 and ACTUATOR_STATE_SIZE == 48
+
+
+def actuator(kind, target, channel, gain=1.0, bias=0.0, lower=-np.inf, upper=np.inf, axis=(0.0, 0.0), kp=0.0, max_speed=0.0, flags=0):
+    """One wire.actuator_dtype record: channels [channel, channel + ACTUATOR_WIDTH[kind]) of the action vector drive `target`."""
+    a = np.zeros(1, dtype=actuator_dtype)[0]
+    a["kind"], a["target"], a["channel"], a["flags"] = kind, target, channel, flags
+    a["gain"], a["bias"], a["lower"], a["upper"], a["axis"], a["kp"], a["maxSpeed"] = gain, bias, lower, upper, axis, kp, max_speed
+    return a
+
+
+def actuator_list(actuators):
+    """A list of the records above (or an array of them) as one contiguous wire.actuator_dtype array."""
+    return np.ascontiguousarray(np.array(list(actuators), dtype=actuator_dtype)) if len(actuators) else np.zeros(0, dtype=actuator_dtype)
