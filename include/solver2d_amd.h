@@ -1477,8 +1477,8 @@ int s2amd_world_field_states(s2amdSolver* solver, s2amdFieldState* out, int32_t 
 /* (additive, API 5) Actuators: the write half of a control loop that stays on the device.  A persistent list of actuators maps channels
  * of an ACTION VECTOR that lives in device memory onto s2amd_world_edit's edits, in front of every s2amd_world_step: a policy network's
  * output, a PD controller's set points or a scripted platform's velocities arrive device to device (s2amd_world_import_actions), the
- * observations leave device to device (s2amd_world_export_ray_ranges, s2amd_world_export_grid_occupancy, s2amd_export_poses), and a step
- * with actuators gains no host wait.  Nothing is downloaded and the structure is kept, as with an edit.
+ * observations leave device to device (s2amd_world_export_observations, s2amd_world_export_ray_ranges, s2amd_world_export_grid_occupancy,
+ * s2amd_export_poses), and a step with actuators gains no host wait.  Nothing is downloaded and the structure is kept, as with an edit.
  *   Action buffer the library owns one float[channels] in device memory, zeroed whenever the list is replaced; values hold until they
  *                 are overwritten (zero-order hold), across steps and uploads.  s2amd_world_set_actions copies host values into
  *                 [first, first + count) through pinned memory: the caller may reuse its array on return.  s2amd_world_import_actions
@@ -1566,6 +1566,110 @@ int s2amd_world_set_actions(s2amdSolver* solver, const float* hostValues, int32_
 int s2amd_world_import_actions(s2amdSolver* solver, const void* deviceValues, int32_t first, int32_t count); /* device -> the same, as s2amd_export_poses in reverse */
 int s2amd_world_actuator_states(s2amdSolver* solver, s2amdActuatorState* out, int32_t capacity, int32_t* count);
 int s2amd_world_actuator_counts(s2amdSolver* solver, int32_t counts[4]); /* actuators per status {APPLIED, DISABLED, SKIPPED, NONFINITE} */
+
+/* (additive, API 5) Observers: the read half of a control loop that stays on the device.  A persistent list of observers maps quantities
+ * of the resident world, and of the reports that already run behind the step, onto channels of an OBSERVATION VECTOR in the library's
+ * device memory: joint angles and speeds, a body's pose and velocity in another body's frame, whether a foot touches, a ray range, the
+ * previous action.  The vector is normalised per observer, optionally stacked over the last `frames` steps, and leaves in one
+ * device-to-device call (s2amd_world_export_observations_async) that does not wait for the host.  Everything is read from the resident
+ * arrays AFTER the step's stage 4, like the other reports; the pass is read-only on the world.
+ *   Kinds         xf(b) = {origins[b], bodies[b].rot}; frame < 0 is the world frame.  The raw value x:
+ *                 1 BODY_POINT             width 2  p = s2TransformPoint(xf(target), local); with a frame s2InvTransformPoint(xf(frame), p)
+ *                 2 BODY_ROTATION          width 2  q = rot(target), with a frame s2InvMulRot(rot(frame), rot(target)); x = {q.s, q.c}
+ *                 3 BODY_ANGLE             width 1  atan2f(q.s, q.c) of kind 2's q (the atan2 of the body and joint reports)
+ *                 4 BODY_LINEAR_VELOCITY   width 2  v = linearVelocity(target); with S2AMD_OBSERVER_RELATIVE and a frame
+ *                                                   v = s2Sub(v, linearVelocity(frame)); with a frame s2InvRotateVector(rot(frame), v)
+ *                 5 BODY_ANGULAR_VELOCITY  width 1  w(target); with S2AMD_OBSERVER_RELATIVE and a frame w(target) - w(frame)
+ *                 6 REVOLUTE_ANGLE         width 1  the joint report's `angle` of joint `target` (what the servo actuator measures)
+ *                 7 REVOLUTE_SPEED         width 1  the joint report's `angularSpeed`, w(bodyB) - w(bodyA)
+ *                 8 REVOLUTE_MOTOR_IMPULSE width 1  joints[target].motorImpulse as stored
+ *                 9 BODY_CONTACT           width 2  {touching > 0 ? 1.0f : +0.0f, normalImpulse} of s2amd_world_body_sums' record of body
+ *                                                   `target`, this step
+ *                 10 RAY_RANGE             width 1  entry `target` of s2amd_world_ray_ranges, this step, verbatim
+ *                 11 ACTION                width 1  channel `target` of the actuators' action buffer as it stands when the pass runs,
+ *                                                   which is what this step's actuator pass read
+ *                 `target` is a body slot for kinds 1-5 and 9, a joint slot for kinds 6-8, a ray for kind 10, an action channel for 11.
+ *   Value         for each component i < width: t = gain * x_i (one multiply); t = t + bias (one add);
+ *                 y_i = t < lower ? lower : (t > upper ? upper : t): the actuators' command rule, so a NaN passes through unclamped.
+ *                 fp32, one rounding per operation in the order given, without contraction, in libs2amd.so and libs2amd_fast.so alike.
+ *   Status        decided in this order.  DISABLED: S2AMD_OBSERVER_DISABLED is set.  SKIPPED: the target or the frame is outside the
+ *                 resident capacities or a free slot; a joint that is not revolute (kinds 6-8); kinds 10 and 11 with a target at or
+ *                 beyond the ray count of the ray list or the channels of the actuator list, where such a list is set (with no list
+ *                 there is no count to be beyond: that is SOURCE_OFF).  SOURCE_OFF: kind 9 when the step did not run with
+ *                 S2AMD_REPORT_BODY_SUMS; kind 10 without S2AMD_RAY_REPORT_RANGES or without a ray list; kind 11 without an actuator
+ *                 list.  OBSERVED: everything else.
+ *   Result        float[frames][channels]: frame 0 is this step, frame k the k-th reporting step before it.  An observer that is not
+ *                 OBSERVED writes +0 to its channels and has raw and value +0; channels no observer covers read +0; components beyond
+ *                 the kind's width are +0 in the state.  The first reporting step after a re-base fills every frame with its own
+ *                 vector; a re-base happens at s2amd_world_upload, when the list is replaced, and when the report flags go from 0 to
+ *                 non-zero.  The frames are a ring: a step writes one row and moves no old one, an export is at most two copies.
+ *   When          the ninth report of a step, behind the grid report, so the contact sums and the ray ranges it reads are this
+ *                 step's.  A step with the report flags at 0 neither advances the history nor enqueues anything; any non-zero flags
+ *                 run the pass, S2AMD_OBSERVATION_REPORT_VECTOR opens the vector's three getters and _STATES writes and opens the
+ *                 states.  A step the library repeats reports once.  The list, `channels` and `frames` hold across uploads.  The step
+ *                 gains no host wait; s2amd_world_observations, s2amd_world_export_observations, s2amd_world_observer_states and
+ *                 s2amd_world_observer_counts wait for the stream, s2amd_world_export_observations_async enqueues the copies and an
+ *                 event in `slot` (0..3; s2amd_export_wait) and waits for nothing.  An export is frames * channels floats, a size
+ *                 known on the host.
+ *   Validation    on the host, before anything is replaced: 0 <= count <= S2AMD_MAX_OBSERVERS; with count > 0 a non-NULL list,
+ *                 1 <= channels <= S2AMD_MAX_OBSERVATION_CHANNELS and 1 <= frames <= S2AMD_MAX_OBSERVATION_FRAMES; per record kind in
+ *                 1..11, target >= 0, frame -1 or >= 0 and -1 for kinds 6-11, channel >= 0 and channel + width <= channels, no flag
+ *                 bits beyond DISABLED | RELATIVE, reserved all 0, gain, bias and local finite, lower <= upper and neither a NaN
+ *                 (infinities are allowed); no two observers' channel ranges overlap.  One bad record refuses the whole list with
+ *                 S2AMD_E_INVALID, and the old list, vector and history stand.  The getters: S2AMD_E_STATE without a resident world
+ *                 or when the getter's flag was not set before the last step; S2AMD_E_CAPACITY with *count filled; *count = 0 (and
+ *                 zero counts) with an empty list.
+ *   Cost          channel ranges are disjoint, so the pass is one launch of one lane per observer with no ordering rule; the vector
+ *                 is zeroed once, in the setter.  No float atomics, no sort, no scratch, no host wait in the step.
+ * The reference has no observers: the composition is ours, every term the reference's function of that name.  Not offered: sharded
+ * worlds; observer lists themselves in device memory; mouse-joint quantities; grid cells in the vector (they have their own export,
+ * s2amd_world_export_grid_occupancy); running normalisation statistics; rewards and termination. */
+#define S2AMD_MAX_OBSERVERS 16384
+#define S2AMD_MAX_OBSERVATION_CHANNELS 65536
+#define S2AMD_MAX_OBSERVATION_FRAMES 16
+#define S2AMD_OBSERVER_BODY_POINT 1
+#define S2AMD_OBSERVER_BODY_ROTATION 2
+#define S2AMD_OBSERVER_BODY_ANGLE 3
+#define S2AMD_OBSERVER_BODY_LINEAR_VELOCITY 4
+#define S2AMD_OBSERVER_BODY_ANGULAR_VELOCITY 5
+#define S2AMD_OBSERVER_REVOLUTE_ANGLE 6
+#define S2AMD_OBSERVER_REVOLUTE_SPEED 7
+#define S2AMD_OBSERVER_REVOLUTE_MOTOR_IMPULSE 8
+#define S2AMD_OBSERVER_BODY_CONTACT 9
+#define S2AMD_OBSERVER_RAY_RANGE 10
+#define S2AMD_OBSERVER_ACTION 11
+#define S2AMD_OBSERVER_DISABLED 1
+#define S2AMD_OBSERVER_RELATIVE 2
+#define S2AMD_OBSERVER_STATUS_OBSERVED 0
+#define S2AMD_OBSERVER_STATUS_DISABLED 1
+#define S2AMD_OBSERVER_STATUS_SKIPPED 2
+#define S2AMD_OBSERVER_STATUS_SOURCE_OFF 3
+#define S2AMD_OBSERVATION_REPORT_VECTOR 1
+#define S2AMD_OBSERVATION_REPORT_STATES 2
+typedef struct s2amdObserver /* 64 bytes */
+{
+	int32_t kind;	 /* S2AMD_OBSERVER_BODY_POINT .. _ACTION */
+	int32_t target;	 /* body slot, joint slot, ray or action channel: see Kinds */
+	int32_t frame;	 /* kinds 1-5: the body whose frame the value is expressed in, or -1 for the world frame; -1 otherwise */
+	int32_t channel; /* the first of the kind's `width` channels */
+	int32_t flags;	 /* S2AMD_OBSERVER_DISABLED | S2AMD_OBSERVER_RELATIVE */
+	float gain, bias, lower, upper; /* y = clamp(gain * x + bias, lower, upper) */
+	float local[2];	 /* BODY_POINT: the point in the target's frame */
+	int32_t reserved[5]; /* 0 */
+} s2amdObserver;
+typedef struct s2amdObserverState /* 32 bytes */
+{
+	int32_t observer, status;
+	float raw[2], value[2];
+	int32_t pad[2];
+} s2amdObserverState;
+int s2amd_world_set_observers(s2amdSolver* solver, const s2amdObserver* list, int32_t count, int32_t channels, int32_t frames); /* replaces the list; count 0 clears */
+int s2amd_world_set_observation_report(s2amdSolver* solver, int32_t flags); /* S2AMD_OBSERVATION_REPORT_* */
+int s2amd_world_observations(s2amdSolver* solver, float* out, int32_t capacity, int32_t* count); /* host; frames * channels floats */
+int s2amd_world_export_observations(s2amdSolver* solver, void* deviceVector, int32_t capacity); /* device to device, waits, as s2amd_world_export_ray_ranges */
+int s2amd_world_export_observations_async(s2amdSolver* solver, void* deviceVector, int32_t capacity, int32_t slot); /* enqueued, an event in slot 0..3: s2amd_export_wait(slot) */
+int s2amd_world_observer_states(s2amdSolver* solver, s2amdObserverState* out, int32_t capacity, int32_t* count);
+int s2amd_world_observer_counts(s2amdSolver* solver, int32_t counts[4]); /* observers per status {OBSERVED, DISABLED, SKIPPED, SOURCE_OFF} */
 
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts

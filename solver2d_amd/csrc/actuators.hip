@@ -384,6 +384,12 @@ int actuatorsStepEnqueue(s2amdSolver* s)
 	return S2AMD_OK;
 }
 
+const float* actuatorsActionBuffer(const s2amdSolver* s, int* channels)
+{
+	*channels = s->actuatorChannels;
+	return s->hActuators.empty() || s->dActuators.p == nullptr ? nullptr : actionBuffer(s);
+}
+
 void actuatorsForgetWorld(s2amdSolver* s)
 {
 	s->actuatorStatesValid = false;

@@ -396,6 +396,16 @@ int contactReportEnqueue(s2amdSolver* s, const s2amdStepParams*)
 	return S2AMD_OK;
 }
 
+const s2amdBodyContactSum* contactReportBodySums(const s2amdSolver* s)
+{
+	const ReportState& r = s->contactReport;
+	if ((r.stepFlags & S2AMD_REPORT_BODY_SUMS) == 0 || s->bodyCapacity <= 0 || r.block.p == nullptr)
+	{
+		return nullptr;
+	}
+	return (const s2amdBodyContactSum*)((const char*)r.block.p + layoutOf(s).sums);
+}
+
 #pragma GCC visibility push(default)
 extern "C"
 {

@@ -597,6 +597,17 @@ int rayReportEnqueue(s2amdSolver* s, const s2amdStepParams*)
 	return S2AMD_OK;
 }
 
+const float* rayReportRanges(const s2amdSolver* s, int* rayCount)
+{
+	const ReportState& r = s->rayReport;
+	*rayCount = rayCountOf(s);
+	if ((r.stepFlags & S2AMD_RAY_REPORT_RANGES) == 0 || *rayCount <= 0 || r.block.p == nullptr)
+	{
+		return nullptr;
+	}
+	return (const float*)((const char*)r.block.p + layoutOf(s).ranges);
+}
+
 #pragma GCC visibility push(default)
 extern "C"
 {

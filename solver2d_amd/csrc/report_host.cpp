@@ -1,5 +1,5 @@
 // The host side that the reports of the resident world share (contact_report.hip, joint_report.hip, shape_report.hip, body_report.hip,
-// step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip): the table of the eight in step order with its walks, the block carver, the prepare and enqueue preambles, the
+// step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip, observers.hip): the table of the nine in step order with its walks, the block carver, the prepare and enqueue preambles, the
 // setter skeleton, the one device-to-host copy, and the getter shapes.  A report supplies its layout, its kernels, its prepare and
 // enqueue bodies, and getters that name their list in terms of these ("The report facility").
 #include "solver_internal.h"
@@ -24,6 +24,7 @@ const ReportFacility facilities[] = {
 	{&SolverRest::sensorReport, sensorReportPrepare, sensorReportEnqueue},
 	{&SolverRest::rayReport, rayReportPrepare, rayReportEnqueue},
 	{&SolverRest::gridReport, gridReportPrepare, gridReportEnqueue},
+	{&SolverRest::observationReport, observationPrepare, observationEnqueue},
 };
 
 int badArgument()

@@ -284,6 +284,7 @@ void s2amd_destroy(s2amdSolver* s)
 	reportsRelease(s);
 	fieldsRelease(s);
 	actuatorsRelease(s);
+	observersRelease(s);
 	treesFree(s);
 	if (s->hostError)
 	{

@@ -621,6 +621,15 @@ struct SolverRest
 	float* hostActionStage = nullptr;	   // the pinned copy of s2amd_world_set_actions' values the device copy reads, and the event of that copy
 	size_t hostActionStageBytes = 0;
 	hipEvent_t evActionStaged = nullptr;
+	// observers (observers.hip; s2amd_world_set_observers, s2amd_world_set_observation_report: S2AMD_OBSERVATION_REPORT_*): the ninth of a
+	// step.  Its ReportState carries the flags alone: the device block belongs to the list, as the actuators', and is written by the setter
+	ReportState observationReport;
+	std::vector<s2amdObserver> hObservers; // the persistent list as the caller set it: held across uploads
+	int observationChannels = 0, observationFrames = 0; // the vector is float[frames][channels] (0 with no list)
+	DevBuf dObservers;					   // {two sets of status counts, the list, the states, the ring of `frames` rows}
+	int observationHead = 0;			   // the row of the ring that holds frame 0; frame k is row (head + k) % frames
+	bool observationFresh = true;		   // re-based: the next reporting step writes its vector into every row
+	long observationPasses = 0;			   // passes since the list was set: pass k counts into set k & 1 and clears the other
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -861,7 +870,7 @@ int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
 // The reports behind s2amd_world_step.  Each file keeps its layout, kernels, prepare and enqueue; report_host.cpp holds the table of
-// the seven in step order and what their host sides share.
+// the nine in step order and what their host sides share.
 //   <x>Prepare   the report's device block for the resident world and its "before" state from the arrays just uploaded
 //   <x>Enqueue   the step's passes on the step's stream, behind stage 4 of the attempt that stands (never part of the captured graph)
 int contactReportPrepare(s2amdSolver* s);
@@ -882,6 +891,14 @@ int rayReportPrepare(s2amdSolver* s);
 int rayReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int gridReportPrepare(s2amdSolver* s);
 int gridReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+int observationPrepare(s2amdSolver* s); // (observers.hip: re-bases the history; the block is the setter's)
+int observationEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+void observersRelease(s2amdSolver* s);
+// What the observation pass reads of the reports in front of it, on the device: nullptr means "not this step" (the source report's
+// stepFlags), and the count is that of the list whether or not it reported.
+const s2amdBodyContactSum* contactReportBodySums(const s2amdSolver* s); // contact_report.hip: bodyCapacity records
+const float* rayReportRanges(const s2amdSolver* s, int* rayCount);		 // ray_report.hip: one float per ray
+const float* actuatorsActionBuffer(const s2amdSolver* s, int* channels); // actuators.hip: nullptr with no list
 // force_field.hip: the persistent list in front of stage 3 (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
 int fieldsStepEnqueue(s2amdSolver* s);
 void fieldsForgetWorld(s2amdSolver* s);

@@ -38,6 +38,8 @@ EXPORTS = [
     "s2amd_world_edit", "s2amd_world_apply_fields", "s2amd_world_set_fields", "s2amd_world_field_states",
     "s2amd_world_set_actuators", "s2amd_world_set_actions", "s2amd_world_import_actions", "s2amd_world_actuator_states", "s2amd_world_actuator_counts",
     "s2amd_device_write",
+    "s2amd_world_set_observers", "s2amd_world_set_observation_report", "s2amd_world_observations", "s2amd_world_export_observations",
+    "s2amd_world_export_observations_async", "s2amd_world_observer_states", "s2amd_world_observer_counts",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
     "s2amd_world_ray_events",
@@ -153,6 +155,13 @@ def load(fast=False):
     L.s2amd_world_actuator_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_actuator_counts.argtypes = [vp, vp]
     L.s2amd_device_write.argtypes = [vp, vp, vp, ctypes.c_uint64]
+    L.s2amd_world_set_observers.argtypes = [vp, vp, i32, i32, i32]
+    L.s2amd_world_set_observation_report.argtypes = [vp, i32]
+    L.s2amd_world_observations.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_export_observations.argtypes = [vp, vp, i32]
+    L.s2amd_world_export_observations_async.argtypes = [vp, vp, i32, i32]
+    L.s2amd_world_observer_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_observer_counts.argtypes = [vp, vp]
     L.s2amd_world_set_sensors.argtypes = [vp, vp, i32]
     L.s2amd_world_set_sensor_report.argtypes = [vp, i32, i32]
     L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -613,6 +622,42 @@ class Solver:
         """int32[4]: actuators per status {APPLIED, DISABLED, SKIPPED, NONFINITE} of the last world_step's pass."""
         counts = np.zeros(4, dtype=np.int32)
         self._ck(self._L.s2amd_world_actuator_counts(self._h, wire.as_ptr(counts)))
+        return counts
+
+    # ---- observers on the resident world (s2amd_world_set_observers, ...): the world's state as a device-side observation vector ----
+    def world_set_observers(self, observers, channels, frames=1):
+        """Replaces the whole persistent list (wire.observer_dtype; an empty one clears it): every world_step with the observation report
+        on writes a vector of `channels` floats, kept for the last `frames` reporting steps."""
+        observers = np.ascontiguousarray(observers)
+        assert observers.dtype == wire.observer_dtype
+        self._ck(self._L.s2amd_world_set_observers(self._h, wire.as_ptr(observers) if len(observers) else None, len(observers), int(channels), int(frames)))
+        self._world_observers = (len(observers), int(frames), int(channels)) if len(observers) else (0, 0, 0)
+
+    def world_set_observation_report(self, flags):
+        """wire.OBSERVATION_REPORT_VECTOR | _STATES: what the next world_step reports (0: nothing, and the history stands still)."""
+        self._ck(self._L.s2amd_world_set_observation_report(self._h, int(flags)))
+
+    def world_observations(self):
+        """float32[frames, channels] of the last world_step: frame 0 is that step, frame k the k-th reporting step before it."""
+        _, frames, channels = getattr(self, "_world_observers", (0, 0, 0))
+        return self._world_list(self._L.s2amd_world_observations, np.float32, frames * channels).reshape(frames, channels)
+
+    def world_export_observations(self, device_ptr, capacity):
+        """world_observations' bytes into a device buffer (device_alloc, or a torch tensor's data_ptr()) of `capacity` floats; waits."""
+        self._ck(self._L.s2amd_world_export_observations(self._h, ctypes.c_void_p(int(device_ptr)), int(capacity)))
+
+    def world_export_observations_async(self, device_ptr, capacity, slot=0):
+        """The same copy enqueued behind the steps on the solver's stream, with an event in `slot`; pair with export_wait(slot)."""
+        self._ck(self._L.s2amd_world_export_observations_async(self._h, ctypes.c_void_p(int(device_ptr)), int(capacity), int(slot)))
+
+    def world_observer_states(self):
+        """wire.observer_state_dtype records, one per observer of the list, of the last world_step's pass."""
+        return self._world_list(self._L.s2amd_world_observer_states, wire.observer_state_dtype, getattr(self, "_world_observers", (0, 0, 0))[0])
+
+    def world_observer_counts(self):
+        """int32[4]: observers per status {OBSERVED, DISABLED, SKIPPED, SOURCE_OFF} of the last world_step's pass."""
+        counts = np.zeros(4, dtype=np.int32)
+        self._ck(self._L.s2amd_world_observer_counts(self._h, wire.as_ptr(counts)))
         return counts
 
     # ---- force fields on the resident world (s2amd_world_apply_fields, s2amd_world_set_fields): writes addressed by region ----

@@ -440,3 +440,35 @@ def actuator(kind, target, channel, gain=1.0, bias=0.0, lower=-np.inf, upper=np.
 def actuator_list(actuators):
     """A list of the records above (or an array of them) as one contiguous wire.actuator_dtype array."""
     return np.ascontiguousarray(np.array(list(actuators), dtype=actuator_dtype)) if len(actuators) else np.zeros(0, dtype=actuator_dtype)
+
+
+# observers on the resident world (include/solver2d_amd.h: s2amd_world_set_observers, s2amd_world_set_observation_report)
+MAX_OBSERVERS, MAX_OBSERVATION_CHANNELS, MAX_OBSERVATION_FRAMES = 16384, 65536, 16
+OBSERVER_BODY_POINT, OBSERVER_BODY_ROTATION, OBSERVER_BODY_ANGLE, OBSERVER_BODY_LINEAR_VELOCITY, OBSERVER_BODY_ANGULAR_VELOCITY = 1, 2, 3, 4, 5
+OBSERVER_REVOLUTE_ANGLE, OBSERVER_REVOLUTE_SPEED, OBSERVER_REVOLUTE_MOTOR_IMPULSE = 6, 7, 8
+OBSERVER_BODY_CONTACT, OBSERVER_RAY_RANGE, OBSERVER_ACTION = 9, 10, 11
+OBSERVER_WIDTH = {1: 2, 2: 2, 3: 1, 4: 2, 5: 1, 6: 1, 7: 1, 8: 1, 9: 2, 10: 1, 11: 1}
+OBSERVER_DISABLED, OBSERVER_RELATIVE = 1, 2
+OBSERVER_STATUS_OBSERVED, OBSERVER_STATUS_DISABLED, OBSERVER_STATUS_SKIPPED, OBSERVER_STATUS_SOURCE_OFF = 0, 1, 2, 3
+OBSERVATION_REPORT_VECTOR, OBSERVATION_REPORT_STATES = 1, 2
+# s2amdObserver, s2amdObserverState
+observer_dtype = np.dtype([("kind", np.int32), ("target", np.int32), ("frame", np.int32), ("channel", np.int32), ("flags", np.int32),
+                           ("gain", np.float32), ("bias", np.float32), ("lower", np.float32), ("upper", np.float32), ("local", np.float32, 2),
+                           ("reserved", np.int32, 5)])
+observer_state_dtype = np.dtype([("observer", np.int32), ("status", np.int32), ("raw", np.float32, 2), ("value", np.float32, 2), ("pad", np.int32, 2)])
+OBSERVER_SIZE, OBSERVER_STATE_SIZE = observer_dtype.itemsize, observer_state_dtype.itemsize
+assert OBSERVER_SIZE == 64 and OBSERVER_STATE_SIZE == 32
+
+
+def observer(kind, target, channel, frame=-1, gain=1.0, bias=0.0, lower=-np.inf, upper=np.inf, local=(0.0, 0.0), flags=0):
+    """One wire.observer_dtype record: `target`'s quantity `kind` goes to channels [channel, channel + OBSERVER_WIDTH[kind]) of the
+    observation vector, expressed in body `frame`'s frame (-1: the world's)."""
+    o = np.zeros(1, dtype=observer_dtype)[0]
+    o["kind"], o["target"], o["frame"], o["channel"], o["flags"] = kind, target, frame, channel, flags
+    o["gain"], o["bias"], o["lower"], o["upper"], o["local"] = gain, bias, lower, upper, local
+    return o
+
+
+def observer_list(observers):
+    """A list of the records above (or an array of them) as one contiguous wire.observer_dtype array."""
+    return np.ascontiguousarray(np.array(list(observers), dtype=observer_dtype)) if len(observers) else np.zeros(0, dtype=observer_dtype)
