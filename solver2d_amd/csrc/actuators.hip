@@ -38,11 +38,6 @@ static_assert(sizeof(s2amdActuator) == 64 && sizeof(s2amdActuatorState) == 48, "
 
 #define S2_ACT_SEGMENT_START 0x80000000u // in an entry of the order: the first actuator of its target
 
-inline size_t roundUp(size_t bytes)
-{
-	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-}
-
 // the device block of a list
 struct ActuatorLayout
 {
@@ -53,12 +48,12 @@ ActuatorLayout actuatorLayout(int count, int channels, bool repeated)
 {
 	ActuatorLayout l{};
 	size_t at = 0;
-	l.counts = at, at += roundUp(8 * sizeof(int));
-	l.list = at, at += roundUp((size_t)count * sizeof(s2amdActuator));
-	l.order = at, at += roundUp((size_t)count * sizeof(uint32_t));
-	l.terms = at, at += repeated ? roundUp((size_t)count * sizeof(s2amdWorldEdit)) : 0;
-	l.states = at, at += roundUp((size_t)count * sizeof(s2amdActuatorState));
-	l.actions = at, at += roundUp((size_t)channels * sizeof(float));
+	l.counts = reportTake(at, 8 * sizeof(int));
+	l.list = reportTake(at, (size_t)count * sizeof(s2amdActuator));
+	l.order = reportTake(at, (size_t)count * sizeof(uint32_t));
+	l.terms = repeated ? reportTake(at, (size_t)count * sizeof(s2amdWorldEdit)) : at;
+	l.states = reportTake(at, (size_t)count * sizeof(s2amdActuatorState));
+	l.actions = reportTake(at, (size_t)channels * sizeof(float));
 	l.total = at;
 	return l;
 }
@@ -72,13 +67,6 @@ __host__ __device__ inline int actuatorWidth(int kind)
 __device__ inline bool notFinite(float a)
 {
 	return (__float_as_uint(a) & 0x7f800000u) == 0x7f800000u;
-}
-
-__device__ inline float commandOf(float a, float gain, float bias, float lower, float upper)
-{
-	float t = gain * a;
-	t = t + bias;
-	return t < lower ? lower : (t > upper ? upper : t);
 }
 
 // One lane per actuator: its term and its state.  APPLY: all targets are distinct and the lane applies its own term; otherwise the term
@@ -158,8 +146,8 @@ __global__ __launch_bounds__(S2_BLOCK) void actuatorTermsKernel(const s2amdActua
 			else
 			{
 				status = S2AMD_ACTUATOR_STATUS_APPLIED;
-				u0 = commandOf(a0, map.x, map.y, map.z, map.w);
-				u1 = width == 2 ? commandOf(a1, map.x, map.y, map.z, map.w) : 0.0f;
+				u0 = clampedAffine(a0, map.x, map.y, map.z, map.w);
+				u1 = width == 2 ? clampedAffine(a1, map.x, map.y, map.z, map.w) : 0.0f;
 				if (kind == S2AMD_ACTUATOR_BODY_THRUST)
 				{
 					// s2RotateVector(rot, axis) (math.h:330-341), then s2MulSV
@@ -417,7 +405,11 @@ extern "C"
 
 int s2amd_world_set_actuators(s2amdSolver* s, const s2amdActuator* list, int32_t count, int32_t channels)
 {
-	if (!s || count < 0 || count > S2AMD_MAX_ACTUATORS || (count > 0 && (!list || channels < 1 || channels > S2AMD_MAX_ACTION_CHANNELS)))
+	if (int rc = listArgs(s, list, count, S2AMD_MAX_ACTUATORS))
+	{
+		return rc;
+	}
+	if (count > 0 && (channels < 1 || channels > S2AMD_MAX_ACTION_CHANNELS))
 	{
 		return fail(S2AMD_E_INVALID, "bad argument");
 	}
@@ -456,19 +448,18 @@ int s2amd_world_set_actuators(s2amdSolver* s, const s2amdActuator* list, int32_t
 	}
 	// The list goes to its device block now, so that a step only launches: waited for, because the block of the list before may still be
 	// read by a step in flight and the copies read the caller's memory and a local.
-	HIP_TRY(hipSetDevice(s->device));
 	const ActuatorLayout l = actuatorLayout(count, channels, repeated);
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	if (int rc = s->dActuators.ensure(l.total))
+	const int rc = listUpload(s, s->dActuators, l.total, [&](char* base) {
+		HIP_TRY(hipMemsetAsync(base + l.counts, 0, 8 * sizeof(int), s->stream));
+		HIP_TRY(hipMemcpyAsync(base + l.list, list, (size_t)count * sizeof(s2amdActuator), hipMemcpyHostToDevice, s->stream));
+		HIP_TRY(hipMemcpyAsync(base + l.order, order.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+		HIP_TRY(hipMemsetAsync(base + l.actions, 0, (size_t)channels * sizeof(float), s->stream));
+		return (int)S2AMD_OK;
+	});
+	if (rc)
 	{
 		return rc; // (the old list stands: its block is as it was)
 	}
-	char* base = (char*)s->dActuators.p;
-	HIP_TRY(hipMemsetAsync(base + l.counts, 0, 8 * sizeof(int), s->stream));
-	HIP_TRY(hipMemcpyAsync(base + l.list, list, (size_t)count * sizeof(s2amdActuator), hipMemcpyHostToDevice, s->stream));
-	HIP_TRY(hipMemcpyAsync(base + l.order, order.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-	HIP_TRY(hipMemsetAsync(base + l.actions, 0, (size_t)channels * sizeof(float), s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
 	s->hActuators.assign(list, list + count);
 	s->actuatorChannels = channels;
 	s->actuatorsRepeated = repeated;
@@ -507,7 +498,7 @@ int s2amd_world_set_actions(s2amdSolver* s, const float* hostValues, int32_t fir
 			s->hostActionStage = nullptr;
 			s->hostActionStageBytes = 0;
 		}
-		const size_t want = std::max(roundUp((size_t)s->actuatorChannels * sizeof(float)), (size_t)4096);
+		const size_t want = std::max(reportRound((size_t)s->actuatorChannels * sizeof(float)), (size_t)4096);
 		HIP_TRY(hipHostMalloc((void**)&s->hostActionStage, want, hipHostMallocDefault));
 		s->hostActionStageBytes = want;
 	}
@@ -552,11 +543,8 @@ int s2amd_world_actuator_states(s2amdSolver* s, s2amdActuatorState* out, int32_t
 	{
 		return fail(S2AMD_E_CAPACITY, "actuator state buffer too small");
 	}
-	HIP_TRY(hipSetDevice(s->device));
 	const ActuatorLayout l = actuatorLayout(*count, s->actuatorChannels, s->actuatorsRepeated);
-	HIP_TRY(hipMemcpyAsync(out, (const char*)s->dActuators.p + l.states, (size_t)*count * sizeof(s2amdActuatorState), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return reportCopyOut(s, out, s->dActuators, l.states, *count, sizeof(s2amdActuatorState), hipMemcpyDeviceToHost);
 }
 
 int s2amd_world_actuator_counts(s2amdSolver* s, int32_t counts[4])
@@ -574,12 +562,7 @@ int s2amd_world_actuator_counts(s2amdSolver* s, int32_t counts[4])
 	{
 		return fail(S2AMD_E_STATE, "s2amd_world_actuator_counts: no s2amd_world_step has applied the list since it was set or since the last upload");
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	// (the set the last pass counted into)
-	const int* set = (const int*)s->dActuators.p + 4 * (int)((s->actuatorPasses - 1) & 1);
-	HIP_TRY(hipMemcpyAsync(counts, set, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return listStatusCounts(s, s->dActuators, s->actuatorPasses, counts);
 }
 
 } // extern "C"

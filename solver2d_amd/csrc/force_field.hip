@@ -1,5 +1,5 @@
 // Force fields on the resident world (include/solver2d_amd.h: s2amd_world_apply_fields, s2amd_world_set_fields,
-// s2amd_world_field_states): a write addressed by region.  A field is a sensor's region (sensor_report.hip: the frame, the candidate
+// s2amd_world_field_states): a write addressed by region.  A field is a sensor's region (mount_ops.h: the frame, the candidate
 // box) with a rule that turns every shape of a dynamic body within reach -- the proximity queries' D(q, s).distance <= range
 // (proximity_query.hip; s2ShapeDistance, src/distance.c:485-636) -- into one term, and a term is one of s2amd_world_edit's two
 // additive setters (edit_ops.h: applyBodyEdit).  The statement is sequential: fields in list order, inside a field the shapes in slot
@@ -9,7 +9,7 @@
 //   fieldKeysKernel     the body -> shapes list, once per upload at the first use: key = the body of a live shape (else the body
 //                       count), value = the slot; rocPRIM's radix sort by body is STABLE, so a body's slots stay ascending;
 //                       report_common.h's reportBodyRangesKernel gives each body its run.
-//   fieldPrepareKernel  one lane per field: active, the world transform, the candidate box; the staged record of the apply pass and
+//   fieldPrepareKernel  one lane per field: active, the world transform, the candidate box (mount_ops.h); the staged record of the apply pass and
 //                       the field's state with terms = 0, lowestShape = -1.
 //   fieldApplyKernel    one lane per body slot.  The prepared fields are staged through LDS in chunks of S2_FIELD_CHUNK (144 bytes
 //                       each), every field a broadcast read.  A lane of a dynamic body walks the fields in index order and inside a
@@ -26,6 +26,7 @@
 #define S2_NP_MAX_VERTS 8
 #include "gjk_ops.h"
 #include "proxy_ops.h"
+#include "mount_ops.h"
 #include "edit_ops.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -58,7 +59,7 @@ struct alignas(16) PreparedField
 static_assert(sizeof(PreparedField) == 144, "nine 16-byte words per staged field");
 #define S2_FIELD_WORDS ((int)(sizeof(PreparedField) / sizeof(float4)))
 
-// one list's device block (roundUp: query_list.h): {the list, the prepared records, the states}
+// one list's device block: {the list, the prepared records, the states}
 struct FieldLayout
 {
 	size_t fields, prepared, states, total;
@@ -68,9 +69,9 @@ FieldLayout fieldLayout(int count)
 {
 	FieldLayout l{};
 	size_t at = 0;
-	l.fields = at, at += roundUp((size_t)count * sizeof(s2amdField));
-	l.prepared = at, at += roundUp((size_t)count * sizeof(PreparedField));
-	l.states = at, at += roundUp((size_t)count * sizeof(s2amdFieldState));
+	l.fields = reportTake(at, (size_t)count * sizeof(s2amdField));
+	l.prepared = reportTake(at, (size_t)count * sizeof(PreparedField));
+	l.states = reportTake(at, (size_t)count * sizeof(s2amdFieldState));
 	l.total = at;
 	return l;
 }
@@ -85,12 +86,12 @@ AdjLayout adjLayout(int ns, int nb, size_t tmpBytes)
 {
 	AdjLayout l{};
 	size_t at = 0;
-	l.ranges = at, at += roundUp((size_t)2 * nb * sizeof(int));
-	l.keysIn = at, at += roundUp((size_t)ns * sizeof(uint32_t));
-	l.keysOut = at, at += roundUp((size_t)ns * sizeof(uint32_t));
-	l.valsIn = at, at += roundUp((size_t)ns * sizeof(int));
-	l.valsOut = at, at += roundUp((size_t)ns * sizeof(int));
-	l.sortTmp = at, at += roundUp(tmpBytes);
+	l.ranges = reportTake(at, (size_t)2 * nb * sizeof(int));
+	l.keysIn = reportTake(at, (size_t)ns * sizeof(uint32_t));
+	l.keysOut = reportTake(at, (size_t)ns * sizeof(uint32_t));
+	l.valsIn = reportTake(at, (size_t)ns * sizeof(int));
+	l.valsOut = reportTake(at, (size_t)ns * sizeof(int));
+	l.sortTmp = reportTake(at, tmpBytes);
 	l.total = at;
 	return l;
 }
@@ -121,46 +122,18 @@ __global__ __launch_bounds__(S2_BLOCK) void fieldPrepareKernel(const s2amdField*
 	const s2amdField* q = fields + i;
 	PreparedField* out = prepared + i;
 	const int body = q->body, flags = q->flags;
-	bool active = (flags & S2AMD_FIELD_DISABLED) == 0;
 	Xf xf;
-	xf.p = v2(q->position[0], q->position[1]);
-	xf.q.s = q->rot[0], xf.q.c = q->rot[1];
-	if (active && body >= 0)
-	{
-		active = body < nb && bodies[body].type != S2AMD_BODY_FREE;
-		if (active)
-		{
-			// s2MulTransforms(xf(body), {position, rot}), include/solver2d/math.h:368-374; s2MulRot :291-300
-			const float2 o = origins[body];
-			const float bs = bodies[body].rot[0], bc = bodies[body].rot[1];
-			const float s = bs * xf.q.c + bc * xf.q.s;
-			const float c = bc * xf.q.c - bs * xf.q.s;
-			const float px = (bc * xf.p.x - bs * xf.p.y) + o.x;
-			const float py = (bs * xf.p.x + bc * xf.p.y) + o.y;
-			xf.p = v2(px, py);
-			xf.q.s = s, xf.q.c = c;
-		}
-	}
+	const bool active = mountFrame(q, S2AMD_FIELD_DISABLED, bodies, origins, nb, xf);
 	const int count8 = q->count < 1 ? 1 : q->count > S2_NP_MAX_VERTS ? S2_NP_MAX_VERTS : q->count;
 	float4 box = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	if (active)
 	{
 		// the proximity queries' query box with maxDistance = range
-		V2 lower = xfPoint(xf, v2(q->vertices[0][0], q->vertices[0][1]));
-		V2 upper = lower;
-		for (int k = 1; k < count8; ++k)
-		{
-			const V2 w = xfPoint(xf, v2(q->vertices[k][0], q->vertices[k][1]));
-			lower = v2(S2_MINF(lower.x, w.x), S2_MINF(lower.y, w.y));
-			upper = v2(S2_MAXF(upper.x, w.x), S2_MAXF(upper.y, w.y));
-		}
-		const float r = q->radius + q->range;
-		box = make_float4(lower.x - r, lower.y - r, upper.x + r, upper.y + r);
+		box = mountBox(xf, q->vertices, count8, &q->radius, &q->range);
 	}
 	else
 	{
-		xf.p = v2(0.0f, 0.0f);
-		xf.q.s = 0.0f, xf.q.c = 0.0f;
+		xf = noFrame();
 	}
 	const float4* from = (const float4*)q->vertices;
 	float4* to = (float4*)out->vertices;
@@ -175,14 +148,6 @@ __global__ __launch_bounds__(S2_BLOCK) void fieldPrepareKernel(const s2amdField*
 	st->pad[0] = st->pad[1] = st->pad[2] = 0;
 	st->position[0] = xf.p.x, st->position[1] = xf.p.y, st->rot[0] = xf.q.s, st->rot[1] = xf.q.c;
 	st->box[0] = box.x, st->box[1] = box.y, st->box[2] = box.z, st->box[3] = box.w;
-}
-
-S2_DEV Xf fieldFrame(const PreparedField& q)
-{
-	Xf xf;
-	xf.p = v2(q.position[0], q.position[1]);
-	xf.q.s = q.rot[0], xf.q.c = q.rot[1];
-	return xf;
 }
 
 // what the candidate rule reads of a shape slot
@@ -227,7 +192,7 @@ S2_DEV bool fieldTerm(const PreparedField& q, const s2amdShape* shapes, const Sh
 	{
 		B.count = type == S2AMD_SHAPE_CIRCLE ? 1 : 2;
 	}
-	const ShapeDistanceOutput D = shapeDistanceWithRadii(A, fieldFrame(q), B, bodyXf);
+	const ShapeDistanceOutput D = shapeDistanceWithRadii(A, frameOf(q.position, q.rot), B, bodyXf);
 	if (!(D.distance <= q.range))
 	{
 		return false;
@@ -384,9 +349,9 @@ bool validField(const s2amdField& q)
 // the whole list, before anything is enqueued or replaced
 int checkList(const s2amdSolver* s, const s2amdField* fields, int32_t count)
 {
-	if (!s || count < 0 || count > S2AMD_MAX_FIELDS || (count > 0 && !fields))
+	if (int rc = listArgs(s, fields, count, S2AMD_MAX_FIELDS))
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		return rc;
 	}
 	for (int32_t i = 0; i < count; ++i)
 	{
@@ -420,7 +385,7 @@ int ensureAdjacency(s2amdSolver* s)
 		return rc;
 	}
 	char* base = (char*)s->dFieldAdj.p;
-	HIP_TRY(hipMemsetAsync(base + l.ranges, 0, roundUp((size_t)2 * nb * sizeof(int)), st));
+	HIP_TRY(hipMemsetAsync(base + l.ranges, 0, reportRound((size_t)2 * nb * sizeof(int)), st));
 	if (ns > 0)
 	{
 		fieldKeysKernel<<<gridFor((size_t)ns), dim3(S2_BLOCK), 0, st>>>((const s2amdShape*)s->dShapes.p, ns, nb, (uint32_t*)(base + l.keysIn), (int*)(base + l.valsIn));
@@ -544,7 +509,7 @@ int s2amd_world_apply_fields(s2amdSolver* s, const s2amdField* fields, int32_t c
 			s->hostFieldStage = nullptr;
 			s->hostFieldStageBytes = 0;
 		}
-		const size_t want = std::max(roundUp(listBytes + listBytes / 2), (size_t)4096);
+		const size_t want = std::max(reportRound(listBytes + listBytes / 2), (size_t)4096);
 		HIP_TRY(hipHostMalloc((void**)&s->hostFieldStage, want, hipHostMallocDefault));
 		s->hostFieldStageBytes = want;
 	}
@@ -579,15 +544,15 @@ int s2amd_world_set_fields(s2amdSolver* s, const s2amdField* fields, int32_t cou
 	{
 		// the list goes to its device block now, so that a step only launches: waited for, because the block of the list before may
 		// still be read by a step in flight and the copy reads the caller's memory
-		HIP_TRY(hipSetDevice(s->device));
 		const FieldLayout l = fieldLayout(count);
-		HIP_TRY(hipStreamSynchronize(s->stream));
-		if (int rc = s->dFieldList.ensure(l.total))
+		const int rc = listUpload(s, s->dFieldList, l.total, [&](char* base) {
+			HIP_TRY(hipMemcpyAsync(base + l.fields, fields, (size_t)count * sizeof(s2amdField), hipMemcpyHostToDevice, s->stream));
+			return (int)S2AMD_OK;
+		});
+		if (rc)
 		{
 			return rc; // (the old list stands: its block is as it was or larger)
 		}
-		HIP_TRY(hipMemcpyAsync((char*)s->dFieldList.p + l.fields, fields, (size_t)count * sizeof(s2amdField), hipMemcpyHostToDevice, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
 	}
 	s->hFields.assign(fields, fields + count);
 	s->fieldStatesValid = false;
@@ -618,10 +583,7 @@ int s2amd_world_field_states(s2amdSolver* s, s2amdFieldState* out, int32_t capac
 	{
 		return fail(S2AMD_E_CAPACITY, "field state buffer too small");
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	HIP_TRY(hipMemcpyAsync(out, (const char*)s->dFieldList.p + fieldLayout(*count).states, (size_t)*count * sizeof(s2amdFieldState), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return reportCopyOut(s, out, s->dFieldList, fieldLayout(*count).states, *count, sizeof(s2amdFieldState), hipMemcpyDeviceToHost);
 }
 
 } // extern "C"

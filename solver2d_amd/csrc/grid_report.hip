@@ -6,7 +6,7 @@
 // grid's own body, and with SKIP_STATIC the shapes on static bodies.  The passes are enqueued behind stage 4 of s2amd_world_step and
 // behind the other seven reports, once per step (a repeated step reports once); the report keeps nothing from step to step.
 //
-//   gridPoseKernel        one lane per grid: active, the frame G (s2MulTransforms(xf(body), {position, rot}) for a mounted grid), the
+//   gridPoseKernel        one lane per grid: active and the frame G (mount_ops.h: the mount rule), the
 //                         box of the four corner cells' centres, staged as one 64-byte record; the state with occupied = 0 and
 //                         lowestShape = -1, which the raster pass counts into.
 //   gridCandidatesKernel  the sensor report's mask idea: a workgroup holds one tile of 256 shape slots -- 28 bytes of the slot (body,
@@ -25,8 +25,7 @@
 //                         the popcount of the grid's mask.
 //
 // No float atomics, no scratch.  The point tests are query_ops.h's and gjk_ops.h's, in scene_query.hip's sequence (s2Shape_TestPoint;
-// that file's kernels stay as they were, instruction for instruction); boxesOverlap is a private copy of query_list.h's, whose list
-// kernels this file has no use for.  All arithmetic is fp32 in the reference's operation order; this file is compiled without
+// that file's kernels stay as they were, instruction for instruction).  All arithmetic is fp32 in the reference's operation order; this file is compiled without
 // contraction in both libraries (Makefile).  All device memory is one block sized by gridReportPrepare; a step allocates nothing and
 // waits for nothing -- the getters do.
 #include "report_common.h"
@@ -34,6 +33,7 @@
 #define S2_NP_BLOCK 1 // a polygon is the wave's eight staged vertices (stride 1); the probed point is a one-vertex proxy of the lane's own
 #define S2_NP_MAX_VERTS 8
 #include "query_ops.h"
+#include "mount_ops.h"
 
 #include <cmath>
 #include <cstring>
@@ -47,22 +47,6 @@ static_assert(sizeof(s2amdShape) == 196, "the shape record");
 #define S2_GRID_SENSOR_KNOWN_FLAGS (S2AMD_GRID_SENSOR_DISABLED | S2AMD_GRID_SENSOR_SKIP_STATIC)
 #define S2_GRID_REPORT_KNOWN (S2AMD_GRID_REPORT_CATEGORIES | S2AMD_GRID_REPORT_SHAPES | S2AMD_GRID_REPORT_OCCUPANCY | S2AMD_GRID_REPORT_STATES)
 #define S2_GRID_CHUNK S2_BLOCK // grids a workgroup of the candidates pass stages: one per lane
-
-// s2AABB_Overlaps(fat, box), include/solver2d/aabb.h:111-123: false only when one of the four differences is > 0
-S2_DEV bool boxesOverlap(const float* fat, float lx, float ly, float ux, float uy)
-{
-	const float d1x = lx - fat[2], d1y = ly - fat[3];
-	const float d2x = fat[0] - ux, d2y = fat[1] - uy;
-	if (d1x > 0.0f || d1y > 0.0f)
-	{
-		return false;
-	}
-	if (d2x > 0.0f || d2y > 0.0f)
-	{
-		return false;
-	}
-	return true;
-}
 
 // a grid as the candidates and the raster pass read it: the frame, the rule's fields, the extent, the candidate box
 struct alignas(16) PosedGrid
@@ -109,11 +93,6 @@ GridLayout gridLayout(int count, size_t cells, size_t cellTiles, int ns)
 	return l;
 }
 
-S2_DEV bool finiteBits(float f)
-{
-	return (asBits(f) & 0x7f800000u) != 0x7f800000u;
-}
-
 // the centre of cell (i, j) in the grid's own frame: everything in front of the one multiply is exact
 S2_DEV V2 cellLocal(int i, int j, int width, int height, float cellSize)
 {
@@ -135,16 +114,16 @@ __global__ __launch_bounds__(S2_BLOCK) void gridPoseKernel(const s2amdGridSensor
 	const int body = q->body, flags = q->flags, width = q->width, height = q->height;
 	const int firstCell = q->pad[0]; // (the prefix sum the setter left there)
 	const float cellSize = q->cellSize;
+	// mount_ops.h's mountFrame, spelt out: called here, the compiler pairs this kernel's loads and multiplies differently, and the kernel is to stay as it was
 	bool active = (flags & S2AMD_GRID_SENSOR_DISABLED) == 0;
 	Xf xf;
 	xf.p = v2(q->position[0], q->position[1]);
 	xf.q.s = q->rot[0], xf.q.c = q->rot[1];
 	if (active && body >= 0)
 	{
-		active = body < nb && bodies[body].type != S2AMD_BODY_FREE;
+		active = liveBody(bodies, nb, body);
 		if (active)
 		{
-			// s2MulTransforms(xf(body), {position, rot}), include/solver2d/math.h:368-374; s2MulRot :291-300
 			const float2 o = origins[body];
 			const float bs = bodies[body].rot[0], bc = bodies[body].rot[1];
 			const float s = bs * xf.q.c + bc * xf.q.s;
@@ -173,10 +152,9 @@ __global__ __launch_bounds__(S2_BLOCK) void gridPoseKernel(const s2amdGridSensor
 			box = make_float4(lower.x, lower.y, upper.x, upper.y);
 		}
 	}
-	if (!active)
+	if (!active) // (the corners of an active mount may still fail)
 	{
-		xf.p = v2(0.0f, 0.0f);
-		xf.q.s = 0.0f, xf.q.c = 0.0f;
+		xf = noFrame();
 	}
 	float4* to = (float4*)(posed + g);
 	to[0] = make_float4(xf.p.x, xf.p.y, xf.q.s, xf.q.c);
@@ -469,18 +447,6 @@ bool validGridSensor(const s2amdGridSensor& q)
 		   (q.flags & ~S2_GRID_SENSOR_KNOWN_FLAGS) == 0;
 }
 
-// the export: `count` floats at `offset` of the block to a device buffer, waited for
-int copyOut(s2amdSolver* s, void* out, size_t offset, int count, size_t size, hipMemcpyKind kind)
-{
-	if (count > 0)
-	{
-		HIP_TRY(hipSetDevice(s->device));
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->gridReport.block.p + offset, (size_t)count * size, kind, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
-}
-
 } // namespace
 
 int gridReportPrepare(s2amdSolver* s)
@@ -544,9 +510,9 @@ extern "C"
 
 int s2amd_world_set_grid_sensors(s2amdSolver* s, const s2amdGridSensor* grids, int32_t count)
 {
-	if (!s || count < 0 || count > S2AMD_MAX_GRID_SENSORS || (count > 0 && !grids))
+	if (int rc = listArgs(s, grids, count, S2AMD_MAX_GRID_SENSORS))
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		return rc;
 	}
 	size_t cells = 0;
 	for (int32_t i = 0; i < count; ++i)
@@ -573,23 +539,12 @@ int s2amd_world_set_grid_sensors(s2amdSolver* s, const s2amdGridSensor* grids, i
 	}
 	std::vector<int32_t> nextTiles;
 	buildTiles(next, nextTiles);
-	// (from here `next`, `nextTiles` and `previousCells` hold what stood before)
-	next.swap(s->hGridSensors);
-	nextTiles.swap(s->hGridTiles);
-	const size_t previousCells = s->gridCells;
-	s->gridCells = cells;
-	const int rc = gridReportPrepare(s);
-	if (rc)
-	{
-		// (the block or the copy failed: the list before stands, under the block it had or a larger one)
-		const std::string why = s2amd_last_error();
-		s->hGridSensors.swap(next);
-		s->hGridTiles.swap(nextTiles);
-		s->gridCells = previousCells;
-		(void)gridReportPrepare(s);
-		return fail(rc, why);
-	}
-	return S2AMD_OK;
+	const auto exchange = [&] {
+		next.swap(s->hGridSensors);
+		nextTiles.swap(s->hGridTiles);
+		std::swap(cells, s->gridCells);
+	};
+	return listSwapIn(s, exchange, gridReportPrepare);
 }
 
 int s2amd_world_set_grid_report(s2amdSolver* s, int32_t flags)
@@ -631,7 +586,7 @@ int s2amd_world_export_grid_occupancy(s2amdSolver* s, void* deviceCells, int32_t
 	{
 		return fail(S2AMD_E_CAPACITY, "device occupancy buffer too small");
 	}
-	return copyOut(s, deviceCells, layoutOf(s).occupancy, cells, sizeof(float), hipMemcpyDeviceToDevice);
+	return reportCopyOut(s, deviceCells, s->gridReport.block, layoutOf(s).occupancy, cells, sizeof(float), hipMemcpyDeviceToDevice);
 }
 
 int s2amd_world_grid_states(s2amdSolver* s, s2amdGridState* out, int32_t capacity, int32_t* count)

@@ -9,8 +9,7 @@
 // ordering rule.  The lane loads its 64-byte record with four 16-byte loads.  The ring's row, whether the ring is fresh (then grid y =
 // frames and workgroup row y writes row y) and the three source pointers are kernel arguments the host decides when it enqueues:
 // nothing is read back.  The vector is zeroed once, in the setter: channel ranges are static, and a channel no observer covers never
-// changes.  The status counts are the actuators': one ballot per status and one integer atomic per wave that has any, into one of two
-// sets of counters -- a pass counts into one and clears the other for the pass behind it.  No float atomics, no sort, no scratch, no
+// changes.  The status counts are the actuators' (two sets of counters, ping-pong).  No float atomics, no sort, no scratch, no
 // LDS, no host wait.  The arithmetic is fp32 one operation at a time; this file is compiled without contraction in both libraries
 // (Makefile), because the result is stated bit for bit.
 //
@@ -30,11 +29,6 @@ static_assert(sizeof(s2amdObserver) == 64 && sizeof(s2amdObserverState) == 32, "
 
 #define S2_OBSERVATION_KNOWN (S2AMD_OBSERVATION_REPORT_VECTOR | S2AMD_OBSERVATION_REPORT_STATES)
 
-inline size_t roundUp(size_t bytes)
-{
-	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-}
-
 // the device block of a list
 struct ObserverLayout
 {
@@ -45,10 +39,10 @@ ObserverLayout observerLayout(int count, int channels, int frames)
 {
 	ObserverLayout l{};
 	size_t at = 0;
-	l.counts = at, at += roundUp(8 * sizeof(int));
-	l.list = at, at += roundUp((size_t)count * sizeof(s2amdObserver));
-	l.states = at, at += roundUp((size_t)count * sizeof(s2amdObserverState));
-	l.ring = at, at += roundUp((size_t)frames * (size_t)channels * sizeof(float));
+	l.counts = reportTake(at, 8 * sizeof(int));
+	l.list = reportTake(at, (size_t)count * sizeof(s2amdObserver));
+	l.states = reportTake(at, (size_t)count * sizeof(s2amdObserverState));
+	l.ring = reportTake(at, (size_t)frames * (size_t)channels * sizeof(float));
 	l.total = at;
 	return l;
 }
@@ -61,19 +55,6 @@ ObserverLayout layoutOf(const s2amdSolver* s)
 __host__ __device__ inline int observerWidth(int kind)
 {
 	return kind == S2AMD_OBSERVER_BODY_POINT || kind == S2AMD_OBSERVER_BODY_ROTATION || kind == S2AMD_OBSERVER_BODY_LINEAR_VELOCITY || kind == S2AMD_OBSERVER_BODY_CONTACT ? 2 : 1;
-}
-
-// the actuators' command rule (actuators.hip: commandOf): a NaN fails both comparisons and passes through
-__device__ inline float valueOf(float x, float gain, float bias, float lower, float upper)
-{
-	float t = gain * x;
-	t = t + bias;
-	return t < lower ? lower : (t > upper ? upper : t);
-}
-
-__device__ inline bool liveBody(const s2amdBody* bodies, int nb, int body)
-{
-	return body >= 0 && body < nb && bodies[body].type != S2AMD_BODY_FREE;
 }
 
 // the joint report's rot of a joint's body: a body outside the array is unrotated (joint_report.hip: poseOf)
@@ -257,8 +238,8 @@ __global__ __launch_bounds__(S2_BLOCK) void observeKernel(const s2amdObserver* l
 		float y0 = 0.0f, y1 = 0.0f;
 		if (status == S2AMD_OBSERVER_STATUS_OBSERVED)
 		{
-			y0 = valueOf(x0, gain, bias, lower, upper);
-			y1 = width == 2 ? valueOf(x1, gain, bias, lower, upper) : 0.0f;
+			y0 = clampedAffine(x0, gain, bias, lower, upper);
+			y1 = width == 2 ? clampedAffine(x1, gain, bias, lower, upper) : 0.0f;
 		}
 		else
 		{
@@ -328,33 +309,11 @@ ReportRef ref(s2amdSolver* s)
 	return s ? ReportRef{s, &s->observationReport, nullptr, 0, "observation-report", "s2amd_world_set_observation_report"} : ReportRef{};
 }
 
-// a getter's state: the arguments, a resident world whose last step ran with `flag` (0: any) set; *count = `entries`, 0 with no list
+// a getter's state (report_host.cpp: reportGetPerItem): *count = `entries`, 0 and S2AMD_OK with no list whatever else holds
 int getterState(s2amdSolver* s, int flag, const char* what, const void* out, int32_t capacity, int32_t* count, int entries)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	if (s->hObservers.empty())
-	{
-		*count = 0;
-		return S2AMD_OK;
-	}
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	const int stepFlags = s->observationReport.stepFlags;
-	if (flag != 0 ? (stepFlags & flag) == 0 : stepFlags == 0)
-	{
-		return fail(S2AMD_E_STATE, std::string(what) + ": the last s2amd_world_step did not run with this observation-report flag set (s2amd_world_set_observation_report, then a step)");
-	}
-	*count = entries;
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, std::string(what) + ": buffer too small");
-	}
-	return S2AMD_OK;
+	const std::string tooSmall = std::string(what) + ": buffer too small";
+	return reportGetPerItem(ref(s), flag, what, tooSmall.c_str(), out, capacity, count, s && !s->hObservers.empty() ? entries : 0, true);
 }
 
 // frames 0 .. frames - 1 of the ring to `out` (host or device), enqueued: rows [head, frames), then rows [0, head)
@@ -445,8 +404,11 @@ extern "C"
 
 int s2amd_world_set_observers(s2amdSolver* s, const s2amdObserver* list, int32_t count, int32_t channels, int32_t frames)
 {
-	if (!s || count < 0 || count > S2AMD_MAX_OBSERVERS ||
-		(count > 0 && (!list || channels < 1 || channels > S2AMD_MAX_OBSERVATION_CHANNELS || frames < 1 || frames > S2AMD_MAX_OBSERVATION_FRAMES)))
+	if (int rc = listArgs(s, list, count, S2AMD_MAX_OBSERVERS))
+	{
+		return rc;
+	}
+	if (count > 0 && (channels < 1 || channels > S2AMD_MAX_OBSERVATION_CHANNELS || frames < 1 || frames > S2AMD_MAX_OBSERVATION_FRAMES))
 	{
 		return fail(S2AMD_E_INVALID, "bad argument");
 	}
@@ -483,19 +445,18 @@ int s2amd_world_set_observers(s2amdSolver* s, const s2amdObserver* list, int32_t
 	}
 	// The list goes to its device block now, so that a step only launches: waited for, because the block of the list before may still be
 	// read by a step or an export in flight and the copy reads the caller's memory.
-	HIP_TRY(hipSetDevice(s->device));
 	const ObserverLayout l = observerLayout(count, channels, frames);
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	if (int rc = s->dObservers.ensure(l.total))
+	const int rc = listUpload(s, s->dObservers, l.total, [&](char* base) {
+		HIP_TRY(hipMemsetAsync(base + l.counts, 0, 8 * sizeof(int), s->stream));
+		HIP_TRY(hipMemcpyAsync(base + l.list, list, (size_t)count * sizeof(s2amdObserver), hipMemcpyHostToDevice, s->stream));
+		// (once: a channel no observer covers reads +0 from here on)
+		HIP_TRY(hipMemsetAsync(base + l.ring, 0, (size_t)frames * (size_t)channels * sizeof(float), s->stream));
+		return (int)S2AMD_OK;
+	});
+	if (rc)
 	{
 		return rc; // (the old list stands: its block is as it was)
 	}
-	char* base = (char*)s->dObservers.p;
-	HIP_TRY(hipMemsetAsync(base + l.counts, 0, 8 * sizeof(int), s->stream));
-	HIP_TRY(hipMemcpyAsync(base + l.list, list, (size_t)count * sizeof(s2amdObserver), hipMemcpyHostToDevice, s->stream));
-	// (once: a channel no observer covers reads +0 from here on)
-	HIP_TRY(hipMemsetAsync(base + l.ring, 0, (size_t)frames * (size_t)channels * sizeof(float), s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
 	s->hObservers.assign(list, list + count);
 	s->observationChannels = channels, s->observationFrames = frames;
 	s->observationHead = 0;
@@ -555,10 +516,7 @@ int s2amd_world_observer_states(s2amdSolver* s, s2amdObserverState* out, int32_t
 	{
 		return rc;
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	HIP_TRY(hipMemcpyAsync(out, (const char*)s->dObservers.p + layoutOf(s).states, (size_t)*count * sizeof(s2amdObserverState), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return reportCopyOut(s, out, s->dObservers, layoutOf(s).states, *count, sizeof(s2amdObserverState), hipMemcpyDeviceToHost);
 }
 
 int s2amd_world_observer_counts(s2amdSolver* s, int32_t counts[4])
@@ -574,12 +532,7 @@ int s2amd_world_observer_counts(s2amdSolver* s, int32_t counts[4])
 		counts[0] = counts[1] = counts[2] = counts[3] = 0;
 		return S2AMD_OK;
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	// (the set the last pass counted into)
-	const int* set = (const int*)s->dObservers.p + 4 * (int)((s->observationPasses - 1) & 1);
-	HIP_TRY(hipMemcpyAsync(counts, set, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipStreamSynchronize(s->stream));
-	return S2AMD_OK;
+	return listStatusCounts(s, s->dObservers, s->observationPasses, counts);
 }
 
 } // extern "C"

@@ -88,9 +88,7 @@ inline int queryOpen(s2amdSolver* s, bool arguments, const QueryKind& kind, cons
 // The carver over the query block: pieces of at least one byte, 256-byte aligned, in the order they are taken; then one ensure.
 inline size_t queryTake(size_t& at, size_t bytes)
 {
-	const size_t here = at;
-	at += roundUp(bytes);
-	return here;
+	return reportTake(at, bytes);
 }
 
 // where the pieces every call begins with lie: the caller's records, then what the kind stages

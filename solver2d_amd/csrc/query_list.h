@@ -1,7 +1,8 @@
 // What the queries on the resident world share on the device (scene_query.hip, proximity_query.hip, contact_query.hip, shape_cast.hip;
-// sensor_report.hip and force_field.hip use parts): the candidate rule's box test, the second half of the ballot-mask -> tile-prefix ->
+// sensor_report.hip and force_field.hip use parts): the second half of the ballot-mask -> tile-prefix ->
 // offsets -> write sequence that turns per-wave hit masks into CSR lists ascending by slot, the no-hit key of the single-answer queries
-// with its decoding (keySlot), the query of a list entry (entryQuery), and two small host helpers (roundUp, queryState).  The first half
+// with its decoding (keySlot), the query of a list entry (entryQuery), and a small host helper (queryState).  The candidate rule's box
+// test is report_common.h's boxesOverlap.  The first half
 // of the sequence -- the mask kernel -- is each file's own; the host side that drives it all is query_host.h.  Everything is in an unnamed
 // namespace: each file holds its own copy of the kernels under the same names.
 //
@@ -19,22 +20,6 @@ namespace
 
 #define S2_QUERY_CHUNK S2_BLOCK // queries a workgroup stages: one per lane
 #define S2_QUERY_MAX_COUNT (65535 * S2_QUERY_CHUNK)
-
-// s2AABB_Overlaps(fat, box), include/solver2d/aabb.h:111-123: false only when one of the four differences is > 0
-S2_DEV bool boxesOverlap(const float* fat, float lx, float ly, float ux, float uy)
-{
-	const float d1x = lx - fat[2], d1y = ly - fat[3];
-	const float d2x = fat[0] - ux, d2y = fat[1] - uy;
-	if (d1x > 0.0f || d1y > 0.0f)
-	{
-		return false;
-	}
-	if (d2x > 0.0f || d2y > 0.0f)
-	{
-		return false;
-	}
-	return true;
-}
 
 S2_DEV int tileHits(const unsigned long long* masks, size_t tileWord)
 {
@@ -167,11 +152,6 @@ S2_DEV int entryQuery(const int* offsets, int count, int e)
 		}
 	}
 	return lo;
-}
-
-inline size_t roundUp(size_t bytes)
-{
-	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
 }
 
 inline int queryState(const s2amdSolver* s)

@@ -5,7 +5,7 @@
 // body, and with SKIP_STATIC the shapes on static bodies.  The passes are enqueued behind stage 4 of s2amd_world_step and behind the
 // other six reports, once per step (a repeated step reports once); the report owns its "before" state on the device.
 //
-//   rayPoseKernel              one lane per ray: active, the world ends (xfPoint(xf(body), p) for a mounted ray), the segment box, the
+//   rayPoseKernel              one lane per ray: active (liveBody, finiteBits), the world ends (xfPoint(xf(body), p) for a mounted ray), the segment box, the
 //                              excluded body, staged as one 48-byte record; the ray's key set to the no-hit key.  Per group of 64 rays
 //                              (a wave here: one fan of 64) the union of the segment boxes of the group's active rays, reduced by wave
 //                              shuffles: the group box.  A group without an active ray is marked empty; one with a box that is not
@@ -35,6 +35,7 @@
 #define S2_NP_BLOCK S2_BLOCK
 #define S2_NP_MAX_VERTS 8
 #include "query_ops.h"
+#include "mount_ops.h"
 
 #include <cmath>
 
@@ -98,11 +99,6 @@ RayLayout rayLayout(int count)
 	return l;
 }
 
-S2_DEV bool finiteBits(float f)
-{
-	return (asBits(f) & 0x7f800000u) != 0x7f800000u;
-}
-
 // posed[i], keys[i] = the no-hit key, and boxes[blockIdx.x * 4 + wave]
 __global__ __launch_bounds__(S2_BLOCK) void rayPoseKernel(const s2amdRaySensor* rays, int count, const s2amdBody* bodies, const float2* origins, int nb, PosedRay* posed,
 														  unsigned long long* keys, GroupBox* boxes)
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(S2_BLOCK) void rayPoseKernel(const s2amdRaySensor* 
 		active = (flags & S2AMD_RAY_SENSOR_DISABLED) == 0;
 		if (active && body >= 0)
 		{
-			active = body < nb && bodies[body].type != S2AMD_BODY_FREE;
+			active = liveBody(bodies, nb, body);
 			if (active)
 			{
 				Xf xf;
@@ -512,41 +508,6 @@ bool validRaySensor(const s2amdRaySensor& r)
 	return finite && 0.0f <= r.maxFraction && r.maxFraction < 100000.0f && (r.flags & ~S2_RAY_SENSOR_KNOWN_FLAGS) == 0;
 }
 
-// a getter whose list has one entry per ray (no head): its state, the count, the capacity
-int perRayGetter(s2amdSolver* s, int flag, const char* what, const char* tooSmall, const void* out, int32_t capacity, int32_t* count)
-{
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	if ((s->rayReport.stepFlags & flag) == 0)
-	{
-		return fail(S2AMD_E_STATE, std::string(what) + ": the last s2amd_world_step did not run with this ray-report flag set (s2amd_world_set_ray_report, then a step)");
-	}
-	*count = rayCountOf(s);
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, tooSmall);
-	}
-	return S2AMD_OK;
-}
-
-// `count` entries of `size` bytes at `offset` of the block to `out` (host or device), waited for
-int copyOut(s2amdSolver* s, void* out, size_t offset, int count, size_t size, hipMemcpyKind kind)
-{
-	if (count > 0)
-	{
-		HIP_TRY(hipSetDevice(s->device));
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->rayReport.block.p + offset, (size_t)count * size, kind, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
-}
-
 } // namespace
 
 int rayReportPrepare(s2amdSolver* s)
@@ -614,9 +575,9 @@ extern "C"
 
 int s2amd_world_set_ray_sensors(s2amdSolver* s, const s2amdRaySensor* rays, int32_t count)
 {
-	if (!s || count < 0 || count > S2AMD_MAX_RAY_SENSORS || (count > 0 && !rays))
+	if (int rc = listArgs(s, rays, count, S2AMD_MAX_RAY_SENSORS))
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		return rc;
 	}
 	for (int32_t i = 0; i < count; ++i)
 	{
@@ -627,18 +588,8 @@ int s2amd_world_set_ray_sensors(s2amdSolver* s, const s2amdRaySensor* rays, int3
 		}
 	}
 	// "before" of the next step is taken under the new list: the change itself is no event; the last step's report is void
-	std::vector<s2amdRaySensor> old(rays, rays + count);
-	old.swap(s->hRaySensors);
-	const int rc = rayReportPrepare(s);
-	if (rc)
-	{
-		// (the block or the copy failed: the old list stands, under the block it had or a larger one)
-		const std::string why = s2amd_last_error();
-		s->hRaySensors.swap(old);
-		(void)rayReportPrepare(s);
-		return fail(rc, why);
-	}
-	return S2AMD_OK;
+	std::vector<s2amdRaySensor> next(rays, rays + count);
+	return listSwapIn(s, [&] { next.swap(s->hRaySensors); }, rayReportPrepare);
 }
 
 int s2amd_world_set_ray_report(s2amdSolver* s, int32_t flags)
@@ -646,23 +597,25 @@ int s2amd_world_set_ray_report(s2amdSolver* s, int32_t flags)
 	return reportSet(ref(s), flags, S2_RAY_REPORT_KNOWN, rayReportPrepare);
 }
 
+// (the states and the ranges need no head: one entry per ray)
 int s2amd_world_ray_states(s2amdSolver* s, s2amdRayState* out, int32_t capacity, int32_t* count)
 {
-	const int rc = perRayGetter(s, S2AMD_RAY_REPORT_STATES, "s2amd_world_ray_states", "ray state buffer too small", out, capacity, count);
-	return rc ? rc : copyOut(s, out, layoutOf(s).states, *count, sizeof(s2amdRayState), hipMemcpyDeviceToHost);
+	const int rc = reportGetPerItem(ref(s), S2AMD_RAY_REPORT_STATES, "s2amd_world_ray_states", "ray state buffer too small", out, capacity, count, s ? rayCountOf(s) : 0);
+	return rc ? rc : reportCopyOut(s, out, s->rayReport.block, layoutOf(s).states, *count, sizeof(s2amdRayState), hipMemcpyDeviceToHost);
 }
 
 int s2amd_world_ray_ranges(s2amdSolver* s, float* out, int32_t capacity, int32_t* count)
 {
-	const int rc = perRayGetter(s, S2AMD_RAY_REPORT_RANGES, "s2amd_world_ray_ranges", "ray range buffer too small", out, capacity, count);
-	return rc ? rc : copyOut(s, out, layoutOf(s).ranges, *count, sizeof(float), hipMemcpyDeviceToHost);
+	const int rc = reportGetPerItem(ref(s), S2AMD_RAY_REPORT_RANGES, "s2amd_world_ray_ranges", "ray range buffer too small", out, capacity, count, s ? rayCountOf(s) : 0);
+	return rc ? rc : reportCopyOut(s, out, s->rayReport.block, layoutOf(s).ranges, *count, sizeof(float), hipMemcpyDeviceToHost);
 }
 
 int s2amd_world_export_ray_ranges(s2amdSolver* s, void* deviceRanges, int32_t capacity)
 {
 	int32_t count = 0;
-	const int rc = perRayGetter(s, S2AMD_RAY_REPORT_RANGES, "s2amd_world_export_ray_ranges", "device range buffer too small", deviceRanges, capacity, &count);
-	return rc ? rc : copyOut(s, deviceRanges, layoutOf(s).ranges, count, sizeof(float), hipMemcpyDeviceToDevice);
+	const int rc = reportGetPerItem(ref(s), S2AMD_RAY_REPORT_RANGES, "s2amd_world_export_ray_ranges", "device range buffer too small", deviceRanges, capacity, &count,
+									s ? rayCountOf(s) : 0);
+	return rc ? rc : reportCopyOut(s, deviceRanges, s->rayReport.block, layoutOf(s).ranges, count, sizeof(float), hipMemcpyDeviceToDevice);
 }
 
 int s2amd_world_ray_events(s2amdSolver* s, s2amdRayEvent* out, int32_t capacity, int32_t* count)

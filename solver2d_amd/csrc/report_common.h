@@ -1,6 +1,7 @@
-// What the reports of the resident world share (contact_report.hip, joint_report.hip, shape_report.hip): the ordered compaction's
-// tile-prefix step, the body-range kernel behind the stable radix sort by body, and the one-wave ordered sum's pieces.  Everything is in
-// an unnamed namespace: each of the files holds its own copy of the kernel below under the same name.
+// What the reports, queries and lists of the resident world share on the device: the candidate rules' box test, the live-body test and
+// the clamp rule of the actuators and observers, the ordered compaction's tile-prefix step, the body-range kernel behind the stable
+// radix sort by body, and the one-wave ordered sum's pieces.  Everything is in an unnamed namespace: each of the files holds its own
+// copy of the kernel below under the same name.
 #pragma once
 
 #include "solver_internal.h"
@@ -32,6 +33,37 @@ S2_DEV float2 transformPoint(float2 origin, float2 rot, float2 p)
 	const float x = (rot.y * p.x - rot.x * p.y) + origin.x;
 	const float y = (rot.x * p.x + rot.y * p.y) + origin.y;
 	return make_float2(x, y);
+}
+
+// s2AABB_Overlaps(fat, box), include/solver2d/aabb.h:111-123: false only when one of the four differences is > 0
+S2_DEV bool boxesOverlap(const float* fat, float lx, float ly, float ux, float uy)
+{
+	const float d1x = lx - fat[2], d1y = ly - fat[3];
+	const float d2x = fat[0] - ux, d2y = fat[1] - uy;
+	if (d1x > 0.0f || d1y > 0.0f)
+	{
+		return false;
+	}
+	if (d2x > 0.0f || d2y > 0.0f)
+	{
+		return false;
+	}
+	return true;
+}
+
+// a body of the array that is in use: what a list entry may be mounted on, what an observer may read
+S2_DEV bool liveBody(const s2amdBody* bodies, int nb, int body)
+{
+	return body >= 0 && body < nb && bodies[body].type != S2AMD_BODY_FREE;
+}
+
+// clamp(gain * x + bias, lower, upper), one operation at a time: an actuator's command, an observer's value.  A NaN fails both
+// comparisons and passes through.
+S2_DEV float clampedAffine(float x, float gain, float bias, float lower, float upper)
+{
+	float t = gain * x;
+	t = t + bias;
+	return t < lower ? lower : (t > upper ? upper : t);
 }
 
 // The tile-prefix step of an ordered compaction: this lane's share of the sum of list `list`'s per-tile counts (counts[list * tiles + b])

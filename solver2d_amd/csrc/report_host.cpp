@@ -1,7 +1,9 @@
 // The host side that the reports of the resident world share (contact_report.hip, joint_report.hip, shape_report.hip, body_report.hip,
 // step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip, observers.hip): the table of the nine in step order with its walks, the block carver, the prepare and enqueue preambles, the
-// setter skeleton, the one device-to-host copy, and the getter shapes.  A report supplies its layout, its kernels, its prepare and
-// enqueue bodies, and getters that name their list in terms of these ("The report facility").
+// setter skeleton, the one device-to-host copy, and the getter shapes; and the host lifecycle of the lists a caller sets (sensors, fields,
+// rays, grids, actuators, observers): the argument check, the two ways a new list goes in, the per-item getter, the copy out and the
+// status counts.  A report supplies its layout, its kernels, its prepare and enqueue bodies, and getters that name their list in terms
+// of these ("The report facility").
 #include "solver_internal.h"
 
 namespace
@@ -83,10 +85,15 @@ void reportsRelease(s2amdSolver* s)
 	}
 }
 
+size_t reportRound(size_t bytes)
+{
+	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
+}
+
 size_t reportTake(size_t& at, size_t bytes)
 {
 	const size_t here = at;
-	at += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
+	at += reportRound(bytes);
 	return here;
 }
 
@@ -233,6 +240,30 @@ int reportGetEvents(const ReportRef& f, int flag, const char* what, const char* 
 	return S2AMD_OK;
 }
 
+int reportGetPerItem(const ReportRef& f, int flag, const char* what, const char* tooSmall, const void* out, int32_t capacity, int32_t* count, int items, bool emptyFirst)
+{
+	if (!f.s || !count || capacity < 0 || (capacity > 0 && !out))
+	{
+		return badArgument();
+	}
+	if (emptyFirst && items == 0)
+	{
+		*count = 0;
+		return S2AMD_OK;
+	}
+	const int rc = getterState(f, flag, what);
+	if (rc)
+	{
+		return rc;
+	}
+	*count = items;
+	if (*count > capacity)
+	{
+		return fail(S2AMD_E_CAPACITY, tooSmall);
+	}
+	return S2AMD_OK;
+}
+
 int reportGetBodyArray(const ReportRef& f, int flag, const char* what, size_t offset, size_t size, void* out, int32_t bodyCapacity)
 {
 	if (!f.s || bodyCapacity < 0 || (bodyCapacity > 0 && !out))
@@ -249,4 +280,65 @@ int reportGetBodyArray(const ReportRef& f, int flag, const char* what, size_t of
 		return fail(S2AMD_E_CAPACITY, "body-sum array smaller than the resident body array");
 	}
 	return fetch(f, out, offset, f.s->bodyCapacity, size);
+}
+
+int reportCopyOut(s2amdSolver* s, void* out, const DevBuf& block, size_t offset, int count, size_t size, hipMemcpyKind kind)
+{
+	if (count > 0)
+	{
+		HIP_TRY(hipSetDevice(s->device));
+		HIP_TRY(hipMemcpyAsync(out, (const char*)block.p + offset, (size_t)count * size, kind, s->stream));
+		HIP_TRY(hipStreamSynchronize(s->stream));
+	}
+	return S2AMD_OK;
+}
+
+int listArgs(const s2amdSolver* s, const void* list, int32_t count, int32_t max)
+{
+	if (!s || count < 0 || count > max || (count > 0 && !list))
+	{
+		return badArgument();
+	}
+	return S2AMD_OK;
+}
+
+int listSwapIn(s2amdSolver* s, const std::function<void()>& exchange, int (*prepare)(s2amdSolver*))
+{
+	exchange();
+	const int rc = prepare(s);
+	if (rc)
+	{
+		// (the block or the copy failed: the list before stands, under the block it had or a larger one)
+		const std::string why = s2amd_last_error();
+		exchange();
+		(void)prepare(s);
+		return fail(rc, why);
+	}
+	return S2AMD_OK;
+}
+
+int listUpload(s2amdSolver* s, DevBuf& block, size_t total, const std::function<int(char*)>& enqueue)
+{
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	if (int rc = block.ensure(total))
+	{
+		return rc;
+	}
+	if (int rc = enqueue((char*)block.p))
+	{
+		return rc;
+	}
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	return S2AMD_OK;
+}
+
+int listStatusCounts(s2amdSolver* s, const DevBuf& block, long passes, int32_t counts[4])
+{
+	HIP_TRY(hipSetDevice(s->device));
+	// (the set the last pass counted into)
+	const int* set = (const int*)block.p + 4 * (int)((passes - 1) & 1);
+	HIP_TRY(hipMemcpyAsync(counts, set, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipStreamSynchronize(s->stream));
+	return S2AMD_OK;
 }

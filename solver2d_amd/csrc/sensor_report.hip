@@ -5,8 +5,8 @@
 // (proximity_query.hip; s2ShapeDistance, src/distance.c:485-636).  The passes are enqueued behind stage 4 of s2amd_world_step and behind
 // the other five reports, once per step (a repeated step reports once); the report owns its "before" state on the device.
 //
-//   sensorPoseKernel     one lane per sensor: active, the world transform (s2MulTransforms(xf(body), {position, rot}) for a sensor on a
-//                        body), the candidate box; the staged record of the mask pass and the fixed fields of the sensor's state.
+//   sensorPoseKernel     one lane per sensor: active, the world transform, the candidate box (mount_ops.h); the staged record of the
+//                        mask pass and the fixed fields of the sensor's state.
 //   sensorMaskKernel     proximity_query.hip's mapping: a workgroup holds one tile of 256 shape slots -- header in registers, the proxy
 //                        vertices in the lane's LDS column -- and walks one chunk of up to 256 posed sensors staged in LDS (128 bytes
 //                        each, 32 KiB), every sensor a broadcast read.  The grid is tiles x chunks.  Per (sensor, tile, wave) it reads the
@@ -26,6 +26,7 @@
 #define S2_NP_MAX_VERTS 8
 #include "gjk_ops.h"
 #include "proxy_ops.h"
+#include "mount_ops.h"
 
 #include <climits>
 #include <cmath>
@@ -99,46 +100,18 @@ __global__ __launch_bounds__(S2_BLOCK) void sensorPoseKernel(const s2amdSensor* 
 	const s2amdSensor* q = sensors + i;
 	PosedSensor* out = posed + i;
 	const int body = q->body, flags = q->flags;
-	bool active = (flags & S2AMD_SENSOR_DISABLED) == 0;
 	Xf xf;
-	xf.p = v2(q->position[0], q->position[1]);
-	xf.q.s = q->rot[0], xf.q.c = q->rot[1];
-	if (active && body >= 0)
-	{
-		active = body < nb && bodies[body].type != S2AMD_BODY_FREE;
-		if (active)
-		{
-			// s2MulTransforms(xf(body), {position, rot}), include/solver2d/math.h:368-374; s2MulRot :291-300
-			const float2 o = origins[body];
-			const float bs = bodies[body].rot[0], bc = bodies[body].rot[1];
-			const float s = bs * xf.q.c + bc * xf.q.s;
-			const float c = bc * xf.q.c - bs * xf.q.s;
-			const float px = (bc * xf.p.x - bs * xf.p.y) + o.x;
-			const float py = (bs * xf.p.x + bc * xf.p.y) + o.y;
-			xf.p = v2(px, py);
-			xf.q.s = s, xf.q.c = c;
-		}
-	}
+	const bool active = mountFrame(q, S2AMD_SENSOR_DISABLED, bodies, origins, nb, xf);
 	const int count8 = q->count < 1 ? 1 : q->count > S2_NP_MAX_VERTS ? S2_NP_MAX_VERTS : q->count;
 	float4 box = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	if (active)
 	{
 		// the proximity queries' query box with maxDistance = margin
-		V2 lower = xfPoint(xf, v2(q->vertices[0][0], q->vertices[0][1]));
-		V2 upper = lower;
-		for (int k = 1; k < count8; ++k)
-		{
-			const V2 w = xfPoint(xf, v2(q->vertices[k][0], q->vertices[k][1]));
-			lower = v2(S2_MINF(lower.x, w.x), S2_MINF(lower.y, w.y));
-			upper = v2(S2_MAXF(upper.x, w.x), S2_MAXF(upper.y, w.y));
-		}
-		const float r = q->radius + q->margin;
-		box = make_float4(lower.x - r, lower.y - r, upper.x + r, upper.y + r);
+		box = mountBox(xf, q->vertices, count8, &q->radius, &q->margin);
 	}
 	else
 	{
-		xf.p = v2(0.0f, 0.0f);
-		xf.q.s = 0.0f, xf.q.c = 0.0f;
+		xf = noFrame();
 	}
 	const float4* from = (const float4*)q->vertices;
 	float4* to = (float4*)out->vertices;
@@ -152,14 +125,6 @@ __global__ __launch_bounds__(S2_BLOCK) void sensorPoseKernel(const s2amdSensor* 
 	st->sensor = i, st->body = body, st->active = active ? 1 : 0, st->pad = 0;
 	st->position[0] = xf.p.x, st->position[1] = xf.p.y, st->rot[0] = xf.q.s, st->rot[1] = xf.q.c;
 	st->box[0] = box.x, st->box[1] = box.y, st->box[2] = box.z, st->box[3] = box.w;
-}
-
-S2_DEV Xf sensorFrame(const PosedSensor& q)
-{
-	Xf xf;
-	xf.p = v2(q.position[0], q.position[1]);
-	xf.q.s = q.rot[0], xf.q.c = q.rot[1];
-	return xf;
 }
 
 // word = ((sensor * tiles) + tile) * 4 + wave, bit = lane: now[word] = the wave's shapes inside the sensor; unless BEFORE also
@@ -214,7 +179,7 @@ __global__ __launch_bounds__(S2_BLOCK) void sensorMaskKernel(const s2amdShape* s
 		{
 			WireProxy A;
 			A.verts = q->vertices, A.count = q->count, A.radius = q->radius;
-			inside = shapeDistanceWithRadii(A, sensorFrame(*q), B, s.xf).distance <= q->margin;
+			inside = shapeDistanceWithRadii(A, frameOf(q->position, q->rot), B, s.xf).distance <= q->margin;
 		}
 		const unsigned long long ballot = __ballot(inside);
 		if (lane == 0)
@@ -561,9 +526,9 @@ extern "C"
 
 int s2amd_world_set_sensors(s2amdSolver* s, const s2amdSensor* sensors, int32_t count)
 {
-	if (!s || count < 0 || count > S2AMD_MAX_SENSORS || (count > 0 && !sensors))
+	if (int rc = listArgs(s, sensors, count, S2AMD_MAX_SENSORS))
 	{
-		return fail(S2AMD_E_INVALID, "bad argument");
+		return rc;
 	}
 	for (int32_t i = 0; i < count; ++i)
 	{
@@ -578,18 +543,8 @@ int s2amd_world_set_sensors(s2amdSolver* s, const s2amdSensor* sensors, int32_t 
 		return fail(S2AMD_E_INVALID, "sensor report: sensors x shape slots beyond 2^31");
 	}
 	// "before" of the next step is taken under the new list: the change itself is no event; the last step's report is void
-	std::vector<s2amdSensor> old(sensors, sensors + count);
-	old.swap(s->hSensors);
-	const int rc = sensorReportPrepare(s);
-	if (rc)
-	{
-		// (the block or the copy failed: the old list stands, under the block it had or a larger one)
-		const std::string why = s2amd_last_error();
-		s->hSensors.swap(old);
-		(void)sensorReportPrepare(s);
-		return fail(rc, why);
-	}
-	return S2AMD_OK;
+	std::vector<s2amdSensor> next(sensors, sensors + count);
+	return listSwapIn(s, [&] { next.swap(s->hSensors); }, sensorReportPrepare);
 }
 
 int s2amd_world_set_sensor_report(s2amdSolver* s, int32_t flags, int32_t listCapacity)
@@ -687,31 +642,9 @@ int s2amd_world_sensor_events(s2amdSolver* s, s2amdSensorEvent* entered, int32_t
 
 int s2amd_world_sensor_states(s2amdSolver* s, s2amdSensorState* out, int32_t capacity, int32_t* count)
 {
-	if (!s || !count || capacity < 0 || (capacity > 0 && !out))
-	{
-		return fail(S2AMD_E_INVALID, "bad argument");
-	}
 	// (the states need no head: their count is the list's)
-	if (!s->worldResident || !s->resident)
-	{
-		return fail(S2AMD_E_STATE, "no resident world");
-	}
-	if ((s->sensorReport.stepFlags & S2AMD_SENSOR_REPORT_STATES) == 0)
-	{
-		return fail(S2AMD_E_STATE, "s2amd_world_sensor_states: the last s2amd_world_step did not run with this sensor-report flag set (s2amd_world_set_sensor_report, then a step)");
-	}
-	*count = sensorCountOf(s);
-	if (*count > capacity)
-	{
-		return fail(S2AMD_E_CAPACITY, "sensor state buffer too small");
-	}
-	if (*count > 0)
-	{
-		HIP_TRY(hipSetDevice(s->device));
-		HIP_TRY(hipMemcpyAsync(out, (const char*)s->sensorReport.block.p + layoutOf(s).states, (size_t)*count * sizeof(s2amdSensorState), hipMemcpyDeviceToHost, s->stream));
-		HIP_TRY(hipStreamSynchronize(s->stream));
-	}
-	return S2AMD_OK;
+	const int rc = reportGetPerItem(ref(s), S2AMD_SENSOR_REPORT_STATES, "s2amd_world_sensor_states", "sensor state buffer too small", out, capacity, count, s ? sensorCountOf(s) : 0);
+	return rc ? rc : reportCopyOut(s, out, s->sensorReport.block, layoutOf(s).states, *count, sizeof(s2amdSensorState), hipMemcpyDeviceToHost);
 }
 
 } // extern "C"

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -925,8 +926,9 @@ struct ReportRef
 	const char* name; // "report", "joint-report", ...: as the messages spell it
 	const char* setter;
 };
-// carves `bytes` (at least one) off a block at `at`, 256-byte aligned: the offset of the piece
+// carves `bytes` (at least one) off a block at `at`, 256-byte aligned: the offset of the piece; reportRound: the size such a piece takes
 size_t reportTake(size_t& at, size_t bytes);
+size_t reportRound(size_t bytes);
 // prepare: the last step's report is void; false: the report is off or no world is resident, nothing to prepare
 bool reportPrepareBegin(const s2amdSolver* s, ReportState& r);
 // ... the block grown to the layout's `total`, both figures noted
@@ -945,6 +947,22 @@ int reportGetEvents(const ReportRef& f, int flag, const char* what, const char* 
 					int32_t firstCapacity, int32_t* firstCount, int32_t* second, int32_t secondCapacity, int32_t* secondCount);
 // ... and one entry per resident body slot (no count, so no head either)
 int reportGetBodyArray(const ReportRef& f, int flag, const char* what, size_t offset, size_t size, void* out, int32_t bodyCapacity);
+// ... and one entry per item of the caller's list (no head either): the argument check, the state, *count = items, the capacity check;
+// the caller copies.  emptyFirst: an empty list answers 0 and S2AMD_OK before the state is looked at (the observers').
+int reportGetPerItem(const ReportRef& f, int flag, const char* what, const char* tooSmall, const void* out, int32_t capacity, int32_t* count, int items, bool emptyFirst = false);
+// `count` entries of `size` bytes at `offset` of `block` to `out` (host or device, as `kind` says), waited for
+int reportCopyOut(s2amdSolver* s, void* out, const DevBuf& block, size_t offset, int count, size_t size, hipMemcpyKind kind);
+// The lists a caller sets (the mounted lists, the actuators, the observers).  listArgs: what every setter checks first, "bad argument".
+int listArgs(const s2amdSolver* s, const void* list, int32_t count, int32_t max);
+// A list whose block is its report's and is prepared again (sensors, rays, grids): `exchange` swaps the new host state in, `prepare`
+// lays the block out under it; if that fails, `exchange` again swaps the old state back, `prepare` again, and the first failure is the answer.
+int listSwapIn(s2amdSolver* s, const std::function<void()>& exchange, int (*prepare)(s2amdSolver*));
+// A list whose block is the setter's (fields, actuators, observers): the stream waited for (a step in flight may read the block), the
+// block grown to `total`, what `enqueue(base)` copies and clears, waited for (it reads the caller's memory).  The caller commits its
+// host state only after S2AMD_OK, so on every failure the old list stands.
+int listUpload(s2amdSolver* s, DevBuf& block, size_t total, const std::function<int(char*)>& enqueue);
+// the four status counts of the last pass: the two sets of four lie at the head of `block`, pass k counts into set k & 1
+int listStatusCounts(s2amdSolver* s, const DevBuf& block, long passes, int32_t counts[4]);
 
 // solver_async.cpp: structure builds in a worker thread on a copy of the solver, adopted a fixed number of steps later
 bool asyncBuildsOn(const s2amdSolver* s);

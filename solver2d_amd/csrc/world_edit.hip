@@ -145,11 +145,6 @@ __global__ __launch_bounds__(S2_BLOCK) void editWalkKernel(const s2amdWorldEdit*
 	}
 }
 
-inline size_t roundUp(size_t bytes)
-{
-	return (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-}
-
 // The pass over the caller's list: every record checked, copied to the pinned stage, its target stamped.  -1: a record is invalid
 // (*bad is its index); 0: all targets distinct; 1: some target occurs twice.
 int checkAndStage(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count, int32_t* bad)
@@ -226,7 +221,7 @@ int s2amd_world_edit(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count,
 			s->hostEditStage = nullptr;
 			s->hostEditStageBytes = 0;
 		}
-		const size_t want = std::max(roundUp(listBytes + listBytes / 2), (size_t)4096);
+		const size_t want = std::max(reportRound(listBytes + listBytes / 2), (size_t)4096);
 		HIP_TRY(hipHostMalloc((void**)&s->hostEditStage, want, hipHostMallocDefault));
 		s->hostEditStageBytes = want;
 	}
@@ -238,19 +233,16 @@ int s2amd_world_edit(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count,
 										 " is invalid (a kind outside 1..8, a target outside the uploaded capacity, reserved != 0): nothing was applied");
 	}
 	// dEdit: {the skip count, the list, [the keys, the sorted keys, rocPRIM's scratch]}
-	size_t at = roundUp(sizeof(int));
-	const size_t listAt = at;
-	at += roundUp(listBytes);
+	size_t at = 0;
+	(void)reportTake(at, sizeof(int));
+	const size_t listAt = reportTake(at, listBytes);
 	size_t keysAt = 0, sortedAt = 0, tmpAt = 0, tmpBytes = 0;
 	if (repeated)
 	{
 		HIP_TRY(rocprim::radix_sort_keys(nullptr, tmpBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (size_t)count, 0, 64, st));
-		keysAt = at;
-		at += roundUp((size_t)count * sizeof(unsigned long long));
-		sortedAt = at;
-		at += roundUp((size_t)count * sizeof(unsigned long long));
-		tmpAt = at;
-		at += roundUp(tmpBytes);
+		keysAt = reportTake(at, (size_t)count * sizeof(unsigned long long));
+		sortedAt = reportTake(at, (size_t)count * sizeof(unsigned long long));
+		tmpAt = reportTake(at, tmpBytes);
 	}
 	if (int rc = s->dEdit.ensure(at))
 	{

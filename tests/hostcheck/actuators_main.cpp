@@ -183,6 +183,18 @@ static void drive(const World& first, const World& second, int count, int target
 		}
 		EXPECT(s2amd_world_set_actuators(s, inside.data(), distinct, here), S2AMD_OK);
 		EXPECT(s->actuatorsRepeated ? 1 : 0, 0);
+		if (count > 0 && count <= S2AMD_MAX_ACTUATORS / 4)
+		{
+			// a longer list whose block cannot be had: the setter fails with the allocation's message before it commits anything
+			int more = 0;
+			std::vector<s2amdActuator> longer = makeList(4 * count + 64, nb, false, &more);
+			setenv("S2_HOSTCHECK_FAIL_MALLOC", "1", 1);
+			EXPECT(s2amd_world_set_actuators(s, longer.data(), (int32_t)longer.size(), more), S2AMD_E_DEVICE);
+			unsetenv("S2_HOSTCHECK_FAIL_MALLOC");
+			EXPECT(strstr(s2amd_last_error(), "hipMalloc") != nullptr, 1);
+			EXPECT((int)s->hActuators.size(), distinct);
+			EXPECT(s->actuatorChannels, here);
+		}
 		askStates(s, distinct, distinct > 0 ? S2AMD_E_STATE : S2AMD_OK, distinct > 0 ? -7 : 0);
 		writers(s, here);
 		EXPECT(s2amd_world_step(s, &params, &info), S2AMD_OK);

@@ -194,6 +194,28 @@ static void drive(const World& first, const World& second, int grids, bool flags
 				EXPECT(s2amd_world_step(s, &params, &info), S2AMD_OK);
 				gettersAfterStep(s, flags, 0, 0);
 				EXPECT(s2amd_world_set_grid_sensors(s, reversed.data(), grids), S2AMD_OK);
+				if (grids <= 300)
+				{
+					// a list of more than twice the grids and cells, whose block cannot be had (larger than any before it: the block
+					// never shrinks): the setter fails with the allocation's message, and the list before stands -- the grids, their
+					// tiles and their cell count -- with its block, prepared again: the next step reports it
+					const size_t tilesBefore = s->hGridTiles.size();
+					std::vector<s2amdGridSensor> longer;
+					for (int k = 0; k < 2 * grids + 64; ++k)
+					{
+						longer.push_back(makeGrid(k, 0));
+					}
+					setenv("S2_HOSTCHECK_FAIL_MALLOC", "1", 1);
+					EXPECT(s2amd_world_set_grid_sensors(s, longer.data(), (int32_t)longer.size()), S2AMD_E_DEVICE);
+					unsetenv("S2_HOSTCHECK_FAIL_MALLOC");
+					EXPECT(strstr(s2amd_last_error(), "hipMalloc") != nullptr, 1);
+					EXPECT((int)s->hGridSensors.size(), grids);
+					EXPECT((int)s->gridCells, cells);
+					EXPECT((int)s->hGridTiles.size(), (int)tilesBefore);
+					gettersRefuse(s, grids, cells);
+					EXPECT(s2amd_world_step(s, &params, &info), S2AMD_OK);
+					gettersAfterStep(s, flags, grids, cells);
+				}
 			}
 		}
 	}

@@ -12,6 +12,8 @@
 //   COPY <kind> <bytes>                                           hipMemcpyAsync
 //   MEMSET <value> <bytes>                                        hipMemsetAsync
 //   SYNC                                                          hipStreamSynchronize
+// While S2_HOSTCHECK_FAIL_MALLOC is set (looked up at every call as well) hipMalloc answers hipErrorOutOfMemory: how a program walks the
+// paths behind a device block that cannot grow (ray_report_main.cpp, grid_report_main.cpp, actuators_main.cpp).
 // Results of a step are therefore meaningless; what is checked is that the host code touches only memory it owns.
 // The product never links this file.
 #include <hip/hip_runtime_api.h>
@@ -173,6 +175,11 @@ const char* hipGetErrorName(hipError_t) { return "hip_stub"; }
 
 hipError_t hipMalloc(void** ptr, size_t size)
 {
+	if (getenv("S2_HOSTCHECK_FAIL_MALLOC") != nullptr)
+	{
+		*ptr = nullptr;
+		return hipErrorOutOfMemory;
+	}
 	*ptr = calloc(size ? size : 1, 1);
 	return *ptr ? hipSuccess : hipErrorOutOfMemory;
 }

@@ -227,6 +227,21 @@ static void drive(const World& first, const World& second, int rays, bool flagsF
 				EXPECT(s2amd_world_step(s, &params, &info), S2AMD_OK);
 				gettersAfterStep(s, flags, 0, 1);
 				EXPECT(s2amd_world_set_ray_sensors(s, reversed.data(), rays), S2AMD_OK);
+				if (rays <= S2AMD_MAX_RAY_SENSORS / 4)
+				{
+					// a longer list whose block cannot be had (longer than any before it: the block never shrinks): the setter fails
+					// with the allocation's message, and the list before stands with its block, prepared again -- the next step reports it
+					std::vector<s2amdRaySensor> longer((size_t)4 * rays + 1024, makeRay(1, 0));
+					setenv("S2_HOSTCHECK_FAIL_MALLOC", "1", 1);
+					EXPECT(s2amd_world_set_ray_sensors(s, longer.data(), (int32_t)longer.size()), S2AMD_E_DEVICE);
+					unsetenv("S2_HOSTCHECK_FAIL_MALLOC");
+					EXPECT(strstr(s2amd_last_error(), "hipMalloc") != nullptr, 1);
+					EXPECT((int)s->hRaySensors.size(), rays);
+					EXPECT(rays == 0 || memcmp(s->hRaySensors.data(), reversed.data(), (size_t)rays * sizeof(s2amdRaySensor)) == 0, 1);
+					gettersRefuse(s, rays);
+					EXPECT(s2amd_world_step(s, &params, &info), S2AMD_OK);
+					gettersAfterStep(s, flags, rays, 1);
+				}
 			}
 		}
 	}
