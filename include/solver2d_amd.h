@@ -1623,7 +1623,8 @@ int s2amd_world_actuator_counts(s2amdSolver* solver, int32_t counts[4]); /* actu
  *                 is zeroed once, in the setter.  No float atomics, no sort, no scratch, no host wait in the step.
  * The reference has no observers: the composition is ours, every term the reference's function of that name.  Not offered: sharded
  * worlds; observer lists themselves in device memory; mouse-joint quantities; grid cells in the vector (they have their own export,
- * s2amd_world_export_grid_occupancy); running normalisation statistics; rewards and termination. */
+ * s2amd_world_export_grid_occupancy); running normalisation statistics.  Rewards and termination are the episode report's, below
+ * (s2amd_world_set_episodes); resetting the bodies of a finished agent is what remains. */
 #define S2AMD_MAX_OBSERVERS 16384
 #define S2AMD_MAX_OBSERVATION_CHANNELS 65536
 #define S2AMD_MAX_OBSERVATION_FRAMES 16
@@ -1670,6 +1671,127 @@ int s2amd_world_export_observations(s2amdSolver* solver, void* deviceVector, int
 int s2amd_world_export_observations_async(s2amdSolver* solver, void* deviceVector, int32_t capacity, int32_t slot); /* enqueued, an event in slot 0..3: s2amd_export_wait(slot) */
 int s2amd_world_observer_states(s2amdSolver* solver, s2amdObserverState* out, int32_t capacity, int32_t* count);
 int s2amd_world_observer_counts(s2amdSolver* solver, int32_t counts[4]); /* observers per status {OBSERVED, DISABLED, SKIPPED, SOURCE_OFF} */
+
+/* (additive, API 5) Episodes: the last leg of a control loop that stays on the device.  A persistent list of EPISODE RULES over AGENTS is
+ * evaluated on the device as the tenth report of a step, on the observation vector of THIS step: it gives one reward and one flags word
+ * per agent, keeps the episode accounting (length, return, automatic restart, time limit) in device memory, and lists the agents that
+ * finished.  Rewards and flags leave in one device-to-device call (s2amd_world_export_episode_step_async) that does not wait for the
+ * host.  The pass is read-only on the world and touches no step kernel.  All arithmetic is fp32, one rounding per operation in the order
+ * given, without contraction, in libs2amd.so and libs2amd_fast.so alike.
+ *   Source        a rule reads the observation vector of this step (the pass runs behind the observers'): a = obs[frameA][channelA],
+ *                 where frame k is row (head + k) % frames of the observers' ring.  With S2AMD_EPISODE_RULE_DIFFERENCE
+ *                 x = a - obs[frameB][channelB] (one subtract), otherwise x = a.  channelA == -1 means no source: x = +0.0f, and the
+ *                 rule is never SKIPPED or SOURCE_OFF.  The first reporting step after the observers' re-base has every frame equal,
+ *                 so a progress rule (frameB = 1 on the same channel) reads +0 there.
+ *   Status        decided in this order.  DISABLED: S2AMD_EPISODE_RULE_DISABLED is set.  SKIPPED: a channel read is at or beyond the
+ *                 current observer list's `channels`, or a frame at or beyond its `frames`, where a list is set (the observer list was
+ *                 replaced by a narrower one).  SOURCE_OFF: a channel is read and the observation report did not run this step, or no
+ *                 observer list is set.  EVALUATED: everything else.  A rule that is not EVALUATED contributes nothing and has
+ *                 x = f = value = +0 and fired = 0.
+ *   Rule value    f = shape(x): LINEAR x, ABS fabsf(x), SQUARE x * x (one multiply).  inside = lower <= f && f <= upper (a NaN is not
+ *                 inside); test = inside != (flags & S2AMD_EPISODE_RULE_OUTSIDE).
+ *                 1 REWARD_VALUE  y = clamp(gain * f + bias, lower, upper): the actuators' and observers' rule, a NaN passes through
+ *                 2 REWARD_TEST   y = test ? gain : bias
+ *                 3 TERMINATE     fired = test; y = test ? gain : +0.0f (gain is the terminal bonus or penalty; bias must be 0)
+ *                 4 TRUNCATE      as TERMINATE, for the other bit
+ *   Agent         per reporting step, one agent's rules taken in LIST ORDER (the reward is a float sum: the order matters to the bit).
+ *                 1. if the pass is fresh (a re-base) or the agent's previous flags & 3 != 0: episodeLength = 0, episodeReturn = +0.
+ *                 2. r = +0; for every EVALUATED rule r = r + y; a fired TERMINATE rule sets S2AMD_EPISODE_TERMINATED, a fired TRUNCATE
+ *                    rule S2AMD_EPISODE_TRUNCATED; `rule` is the list index of the first fired rule, else -1.
+ *                 3. episodeLength += 1; with stepLimits[a] > 0 && episodeLength >= stepLimits[a]: TRUNCATED | TIME_LIMIT.
+ *                 4. episodeReturn = episodeReturn + r; reward = r.
+ *                 5. if flags & 3: episodes += 1, lastReturn = episodeReturn, lastLength = episodeLength; the accounting restarts by
+ *                    itself at the next reporting step (step 1), the vector-environment convention.
+ *                 An agent with no rules has reward +0 and still counts steps.
+ *   Re-base       all accumulators, `episodes` and the last* fields go to zero and the next pass is fresh: at s2amd_world_upload, when
+ *                 the rule list is replaced, and when the report flags go from 0 to non-zero.  A step with the flags at 0 neither
+ *                 counts nor enqueues anything.  A step the library repeats reports once.  The list holds across uploads.
+ *   Events        one record per agent with flags & 3 this step, ascending by agent, with the values of step 5.
+ *   Counts        counts[0..3]: rules per status; counts[4..7]: agents done (flags & 3), terminated, truncated, at the time limit.
+ *                 Integers only, from wave ballots.
+ *   Report flags  any non-zero flags run the pass.  S2AMD_EPISODE_REPORT_STEP opens s2amd_world_episode_rewards, _flags and the two
+ *                 exports; _STATES opens s2amd_world_episode_states; _RULE_STATES writes and opens s2amd_world_episode_rule_states;
+ *                 _EVENTS runs the compaction and opens s2amd_world_episode_events.  s2amd_world_episode_counts answers for any.
+ *   Validation    on the host, before anything is replaced: 0 <= agents <= S2AMD_MAX_EPISODE_AGENTS, 0 <= ruleCount <=
+ *                 S2AMD_MAX_EPISODE_RULES; ruleCount > 0 needs agents > 0 and a non-NULL list; per record kind in 1..4, shape in 0..2,
+ *                 agent in [0, agents), channelA >= -1, frameA >= 0, channelB and frameB >= 0 with DIFFERENCE and 0 without,
+ *                 DIFFERENCE needs channelA >= 0, no unknown flag bits, reserved all 0, gain and bias finite, lower <= upper and
+ *                 neither a NaN (infinities are allowed), bias == 0 for kinds 3 and 4; stepLimits[i] >= 0.  One bad record refuses the
+ *                 whole call with S2AMD_E_INVALID, and the old list and its accounting stand.  Whether a channel fits the observer list
+ *                 is the device's to judge (SKIPPED).  The getters: S2AMD_E_STATE without a resident world or when the getter's flag
+ *                 was not set before the last step; S2AMD_E_CAPACITY with *count filled; *count = 0 (and zero counts) with no list.
+ *   Cost          the setter groups the static list once, stably by (agent, list index).  A reporting step is two launches -- one lane
+ *                 per rule, then one lane per agent walking its contiguous run in order -- and a third, one workgroup, only with
+ *                 S2AMD_EPISODE_REPORT_EVENTS.  No float atomics, no sort, no scratch, no memset and no host wait in the step.
+ * The reference has no episodes: the statement is ours.  Not offered: resetting the bodies of a finished agent (s2Body_SetTransform is
+ * not offered by the edits either: it would move boxes and trees); sharded worlds; rules in device memory; transcendental reward shapes
+ * such as exp or tanh (they cannot be stated bit for bit); discounting; float sums across agents. */
+#define S2AMD_MAX_EPISODE_AGENTS 16384
+#define S2AMD_MAX_EPISODE_RULES 65536
+#define S2AMD_EPISODE_REWARD_VALUE 1
+#define S2AMD_EPISODE_REWARD_TEST 2
+#define S2AMD_EPISODE_TERMINATE 3
+#define S2AMD_EPISODE_TRUNCATE 4
+#define S2AMD_EPISODE_SHAPE_LINEAR 0
+#define S2AMD_EPISODE_SHAPE_ABS 1
+#define S2AMD_EPISODE_SHAPE_SQUARE 2
+#define S2AMD_EPISODE_RULE_DISABLED 1
+#define S2AMD_EPISODE_RULE_DIFFERENCE 2
+#define S2AMD_EPISODE_RULE_OUTSIDE 4
+#define S2AMD_EPISODE_STATUS_EVALUATED 0
+#define S2AMD_EPISODE_STATUS_DISABLED 1
+#define S2AMD_EPISODE_STATUS_SKIPPED 2
+#define S2AMD_EPISODE_STATUS_SOURCE_OFF 3
+#define S2AMD_EPISODE_TERMINATED 1
+#define S2AMD_EPISODE_TRUNCATED 2
+#define S2AMD_EPISODE_TIME_LIMIT 4
+#define S2AMD_EPISODE_REPORT_STEP 1
+#define S2AMD_EPISODE_REPORT_STATES 2
+#define S2AMD_EPISODE_REPORT_RULE_STATES 4
+#define S2AMD_EPISODE_REPORT_EVENTS 8
+typedef struct s2amdEpisodeRule /* 64 bytes */
+{
+	int32_t kind;	  /* S2AMD_EPISODE_REWARD_VALUE .. _TRUNCATE */
+	int32_t agent;	  /* [0, agents) */
+	int32_t channelA; /* the observation channel read, or -1 for no source (x = +0) */
+	int32_t frameA;	  /* ... and its frame (0: this step) */
+	int32_t channelB, frameB; /* with S2AMD_EPISODE_RULE_DIFFERENCE: what is subtracted; 0 otherwise */
+	int32_t shape;	  /* S2AMD_EPISODE_SHAPE_* */
+	int32_t flags;	  /* S2AMD_EPISODE_RULE_DISABLED | _DIFFERENCE | _OUTSIDE */
+	float gain, bias, lower, upper;
+	int32_t reserved[4]; /* 0 */
+} s2amdEpisodeRule;
+typedef struct s2amdEpisodeState /* 32 bytes */
+{
+	int32_t flags; /* S2AMD_EPISODE_TERMINATED | _TRUNCATED | _TIME_LIMIT of this step */
+	int32_t rule;  /* the list index of the first fired rule, else -1 */
+	float reward, episodeReturn;
+	int32_t episodeLength, episodes;
+	float lastReturn;
+	int32_t lastLength;
+} s2amdEpisodeState;
+typedef struct s2amdEpisodeRuleState /* 32 bytes */
+{
+	int32_t rule, status;
+	float x, f, value;
+	int32_t fired;
+	int32_t pad[2];
+} s2amdEpisodeRuleState;
+typedef struct s2amdEpisodeEvent /* 16 bytes */
+{
+	int32_t agent, flags, episodeLength;
+	float episodeReturn;
+} s2amdEpisodeEvent;
+int s2amd_world_set_episodes(s2amdSolver* solver, const s2amdEpisodeRule* rules, int32_t ruleCount, int32_t agents, const int32_t* stepLimits); /* replaces everything; agents 0 clears; stepLimits: [agents], NULL or 0 = no limit */
+int s2amd_world_set_episode_report(s2amdSolver* solver, int32_t flags); /* S2AMD_EPISODE_REPORT_* */
+int s2amd_world_episode_rewards(s2amdSolver* solver, float* out, int32_t capacity, int32_t* count); /* host; one float per agent */
+int s2amd_world_episode_flags(s2amdSolver* solver, int32_t* out, int32_t capacity, int32_t* count); /* host; one word per agent */
+int s2amd_world_export_episode_step(s2amdSolver* solver, void* deviceRewards, void* deviceFlags, int32_t capacity); /* device to device, both arrays, waits */
+int s2amd_world_export_episode_step_async(s2amdSolver* solver, void* deviceRewards, void* deviceFlags, int32_t capacity, int32_t slot); /* enqueued, an event in slot 0..3: s2amd_export_wait(slot) */
+int s2amd_world_episode_states(s2amdSolver* solver, s2amdEpisodeState* out, int32_t capacity, int32_t* count);
+int s2amd_world_episode_rule_states(s2amdSolver* solver, s2amdEpisodeRuleState* out, int32_t capacity, int32_t* count); /* in list order */
+int s2amd_world_episode_events(s2amdSolver* solver, s2amdEpisodeEvent* out, int32_t capacity, int32_t* count); /* agents done this step, ascending */
+int s2amd_world_episode_counts(s2amdSolver* solver, int32_t counts[8]); /* rules per status [0..3]; agents done, terminated, truncated, at the time limit [4..7] */
 
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts

@@ -398,6 +398,16 @@ void observersRelease(s2amdSolver* s)
 	s->dObservers.release();
 }
 
+const float* observationRing(const s2amdSolver* s, int* channels, int* frames, int* head)
+{
+	*channels = s->observationChannels, *frames = s->observationFrames, *head = s->observationHead;
+	if (s->hObservers.empty() || s->observationReport.stepFlags == 0 || s->dObservers.p == nullptr)
+	{
+		return nullptr;
+	}
+	return (const float*)((const char*)s->dObservers.p + layoutOf(s).ring);
+}
+
 #pragma GCC visibility push(default)
 extern "C"
 {

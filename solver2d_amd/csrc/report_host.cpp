@@ -1,7 +1,7 @@
 // The host side that the reports of the resident world share (contact_report.hip, joint_report.hip, shape_report.hip, body_report.hip,
-// step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip, observers.hip): the table of the nine in step order with its walks, the block carver, the prepare and enqueue preambles, the
+// step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip, observers.hip, episodes.hip): the table of the ten in step order with its walks, the block carver, the prepare and enqueue preambles, the
 // setter skeleton, the one device-to-host copy, and the getter shapes; and the host lifecycle of the lists a caller sets (sensors, fields,
-// rays, grids, actuators, observers): the argument check, the two ways a new list goes in, the per-item getter, the copy out and the
+// rays, grids, actuators, observers, episode rules): the argument check, the two ways a new list goes in, the per-item getter, the copy out and the
 // status counts.  A report supplies its layout, its kernels, its prepare and enqueue bodies, and getters that name their list in terms
 // of these ("The report facility").
 #include "solver_internal.h"
@@ -27,6 +27,7 @@ const ReportFacility facilities[] = {
 	{&SolverRest::rayReport, rayReportPrepare, rayReportEnqueue},
 	{&SolverRest::gridReport, gridReportPrepare, gridReportEnqueue},
 	{&SolverRest::observationReport, observationPrepare, observationEnqueue},
+	{&SolverRest::episodeReport, episodePrepare, episodeEnqueue},
 };
 
 int badArgument()

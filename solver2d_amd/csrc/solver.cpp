@@ -285,6 +285,7 @@ void s2amd_destroy(s2amdSolver* s)
 	fieldsRelease(s);
 	actuatorsRelease(s);
 	observersRelease(s);
+	episodesRelease(s);
 	treesFree(s);
 	if (s->hostError)
 	{

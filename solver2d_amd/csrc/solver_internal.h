@@ -631,6 +631,15 @@ struct SolverRest
 	int observationHead = 0;			   // the row of the ring that holds frame 0; frame k is row (head + k) % frames
 	bool observationFresh = true;		   // re-based: the next reporting step writes its vector into every row
 	long observationPasses = 0;			   // passes since the list was set: pass k counts into set k & 1 and clears the other
+	// episodes (episodes.hip; s2amd_world_set_episodes, s2amd_world_set_episode_report: S2AMD_EPISODE_REPORT_*): the tenth of a step, behind
+	// the observers whose ring it reads.  As theirs, its ReportState carries the flags alone and the device block is the setter's
+	ReportState episodeReport;
+	std::vector<s2amdEpisodeRule> hEpisodeRules; // the persistent list as the caller set it, in list order: held across uploads
+	std::vector<int32_t> hEpisodeLimits;		 // one step limit per agent (0: none)
+	int episodeAgents = 0;						 // 0: no list
+	DevBuf dEpisodes;		   // {two sets of eight counts, the rules grouped by agent, first[agents + 1], limits, y, codes, the agent records, rewards, flags, rule states, events}
+	bool episodeFresh = true;  // re-based: the next reporting step takes every agent record as zero
+	long episodePasses = 0;	   // passes since the list was set: pass k counts into set k & 1 and clears the other
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -871,7 +880,7 @@ int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
 // The reports behind s2amd_world_step.  Each file keeps its layout, kernels, prepare and enqueue; report_host.cpp holds the table of
-// the nine in step order and what their host sides share.
+// the ten in step order and what their host sides share.
 //   <x>Prepare   the report's device block for the resident world and its "before" state from the arrays just uploaded
 //   <x>Enqueue   the step's passes on the step's stream, behind stage 4 of the attempt that stands (never part of the captured graph)
 int contactReportPrepare(s2amdSolver* s);
@@ -895,6 +904,12 @@ int gridReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int observationPrepare(s2amdSolver* s); // (observers.hip: re-bases the history; the block is the setter's)
 int observationEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 void observersRelease(s2amdSolver* s);
+// What the episode pass reads of the observers in front of it: the ring on the device, nullptr when the observation report did not run
+// this step or no list is set; channels, frames (those of the list whether or not it reported, 0 with no list) and the row of frame 0.
+const float* observationRing(const s2amdSolver* s, int* channels, int* frames, int* head);
+int episodePrepare(s2amdSolver* s); // (episodes.hip: re-bases the accounting; the block is the setter's)
+int episodeEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+void episodesRelease(s2amdSolver* s);
 // What the observation pass reads of the reports in front of it, on the device: nullptr means "not this step" (the source report's
 // stepFlags), and the count is that of the list whether or not it reported.
 const s2amdBodyContactSum* contactReportBodySums(const s2amdSolver* s); // contact_report.hip: bodyCapacity records

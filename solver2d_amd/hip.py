@@ -40,6 +40,9 @@ EXPORTS = [
     "s2amd_device_write",
     "s2amd_world_set_observers", "s2amd_world_set_observation_report", "s2amd_world_observations", "s2amd_world_export_observations",
     "s2amd_world_export_observations_async", "s2amd_world_observer_states", "s2amd_world_observer_counts",
+    "s2amd_world_set_episodes", "s2amd_world_set_episode_report", "s2amd_world_episode_rewards", "s2amd_world_episode_flags",
+    "s2amd_world_export_episode_step", "s2amd_world_export_episode_step_async", "s2amd_world_episode_states", "s2amd_world_episode_rule_states",
+    "s2amd_world_episode_events", "s2amd_world_episode_counts",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
     "s2amd_world_ray_events",
@@ -162,6 +165,16 @@ def load(fast=False):
     L.s2amd_world_export_observations_async.argtypes = [vp, vp, i32, i32]
     L.s2amd_world_observer_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_observer_counts.argtypes = [vp, vp]
+    L.s2amd_world_set_episodes.argtypes = [vp, vp, i32, i32, vp]
+    L.s2amd_world_set_episode_report.argtypes = [vp, i32]
+    L.s2amd_world_episode_rewards.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_episode_flags.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_export_episode_step.argtypes = [vp, vp, vp, i32]
+    L.s2amd_world_export_episode_step_async.argtypes = [vp, vp, vp, i32, i32]
+    L.s2amd_world_episode_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_episode_rule_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_episode_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_episode_counts.argtypes = [vp, vp]
     L.s2amd_world_set_sensors.argtypes = [vp, vp, i32]
     L.s2amd_world_set_sensor_report.argtypes = [vp, i32, i32]
     L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -658,6 +671,56 @@ class Solver:
         """int32[4]: observers per status {OBSERVED, DISABLED, SKIPPED, SOURCE_OFF} of the last world_step's pass."""
         counts = np.zeros(4, dtype=np.int32)
         self._ck(self._L.s2amd_world_observer_counts(self._h, wire.as_ptr(counts)))
+        return counts
+
+    # ---- episodes on the resident world (s2amd_world_set_episodes, ...): rewards, termination and the episode accounting on the device ----
+    def world_set_episodes(self, rules, agents, step_limits=None):
+        """Replaces the whole persistent list (wire.episode_rule_dtype) over `agents` agents, with one step limit per agent (None or 0:
+        no limit); agents = 0 clears it.  Every world_step with the episode report on gives one reward and one flags word per agent."""
+        rules = np.ascontiguousarray(rules)
+        assert rules.dtype == wire.episode_rule_dtype
+        limits = None if step_limits is None else np.ascontiguousarray(step_limits, dtype=np.int32)
+        assert limits is None or len(limits) == int(agents)
+        self._ck(self._L.s2amd_world_set_episodes(self._h, wire.as_ptr(rules) if len(rules) else None, len(rules), int(agents),
+                                                  wire.as_ptr(limits) if limits is not None and len(limits) else None))
+        self._world_episodes = (len(rules), int(agents))
+
+    def world_set_episode_report(self, flags):
+        """wire.EPISODE_REPORT_STEP | _STATES | _RULE_STATES | _EVENTS: what the next world_step reports (0: nothing, and no episode advances)."""
+        self._ck(self._L.s2amd_world_set_episode_report(self._h, int(flags)))
+
+    def world_episode_rewards(self):
+        """float32[agents]: the rewards of the last world_step."""
+        return self._world_list(self._L.s2amd_world_episode_rewards, np.float32, getattr(self, "_world_episodes", (0, 0))[1])
+
+    def world_episode_flags(self):
+        """int32[agents]: wire.EPISODE_TERMINATED | _TRUNCATED | _TIME_LIMIT of the last world_step."""
+        return self._world_list(self._L.s2amd_world_episode_flags, np.int32, getattr(self, "_world_episodes", (0, 0))[1])
+
+    def world_export_episode_step(self, rewards_ptr, flags_ptr, capacity):
+        """The two arrays above into device buffers (device_alloc, or a torch tensor's data_ptr()) of `capacity` entries each; waits."""
+        self._ck(self._L.s2amd_world_export_episode_step(self._h, ctypes.c_void_p(int(rewards_ptr)), ctypes.c_void_p(int(flags_ptr)), int(capacity)))
+
+    def world_export_episode_step_async(self, rewards_ptr, flags_ptr, capacity, slot=0):
+        """The same copies enqueued behind the steps on the solver's stream, with an event in `slot`; pair with export_wait(slot)."""
+        self._ck(self._L.s2amd_world_export_episode_step_async(self._h, ctypes.c_void_p(int(rewards_ptr)), ctypes.c_void_p(int(flags_ptr)), int(capacity), int(slot)))
+
+    def world_episode_states(self):
+        """wire.episode_state_dtype records, one per agent: this step's flags and reward, and the episode accounting."""
+        return self._world_list(self._L.s2amd_world_episode_states, wire.episode_state_dtype, getattr(self, "_world_episodes", (0, 0))[1])
+
+    def world_episode_rule_states(self):
+        """wire.episode_rule_state_dtype records, one per rule in list order, of the last world_step's pass."""
+        return self._world_list(self._L.s2amd_world_episode_rule_states, wire.episode_rule_state_dtype, getattr(self, "_world_episodes", (0, 0))[0])
+
+    def world_episode_events(self, expected=16):
+        """wire.episode_event_dtype records: the agents whose episode ended in the last world_step, ascending."""
+        return self._world_list(self._L.s2amd_world_episode_events, wire.episode_event_dtype, expected)
+
+    def world_episode_counts(self):
+        """int32[8]: rules per status {EVALUATED, DISABLED, SKIPPED, SOURCE_OFF}, then agents done, terminated, truncated, at the time limit."""
+        counts = np.zeros(8, dtype=np.int32)
+        self._ck(self._L.s2amd_world_episode_counts(self._h, wire.as_ptr(counts)))
         return counts
 
     # ---- force fields on the resident world (s2amd_world_apply_fields, s2amd_world_set_fields): writes addressed by region ----

@@ -472,3 +472,43 @@ def observer(kind, target, channel, frame=-1, gain=1.0, bias=0.0, lower=-np.inf,
 def observer_list(observers):
     """A list of the records above (or an array of them) as one contiguous wire.observer_dtype array."""
     return np.ascontiguousarray(np.array(list(observers), dtype=observer_dtype)) if len(observers) else np.zeros(0, dtype=observer_dtype)
+
+
+# episodes on the resident world (include/solver2d_amd.h: s2amd_world_set_episodes, s2amd_world_set_episode_report)
+MAX_EPISODE_AGENTS, MAX_EPISODE_RULES = 16384, 65536
+EPISODE_REWARD_VALUE, EPISODE_REWARD_TEST, EPISODE_TERMINATE, EPISODE_TRUNCATE = 1, 2, 3, 4
+EPISODE_SHAPE_LINEAR, EPISODE_SHAPE_ABS, EPISODE_SHAPE_SQUARE = 0, 1, 2
+EPISODE_RULE_DISABLED, EPISODE_RULE_DIFFERENCE, EPISODE_RULE_OUTSIDE = 1, 2, 4
+EPISODE_STATUS_EVALUATED, EPISODE_STATUS_DISABLED, EPISODE_STATUS_SKIPPED, EPISODE_STATUS_SOURCE_OFF = 0, 1, 2, 3
+EPISODE_TERMINATED, EPISODE_TRUNCATED, EPISODE_TIME_LIMIT = 1, 2, 4
+EPISODE_REPORT_STEP, EPISODE_REPORT_STATES, EPISODE_REPORT_RULE_STATES, EPISODE_REPORT_EVENTS = 1, 2, 4, 8
+EPISODE_REPORT_ALL = 15
+# s2amdEpisodeRule, s2amdEpisodeState, s2amdEpisodeRuleState, s2amdEpisodeEvent
+episode_rule_dtype = np.dtype([("kind", np.int32), ("agent", np.int32), ("channelA", np.int32), ("frameA", np.int32), ("channelB", np.int32),
+                               ("frameB", np.int32), ("shape", np.int32), ("flags", np.int32), ("gain", np.float32), ("bias", np.float32),
+                               ("lower", np.float32), ("upper", np.float32), ("reserved", np.int32, 4)])
+episode_state_dtype = np.dtype([("flags", np.int32), ("rule", np.int32), ("reward", np.float32), ("episodeReturn", np.float32),
+                                ("episodeLength", np.int32), ("episodes", np.int32), ("lastReturn", np.float32), ("lastLength", np.int32)])
+episode_rule_state_dtype = np.dtype([("rule", np.int32), ("status", np.int32), ("x", np.float32), ("f", np.float32), ("value", np.float32),
+                                     ("fired", np.int32), ("pad", np.int32, 2)])
+episode_event_dtype = np.dtype([("agent", np.int32), ("flags", np.int32), ("episodeLength", np.int32), ("episodeReturn", np.float32)])
+EPISODE_RULE_SIZE, EPISODE_STATE_SIZE, EPISODE_RULE_STATE_SIZE, EPISODE_EVENT_SIZE = (episode_rule_dtype.itemsize, episode_state_dtype.itemsize,
+                                                                                      episode_rule_state_dtype.itemsize, episode_event_dtype.itemsize)
+assert (EPISODE_RULE_SIZE, EPISODE_STATE_SIZE, EPISODE_RULE_STATE_SIZE, EPISODE_EVENT_SIZE) == (64, 32, 32, 16)
+
+
+def episode_rule(kind, agent, channel=-1, frame=0, minus=None, shape=0, gain=1.0, bias=0.0, lower=-np.inf, upper=np.inf, flags=0):
+    """One wire.episode_rule_dtype record of agent `agent`: x = obs[frame][channel] (channel -1: no source, x = +0); with
+    minus=(channelB, frameB) the DIFFERENCE flag is set and x = obs[frame][channel] - obs[frameB][channelB]."""
+    r = np.zeros(1, dtype=episode_rule_dtype)[0]
+    r["kind"], r["agent"], r["channelA"], r["frameA"], r["shape"], r["flags"] = kind, agent, channel, frame, shape, flags
+    if minus is not None:
+        r["channelB"], r["frameB"] = minus
+        r["flags"] |= EPISODE_RULE_DIFFERENCE
+    r["gain"], r["bias"], r["lower"], r["upper"] = gain, bias, lower, upper
+    return r
+
+
+def episode_rule_list(rules):
+    """A list of the records above (or an array of them) as one contiguous wire.episode_rule_dtype array."""
+    return np.ascontiguousarray(np.array(list(rules), dtype=episode_rule_dtype)) if len(rules) else np.zeros(0, dtype=episode_rule_dtype)
