@@ -12,7 +12,7 @@ THRESHOLDS are at rest after step 3 and awake after step 4; bodies without gravi
 import numpy as np
 
 from solver2d_amd import synthetic, wire
-from tests import oraclebind
+from tests import body_report_ref, oraclebind
 
 SLOTS = 640
 DT = np.float32(1.0 / 60.0)
@@ -126,3 +126,51 @@ def expected_islands():
     groups = [{2, 3, 4}, {5, 6}, {8, 10}, {11, 18}, {13, 14}, {15, 16}, {61, 62, 63, 64, 65, 66}, {253, 254, 255, 256, 257, 258},
               {70, 300, 72, 560, 74, 302, 76, 562}, {HUB} | set(SPOKES)]
     return groups
+
+
+def thresholds_of(linear, dt):
+    return (np.float32(linear), np.float32(np.float32(linear) * np.float32(3.4906585)), np.float32(3) * np.float32(dt))
+
+
+def assert_records_equal(got, want, what):
+    assert len(got) == len(want), "%s: %d records, reference %d" % (what, len(got), len(want))
+    if got.tobytes() != want.tobytes():
+        bad = [n for n in got.dtype.names if got[n].tobytes() != want[n].tobytes()]
+        rows = np.flatnonzero([got[i].tobytes() != want[i].tobytes() for i in range(len(got))])
+        raise AssertionError("%s: records differ in %s, first rows %s: %s / %s" % (what, bad, rows[:3].tolist(), got[rows[:2]], want[rows[:2]]))
+
+
+def assert_body_report_equals_reference(s, state, world, thresholds, dt, what, flags=wire.BODY_REPORT_ALL, totals=None):
+    """The four getters against the reference statement on `world` (the oracle chain after the step); `state` moves on by one step."""
+    step = body_report_ref.advance(state, world, thresholds, dt)
+    island = island_states = None
+    if flags & wire.BODY_REPORT_ISLANDS:
+        island, island_states = body_report_ref.islands(world, step)
+        assert_records_equal(s.world_islands(expected=max(len(island_states), 1)), island_states, what + ": islands")
+    if flags & wire.BODY_REPORT_STATES:
+        want = body_report_ref.states(world, step, bool(flags & wire.BODY_REPORT_MOVED_ONLY), island, island_states)
+        assert_records_equal(s.world_body_states(expected=max(len(want), 1)), want, what + ": states")
+    if flags & wire.BODY_REPORT_REST:
+        want_rested, want_woke = body_report_ref.events(step)
+        rested, woke = s.world_body_rest_events()
+        assert rested.tolist() == want_rested.tolist(), what + ": rested"
+        assert woke.tolist() == want_woke.tolist(), what + ": woke"
+    want_summary = body_report_ref.summary(world, step, island_states)
+    summary = s.world_body_summary()
+    assert summary.tobytes() == want_summary.tobytes(), "%s: summary %s, reference %s" % (what, summary, want_summary)
+    if totals is not None:
+        # (counted on the reference chain of the run)
+        rested, woke = body_report_ref.events(step)
+        totals["rested"] += len(rested)
+        totals["woke"] += len(woke)
+        totals["rested_high"] += int((rested >= 256).sum())
+        totals["woke_high"] += int((woke >= 256).sum())
+        totals["records"] += int(step["reported"].sum())
+        totals["unmoved"] += int((step["reported"] & ~step["moved"]).sum())
+        totals["last_moved"] = step["moved"]
+        if island_states is not None:
+            totals["islands"].append(len(island_states))
+            totals["largest"] = max(totals["largest"], int(island_states["bodyCount"].max()) if len(island_states) else 0)
+            low = set(island[:256][island[:256] >= 0].tolist())
+            totals["spanning"] = max(totals["spanning"], len(low & set(island[256:][island[256:] >= 0].tolist())))
+    return step

@@ -209,8 +209,23 @@ def record(name, world):
             "distance": np.array([into[k][0] for k in keys], dtype=np.float32), "pointB": np.array([into[k][1:] for k in keys], dtype=np.float32).reshape(-1, 2)}
 
 
+def assert_zoo_condition(world, states, edits):
+    """What keeps the shapes_zoo40 cases from passing vacuously: every field has at least 12 terms and at least 3 bodies with two terms,
+    and at least 5 bodies are reached by two or more fields"""
+    at, reach = 0, {}
+    for i, n in enumerate(states["terms"]):
+        targets, counts = np.unique(edits["target"][at:at + n], return_counts=True)
+        at += n
+        assert n >= 12 and (counts >= 2).sum() >= 3, (i, n, counts)
+        for b in targets:
+            reach.setdefault(int(b), set()).add(i)
+    assert sum(len(v) >= 2 for v in reach.values()) >= 5
+    static_six = [b for b in np.flatnonzero(world["bodies"]["type"] == wire.BODY_STATIC) if (world["shapes"]["body"] == b).sum() >= 6]
+    assert static_six and not np.isin(edits["target"], static_six).any()
+
+
 if __name__ == "__main__":
-    from tests.test_gpu_step_metrics import golden
+    from tests.world_chain import golden
     os.makedirs(GOLDEN, exist_ok=True)
     for world_name in FIXTURES:
         data = record(world_name, golden(world_name)[1])

@@ -4,7 +4,7 @@ ill-conditioned block K, limits at both ends, motors, mouse joints, kinematic an
 rotated static bodies whose rot is NOT a fixed point of the normalisation, free slots everywhere."""
 import numpy as np
 
-from solver2d_amd import wire
+from solver2d_amd import synthetic, wire
 
 
 def random_world(seed, n_bodies=40, n_contacts=80, n_joints=12):
@@ -112,3 +112,35 @@ def random_world(seed, n_bodies=40, n_contacts=80, n_joints=12):
             jn[i]["lowerImpulse"] = rng.choice([0.0, 0.1])
             jn[i]["upperImpulse"] = rng.choice([0.0, 0.1])
     return b, c, jn
+
+
+def perturbed_pyramid(seed, base=36):
+    """The pyramid's contact graph (long BFS diameter, degree <= 6: strips and the persistent kernel apply) with
+    randomised numbers: velocities, impulses, anchors, separations, one-point contacts, a few inactive contacts,
+    kinematic and static bodies in the pile."""
+    rng = np.random.default_rng(1000 + seed)
+    bodies, contacts, joints = tuple(x.copy() for x in synthetic.pyramid(base))
+    nb, nc = len(bodies), len(contacts)
+    bodies["linearVelocity"] += rng.normal(0.0, 0.5, (nb, 2)).astype(np.float32)
+    bodies["angularVelocity"] += rng.normal(0.0, 0.5, nb).astype(np.float32)
+    ang = rng.normal(0.0, 0.05, nb).astype(np.float32)
+    bodies["rot"][:, 0], bodies["rot"][:, 1] = np.sin(ang), np.cos(ang)
+    bodies["linearDamping"] = rng.uniform(0.0, 0.2, nb).astype(np.float32)
+    for i in rng.choice(np.arange(1, nb), size=6, replace=False):
+        bodies["type"][i] = wire.BODY_KINEMATIC if i % 2 else wire.BODY_STATIC
+        bodies["mass"][i] = bodies["invMass"][i] = bodies["I"][i] = bodies["invI"][i] = 0.0
+        if bodies["type"][i] == wire.BODY_STATIC:
+            bodies["linearVelocity"][i] = 0.0
+            bodies["angularVelocity"][i] = 0.0
+    pts = contacts["points"]
+    pts["normalImpulse"] = rng.uniform(0.0, 2.0, pts["normalImpulse"].shape).astype(np.float32)
+    pts["tangentImpulse"] = rng.normal(0.0, 0.3, pts["tangentImpulse"].shape).astype(np.float32)
+    pts["separation"] += rng.normal(0.0, 0.01, pts["separation"].shape).astype(np.float32)
+    pts["localAnchorA"] += rng.normal(0.0, 0.02, pts["localAnchorA"].shape).astype(np.float32)
+    pts["localAnchorB"] += rng.normal(0.0, 0.02, pts["localAnchorB"].shape).astype(np.float32)
+    contacts["friction"] = rng.uniform(0.0, 1.0, nc).astype(np.float32)
+    if seed % 2:
+        one = rng.random(nc) < 0.3
+        contacts["pointCount"][one & (contacts["pointCount"] == 2)] = 1
+        contacts["pointCount"][rng.random(nc) < 0.03] = 0
+    return bodies, contacts, joints

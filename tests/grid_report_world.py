@@ -17,7 +17,8 @@ import os
 import numpy as np
 
 from solver2d_amd import wire
-from tests import sensor_report_world as sw
+from tests import grid_report_ref, sensor_report_world as sw
+from tests.resident import downloaded_world
 
 f32 = np.float32
 ALL = 0xFFFFFFFF
@@ -262,3 +263,94 @@ if __name__ == "__main__":
         print("%s: %d grids, robust share %.4f" % (name, len(built["grids"]), condition(built)[0]))
         np.savez_compressed(fixture_path(name), **built)
         print("  %d bytes" % os.path.getsize(fixture_path(name)))
+
+
+def getters(s):
+    return s.world_grid_categories(), s.world_grid_shapes(), s.world_grid_occupancy(), s.world_grid_states()
+
+
+def plain(world, grids):
+    """Which grids the two exclusions cannot change: fixed in the world or on a body without a live shape, and no SKIP_STATIC"""
+    shapes = world["shapes"]
+    live_bodies = set(shapes["body"][shapes["type"] != wire.SHAPE_FREE].tolist())
+    return np.array([(int(q["body"]) < 0 or int(q["body"]) not in live_bodies) and not (int(q["flags"]) & wire.GRID_SENSOR_SKIP_STATIC) for q in grids], dtype=bool)
+
+
+def assert_structure(world, grids, got, what):
+    """What every report satisfies whatever the geometry: sizes, the fixed fields, the states' figures from the arrays"""
+    cats, low, occ, states = got
+    first, total = grid_report_ref.first_cells(grids)
+    assert len(cats) == len(low) == len(occ) == total and len(states) == len(grids), what
+    assert states["grid"].tolist() == list(range(len(grids))) and states["body"].tobytes() == grids["body"].tobytes(), what
+    assert states["firstCell"].tolist() == first.tolist() and states["cells"].tolist() == (grids["width"] * grids["height"]).tolist(), what
+    assert occ.tobytes() == (low >= 0).astype(np.float32).tobytes() and ((cats != 0) == (low >= 0)).all(), what
+    shapes = world["shapes"]
+    hit = low >= 0
+    assert (shapes["type"][low[hit]] != wire.SHAPE_FREE).all() and ((cats[hit] & shapes["categoryBits"][low[hit]]) != 0).all(), what
+    for g, q in enumerate(grids):
+        mine = low[first[g]: first[g] + int(q["width"]) * int(q["height"])]
+        st = states[g]
+        assert st["occupied"] == (mine >= 0).sum() and st["lowestShape"] == (mine[mine >= 0].min() if (mine >= 0).any() else -1), (what, g)
+        if not st["active"]:
+            assert (mine == -1).all() and st["candidates"] == 0 and st["position"].tobytes() + st["rot"].tobytes() + st["box"].tobytes() == bytes(32), (what, g)
+        else:
+            own = int(q["body"])
+            assert own < 0 or (shapes["body"][mine[mine >= 0]] != own).all(), (what, g)  # a mounted grid never sees its own body
+            if int(q["flags"]) & wire.GRID_SENSOR_SKIP_STATIC:
+                assert (world["bodies"]["type"][shapes["body"][mine[mine >= 0]]] != wire.BODY_STATIC).all(), (what, g)
+
+
+def assert_probe(s, world, grids, got, what):
+    """The device's own s2amd_world_point_probe of the statement's cell points, folded: the arrays of every plain grid"""
+    cats, low, occ, states = got
+    first, total = grid_report_ref.first_cells(grids)
+    active = np.array([grid_report_ref.cell_points(world, q)[0] for q in grids], dtype=bool)
+    assert states["active"].tolist() == active.astype(int).tolist(), what
+    points, index = grid_report_ref.probes_of(world, grids)
+    if len(points) == 0:
+        return
+    offsets, flat = s.world_point_probe(points, expected=4 * len(points) + 64)
+    pc, pl, po = grid_report_ref.fold_probe(world, total, index, offsets, flat)
+    keep = np.zeros(total, dtype=bool)
+    ok = plain(world, grids)
+    for g, q in enumerate(grids):
+        if ok[g] or not active[g]:
+            keep[first[g]: first[g] + int(q["width"]) * int(q["height"])] = True
+    assert cats[keep].tobytes() == pc[keep].tobytes(), what
+    assert low[keep].tobytes() == pl[keep].tobytes(), what
+    assert occ[keep].tobytes() == po[keep].tobytes(), what
+    # ... and an exclusion only ever removes hits
+    assert ((cats & ~pc) == 0).all() and ((low >= pl) | (low < 0)).all(), what
+
+
+def assert_statement(world, grids, got, what, period=None):
+    """The statement's bytes where the reference is built; a list that repeats its first `period` grids is compared on one period"""
+    if not grid_report_ref.available():
+        return
+    cats, low, occ, states = got
+    n = len(grids) if period is None or period >= len(grids) else period
+    if n < len(grids):
+        assert all(grids[i].tobytes() == grids[i % n].tobytes() for i in range(len(grids)))
+    wc, wl, wo, ws = grid_report_ref.report(world, grids[:n])
+    cells = len(wc)
+    for k in range(0, len(grids), n):
+        m = min(n, len(grids) - k)
+        c = int(ws["firstCell"][m - 1] + ws["cells"][m - 1])
+        at = (k // n) * cells
+        assert cats[at: at + c].tobytes() == wc[:c].tobytes() and low[at: at + c].tobytes() == wl[:c].tobytes() and occ[at: at + c].tobytes() == wo[:c].tobytes(), (what, k)
+        want = ws[:m].copy()
+        want["grid"] += k
+        want["firstCell"] += at
+        if states[k: k + m].tobytes() != want.tobytes():
+            bad = [f for f in want.dtype.names if states[k: k + m][f].tobytes() != want[f].tobytes()]
+            raise AssertionError("%s: states of period %d differ in %s: %s / %s" % (what, k, bad, states[k: k + m][:2], want[:2]))
+
+
+def assert_report(s, world, grids, what, period=None, statement=True):
+    resident = downloaded_world(s, world)
+    got = getters(s)
+    assert_structure(resident, grids, got, what)
+    assert_probe(s, resident, grids, got, what)
+    if statement:
+        assert_statement(resident, grids, got, what, period)
+    return got

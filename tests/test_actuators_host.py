@@ -2,19 +2,13 @@
 (tests/actuator_ref.py) on hand-made cases -- the clamp's edges, values that are not finite, every status --, the servo's sign pinned
 against the solver itself on a motorised pendulum stepped by the oracle chain, the compiler's resource report of the new kernels, and the
 host side under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
-from solver2d_amd import hip, synthetic, wire
-from tests import actuator_ref as ref, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import synthetic, wire
+from tests import actuator_ref as ref, hostcheck_util, world_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("s2amd_world_set_actuators", "s2amd_world_set_actions", "s2amd_world_import_actions", "s2amd_world_actuator_states",
          "s2amd_world_actuator_counts", "s2amd_device_write")
 F = np.float32
@@ -23,29 +17,11 @@ INF = F(np.inf)
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
     records = {"s2amdActuator": wire.actuator_dtype, "s2amdActuatorState": wire.actuator_state_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in records.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, records)
     assert (wire.ACTUATOR_SIZE, wire.ACTUATOR_STATE_SIZE) == (64, 48)
 
 
 def test_header_defines_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
     defines = {"S2AMD_MAX_ACTUATORS": wire.MAX_ACTUATORS, "S2AMD_MAX_ACTION_CHANNELS": wire.MAX_ACTION_CHANNELS,
                "S2AMD_ACTUATOR_BODY_FORCE": wire.ACTUATOR_BODY_FORCE, "S2AMD_ACTUATOR_BODY_THRUST": wire.ACTUATOR_BODY_THRUST,
                "S2AMD_ACTUATOR_BODY_LINEAR_VELOCITY": wire.ACTUATOR_BODY_LINEAR_VELOCITY,
@@ -54,19 +30,11 @@ def test_header_defines_and_bindings():
                "S2AMD_ACTUATOR_MOUSE_TARGET": wire.ACTUATOR_MOUSE_TARGET, "S2AMD_ACTUATOR_DISABLED": wire.ACTUATOR_DISABLED,
                "S2AMD_ACTUATOR_STATUS_APPLIED": ref.APPLIED, "S2AMD_ACTUATOR_STATUS_DISABLED": ref.DISABLED,
                "S2AMD_ACTUATOR_STATUS_SKIPPED": ref.SKIPPED, "S2AMD_ACTUATOR_STATUS_NONFINITE": ref.NONFINITE, "S2AMD_API_VERSION": 5}
-    for name, value in defines.items():
-        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), header), name
+    header = hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_ACTUATORS, wire.MAX_ACTION_CHANNELS, wire.API_VERSION) == (16384, 65536, 5)
     assert wire.ACTUATOR_WIDTH == {1: 2, 2: 1, 3: 2, 4: 1, 5: 1, 6: 1, 7: 2}
-    for method in ("world_set_actuators", "world_set_actions", "world_import_actions", "world_actuator_states", "world_actuator_counts", "device_write"):
-        assert callable(getattr(hip.Solver, method))
     # the notes under the edits and the fields point here for values in device memory
     assert len(re.findall(r"lists in device memory \([^)]*s2amd_world_set_actuators", header)) == 2
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 # ---- the statement on hand-made cases ----
@@ -220,38 +188,15 @@ def test_servo_sign_against_the_solver():
 def test_kernels_use_no_scratch():
     """hipcc's own report for actuators.hip (make resources-actuators), through tools/kernel_resources.py: every kernel of the file is
     there, none has a private frame or spills."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-actuators"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_actuators.txt"))
-    for kernel in ("actuatorTermsKernelILb1E", "actuatorTermsKernelILb0E", "actuatorWalkKernel", "reportBodyRangesKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r
+    kernels = dict.fromkeys(("actuatorTermsKernelILb1E", "actuatorTermsKernelILb0E", "actuatorWalkKernel", "reportBodyRangesKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-actuators", "resources_actuators.txt", kernels, floor=4)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_actuator_host_code_under_asan_and_ubsan(tmp_path):
     """Every validation rule with and without a world -> the list held across uploads with other capacities -> the grouping's verdict
     (a target twice or not) -> both writers on whole and partial ranges, twice in a row, past the end -> the getters with too-small,
     exact and ample heap buffers of exactly the size passed, before a step, after it, after the list was replaced, refused and cleared
     -> destroy, for 0, 1, 65, 257, 1,000 and 16,384 actuators, on the sanitizer build of tests/test_hostcheck.py (kernels never run
     there)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "actuators_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "actuators_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "ACTUATORS MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "actuators_main.cpp", "ACTUATORS MAIN OK", timeout=600)

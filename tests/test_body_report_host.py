@@ -4,37 +4,19 @@ the values written out here, the synthetic world of the GPU test has on the CPU 
 side of the report runs clean under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing
 preloaded)."""
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from solver2d_amd import hip, islands, wire
-from tests import body_report_ref as ref, body_report_world, common, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from tests import body_report_ref as ref, body_report_world, common, hostcheck_util, world_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 NAN = float("nan")
 
 
 def test_body_report_struct_sizes_and_offsets_match_header(tmp_path):
     fields = {"s2amdBodyState": wire.body_state_dtype, "s2amdIslandState": wire.island_state_dtype, "s2amdBodySummary": wire.body_summary_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in fields.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, fields)
     assert (wire.body_state_dtype.itemsize, wire.island_state_dtype.itemsize, wire.body_summary_dtype.itemsize) == (64, 32, 64)
     assert wire.body_state_dtype.fields["origin"][1] == 16 and wire.body_state_dtype.fields["restTime"][1] == 56
     assert wire.island_state_dtype.fields["maxSpeedSquared"][1] == 24 and wire.body_summary_dtype.fields["pad"][1] == 44
@@ -43,15 +25,11 @@ def test_body_report_struct_sizes_and_offsets_match_header(tmp_path):
 def test_body_report_exports_and_flags():
     names = ("s2amd_world_set_body_report", "s2amd_world_set_rest_thresholds", "s2amd_world_body_states", "s2amd_world_body_rest_events",
              "s2amd_world_islands", "s2amd_world_body_summary")
-    for name in names:
-        assert name in hip.EXPORTS
     assert (wire.BODY_REPORT_STATES, wire.BODY_REPORT_REST, wire.BODY_REPORT_ISLANDS, wire.BODY_REPORT_MOVED_ONLY, wire.BODY_REPORT_ALL) == (1, 2, 4, 8, 15)
     # the other three flag spaces and the API version are untouched
     assert wire.REPORT_ALL == 7 and wire.JOINT_REPORT_ALL == 7 and wire.SHAPE_REPORT_ALL == 7 and wire.API_VERSION == 5
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for define in ("#define S2AMD_BODY_REPORT_STATES 1", "#define S2AMD_BODY_REPORT_REST 2", "#define S2AMD_BODY_REPORT_ISLANDS 4",
-                   "#define S2AMD_BODY_REPORT_MOVED_ONLY 8", "#define S2AMD_API_VERSION 5"):
-        assert define in header
+    hostcheck_util.assert_header_and_bindings(names, {"S2AMD_BODY_REPORT_STATES": 1, "S2AMD_BODY_REPORT_REST": 2, "S2AMD_BODY_REPORT_ISLANDS": 4,
+                                                      "S2AMD_BODY_REPORT_MOVED_ONLY": 8, "S2AMD_API_VERSION": 5})
     if os.path.exists(hip.LIB_PATH):
         # (the built library: every function is there to be called)
         lib = hip.load()
@@ -225,23 +203,9 @@ def test_synthetic_world_has_the_events_the_gpu_test_needs():
     assert np.isfinite(world["bodies"]["position"]).all()
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_body_report_host_code_under_asan_and_ubsan(tmp_path):
     """tests/hostcheck/body_report_main.cpp, a program of its own: upload -> every flag combination -> thresholds set and changed ->
     every getter with too-small, exact and ample buffers -> uploads with other capacities -> destroy, on the sanitizer build of
     tests/test_hostcheck.py (kernels never run there: what is checked is that the host code touches only memory it owns)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "body_report_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "body_report_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "BODY REPORT MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "body_report_main.cpp", "BODY REPORT MAIN OK", timeout=600)

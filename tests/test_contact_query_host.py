@@ -3,14 +3,12 @@ as the statement (tests/contact_query_ref.py) calls them pinned to three closed 
 with the conditions they must meet, and the compiler's resource report of the new kernels."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import contact_query_ref as ref, contact_query_world as cw, proximity_world as pw, scene_query_world as sq
+from tests import contact_query_ref as ref, contact_query_world as cw, hostcheck_util, proximity_world as pw, scene_query_world as sq
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
@@ -242,11 +240,7 @@ def test_the_new_kernels_are_in_the_resource_report():
     """hipcc's own report for contact_query.hip (make resources-contact-query), through tools/kernel_resources.py: every kernel of the
     file is there; the staging and list kernels have no private frame, the manifold kernels at most narrowphase.hip's 144 bytes a lane,
     and 64 KiB of LDS a workgroup leave two workgroups a CU."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-contact-query"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_contact_query.txt"))
+    rows = hostcheck_util.kernel_rows("resources-contact-query", "resources_contact_query.txt")
     for kernel, frame in (("contactCandidatesKernelILb0E", 144), ("contactCandidatesKernelILb1E", 144), ("contactDeepestKernel", 144),
                           ("contactRecordsKernel", 144), ("contactStageKernel", 0), ("listTilePrefixKernel", 0), ("listOffsetsKernel", 0),
                           ("listWriteKernel", 0)):

@@ -1,30 +1,19 @@
 """The contact report without a GPU: the two new structs of include/solver2d_amd.h have the sizes of their wire dtypes, and the
 reference statement the GPU tests compare against (tests/contact_report_ref.py) gives, on a world small enough to work out by hand,
 the values written out here."""
-import os
-import subprocess
-
 import numpy as np
 
-from solver2d_amd import hip, wire
-from tests import contact_report_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from solver2d_amd import wire
+from tests import contact_report_ref as ref, hostcheck_util
 
 
 def test_report_struct_sizes_match_header(tmp_path):
-    src = tmp_path / "sz.c"
-    src.write_text('#include "solver2d_amd.h"\n#include <stdio.h>\nint main(){printf("%zu %zu\\n",'
-                   'sizeof(s2amdTouchingContact),sizeof(s2amdBodyContactSum));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert sizes == [wire.touching_contact_dtype.itemsize, wire.body_contact_sum_dtype.itemsize] == [64, 16]
+    hostcheck_util.assert_struct_layout(tmp_path, {"s2amdTouchingContact": wire.touching_contact_dtype, "s2amdBodyContactSum": wire.body_contact_sum_dtype})
+    assert [wire.touching_contact_dtype.itemsize, wire.body_contact_sum_dtype.itemsize] == [64, 16]
 
 
 def test_report_exports_and_flags():
-    for name in ("s2amd_world_set_report", "s2amd_world_touch_events", "s2amd_world_touching", "s2amd_world_body_sums"):
-        assert name in hip.EXPORTS
+    hostcheck_util.assert_header_and_bindings(("s2amd_world_set_report", "s2amd_world_touch_events", "s2amd_world_touching", "s2amd_world_body_sums"))
     assert (wire.REPORT_TOUCH, wire.REPORT_CONTACTS, wire.REPORT_BODY_SUMS, wire.REPORT_ALL) == (1, 2, 4, 7)
 
 

@@ -3,19 +3,13 @@
 a NaN, the order of the float sum, every status in the stated priority order, the time limit beside a fired rule, the restart, the
 re-base --, the setter's validation cases as data, the compiler's resource report of the new kernels, and the host side under
 ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
-from solver2d_amd import hip, wire
-from tests import episode_ref as ref
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import episode_ref as ref, hostcheck_util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("s2amd_world_set_episodes", "s2amd_world_set_episode_report", "s2amd_world_episode_rewards", "s2amd_world_episode_flags",
          "s2amd_world_export_episode_step", "s2amd_world_export_episode_step_async", "s2amd_world_episode_states",
          "s2amd_world_episode_rule_states", "s2amd_world_episode_events", "s2amd_world_episode_counts")
@@ -31,31 +25,12 @@ def bits(x):
 
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
-    records = {"s2amdEpisodeRule": wire.episode_rule_dtype, "s2amdEpisodeState": wire.episode_state_dtype,
-               "s2amdEpisodeRuleState": wire.episode_rule_state_dtype, "s2amdEpisodeEvent": wire.episode_event_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in records.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, {"s2amdEpisodeRule": wire.episode_rule_dtype, "s2amdEpisodeState": wire.episode_state_dtype,
+                                                   "s2amdEpisodeRuleState": wire.episode_rule_state_dtype, "s2amdEpisodeEvent": wire.episode_event_dtype})
     assert (wire.EPISODE_RULE_SIZE, wire.EPISODE_STATE_SIZE, wire.EPISODE_RULE_STATE_SIZE, wire.EPISODE_EVENT_SIZE) == (64, 32, 32, 16)
 
 
 def test_header_defines_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
     defines = {"S2AMD_MAX_EPISODE_AGENTS": wire.MAX_EPISODE_AGENTS, "S2AMD_MAX_EPISODE_RULES": wire.MAX_EPISODE_RULES,
                "S2AMD_EPISODE_REWARD_VALUE": ref.REWARD_VALUE, "S2AMD_EPISODE_REWARD_TEST": ref.REWARD_TEST, "S2AMD_EPISODE_TERMINATE": ref.TERMINATE,
                "S2AMD_EPISODE_TRUNCATE": ref.TRUNCATE, "S2AMD_EPISODE_SHAPE_LINEAR": ref.LINEAR, "S2AMD_EPISODE_SHAPE_ABS": ref.ABS,
@@ -66,20 +41,12 @@ def test_header_defines_and_bindings():
                "S2AMD_EPISODE_TIME_LIMIT": ref.TIME_LIMIT, "S2AMD_EPISODE_REPORT_STEP": wire.EPISODE_REPORT_STEP,
                "S2AMD_EPISODE_REPORT_STATES": wire.EPISODE_REPORT_STATES, "S2AMD_EPISODE_REPORT_RULE_STATES": wire.EPISODE_REPORT_RULE_STATES,
                "S2AMD_EPISODE_REPORT_EVENTS": wire.EPISODE_REPORT_EVENTS, "S2AMD_API_VERSION": 5}
-    for name, value in defines.items():
-        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), header), name
+    header = hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_EPISODE_AGENTS, wire.MAX_EPISODE_RULES, wire.API_VERSION) == (16384, 65536, 5)
     assert (wire.EPISODE_RULE_DISABLED, wire.EPISODE_RULE_DIFFERENCE, wire.EPISODE_RULE_OUTSIDE) == (1, 2, 4)
     assert (wire.EPISODE_REPORT_STEP, wire.EPISODE_REPORT_STATES, wire.EPISODE_REPORT_RULE_STATES, wire.EPISODE_REPORT_EVENTS, wire.EPISODE_REPORT_ALL) == (1, 2, 4, 8, 15)
-    for call in CALLS:
-        assert callable(getattr(hip.Solver, call[len("s2amd_"):])), call
     # the observers' "Not offered" points here and names what remains
     assert re.search(r"Rewards and termination are the episode report's", header) and "resetting the bodies of a finished agent" in header
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 # ---- the statement on hand-made cases ----
@@ -250,38 +217,14 @@ def test_validation_rules_of_the_statement():
 def test_kernels_use_no_scratch():
     """hipcc's own report for episodes.hip (make resources-episodes), through tools/kernel_resources.py: each kernel of the file is there
     once, has no private frame, spills nothing and keeps four waves per SIMD or more."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-episodes"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_episodes.txt"))
-    for kernel in ("episodeRulesKernel", "episodeAgentsKernel", "episodeEventsKernel", "reportBodyRangesKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r
-    assert len([r for r in rows if "Kernel" in r["mangled"]]) == 4
+    kernels = dict.fromkeys(("episodeRulesKernel", "episodeAgentsKernel", "episodeEventsKernel", "reportBodyRangesKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-episodes", "resources_episodes.txt", kernels, floor=4, total=4)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_episode_host_code_under_asan_and_ubsan(tmp_path):
     """Every validation refusal, with and without a world and a list, each leaving the old list, its accounting and its answers standing
     -> the list held across uploads -> the re-bases by upload, replacement and flags -> the getters' state machine per flag -> every
     getter and both exports with too-small and exact heap buffers -> destroy, for 0, 1, 65, 257 and 16,384 agents and 0, 1 and 65,536
     rules, on the sanitizer build of tests/test_hostcheck.py (kernels never run there: the program plays the kernels' writes)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "episodes_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "episodes_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "EPISODES MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "episodes_main.cpp", "EPISODES MAIN OK", timeout=600)

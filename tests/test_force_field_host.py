@@ -3,63 +3,30 @@
 term list on the fixtures tests/golden/force_fields/*.npz (the reference's recorded distance outputs, so this runs where the compiled
 reference is absent; where it is built the fixtures are made again and compared), the compiler's resource report of the new kernels,
 and the host side under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
-import os
-import re
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from solver2d_amd import hip, wire
-from tests import force_field_ref as ref, world_chain, world_edit_ref
-from tests.test_gpu_step_metrics import golden
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import force_field_ref as ref, hostcheck_util, world_edit_ref
+from tests.world_chain import golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
 CALLS = ("s2amd_world_apply_fields", "s2amd_world_set_fields", "s2amd_world_field_states")
 F = np.float32
 
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
-    fields = {"s2amdField": wire.field_dtype, "s2amdFieldState": wire.field_state_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in fields.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, {"s2amdField": wire.field_dtype, "s2amdFieldState": wire.field_state_dtype})
     assert (wire.FIELD_SIZE, wire.FIELD_STATE_SIZE) == (128, 64)
 
 
 def test_header_defines_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
-    for define in ("#define S2AMD_MAX_FIELDS 1024", "#define S2AMD_FIELD_RADIAL 1", "#define S2AMD_FIELD_UNIFORM 2", "#define S2AMD_FIELD_DRAG 3",
-                   "#define S2AMD_FIELD_DISABLED 1", "#define S2AMD_FIELD_AS_IMPULSE 2", "#define S2AMD_FIELD_LINEAR_FALLOFF 4", "#define S2AMD_API_VERSION 5"):
-        assert re.search(re.escape(define).replace(r"\ ", r"\s+") + r"\b", header), define
+    defines = {"S2AMD_MAX_FIELDS": 1024, "S2AMD_FIELD_RADIAL": 1, "S2AMD_FIELD_UNIFORM": 2, "S2AMD_FIELD_DRAG": 3, "S2AMD_FIELD_DISABLED": 1,
+               "S2AMD_FIELD_AS_IMPULSE": 2, "S2AMD_FIELD_LINEAR_FALLOFF": 4, "S2AMD_API_VERSION": 5}
+    hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_FIELDS, wire.FIELD_RADIAL, wire.FIELD_UNIFORM, wire.FIELD_DRAG) == (1024, 1, 2, 3)
     assert (wire.FIELD_DISABLED, wire.FIELD_AS_IMPULSE, wire.FIELD_LINEAR_FALLOFF) == (1, 2, 4)
     assert wire.API_VERSION == 5
-    for method in ("world_apply_fields", "world_set_fields", "world_field_states"):
-        assert callable(getattr(hip.Solver, method))
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 # ---- the statement on hand-made cases whose products are exact: the distance is given, not computed ----
@@ -181,24 +148,9 @@ def test_statement_equals_the_edit_route_on_the_fixtures(name):
     other = [n for n in bodies.dtype.names if n not in ("linearVelocity", "angularVelocity", "force")]
     assert all(bodies[n].tobytes() == world["bodies"][n].tobytes() for n in other)
     if name == "shapes_zoo40_PGS_NGS_Block":
-        assert_zoo_condition(world, states, edits)
+        ref.assert_zoo_condition(world, states, edits)
     if name == "tumbler60_TGS_Soft":  # the drum: one dynamic body with four shapes -- four terms per field on it
         assert np.bincount(edits["target"]).max() == 4 * len(fields) and (states["terms"] == 64).all()
-
-
-def assert_zoo_condition(world, states, edits):
-    """What keeps the shapes_zoo40 cases from passing vacuously: every field has at least 12 terms and at least 3 bodies with two terms,
-    and at least 5 bodies are reached by two or more fields"""
-    at, reach = 0, {}
-    for i, n in enumerate(states["terms"]):
-        targets, counts = np.unique(edits["target"][at:at + n], return_counts=True)
-        at += n
-        assert n >= 12 and (counts >= 2).sum() >= 3, (i, n, counts)
-        for b in targets:
-            reach.setdefault(int(b), set()).add(i)
-    assert sum(len(v) >= 2 for v in reach.values()) >= 5
-    static_six = [b for b in np.flatnonzero(world["bodies"]["type"] == wire.BODY_STATIC) if (world["shapes"]["body"] == b).sum() >= 6]
-    assert static_six and not np.isin(edits["target"], static_six).any()
 
 
 @needs_reference
@@ -215,38 +167,15 @@ def test_recorded_fixtures_equal_the_compiled_reference(name):
 def test_kernels_use_no_scratch():
     """hipcc's own report for force_field.hip (make resources-force-field), through tools/kernel_resources.py: every kernel of the file
     is there, none has a private frame or spills."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-force-field"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_force_field.txt"))
-    for kernel in ("fieldKeysKernel", "fieldPrepareKernel", "fieldApplyKernel", "reportBodyRangesKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 3, r
+    kernels = dict.fromkeys(("fieldKeysKernel", "fieldPrepareKernel", "fieldApplyKernel", "reportBodyRangesKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-force-field", "resources_force_field.txt", kernels, floor=3)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_force_field_host_code_under_asan_and_ubsan(tmp_path):
     """Every validation rule through both entry points, with and without a world -> the list held across uploads with other capacities
     -> one-shot calls with and without states, shorter and longer than the pinned stage -> the body -> shapes list built once per upload
     and only when fields are used -> the states getter with too-small, exact and ample heap buffers of exactly the size passed, before
     a step, after it, after the list was replaced, refused and cleared -> destroy, for 0, 1, 129, 257 and 1,024 fields, on the sanitizer
     build of tests/test_hostcheck.py (kernels never run there)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "force_field_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "force_field_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "FORCE FIELD MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "force_field_main.cpp", "FORCE FIELD MAIN OK", timeout=600)

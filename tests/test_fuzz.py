@@ -6,6 +6,8 @@ import pytest
 
 from solver2d_amd import islands, wire
 from tests import common, fuzz_worlds, oraclebind
+from tests.fuzz_worlds import perturbed_pyramid
+from tests.parity import gpu_vs_oracle_loose
 
 SEEDS = list(range(12))
 
@@ -28,7 +30,6 @@ def test_oracle_is_finite_or_consistent_on_random_worlds(seed, solver_name):
 @pytest.mark.parametrize("seed", SEEDS)
 def test_gpu_equals_oracle_on_random_worlds(seed, groups):
     from solver2d_amd import hip
-    from tests.test_gpu_parity import gpu_vs_oracle_loose
 
     world = fuzz_worlds.random_world(seed, n_bodies=30 + 7 * seed, n_contacts=60 + 15 * seed, n_joints=8 + seed)
     with hip.Solver(0) as gpu:
@@ -48,7 +49,6 @@ def test_gpu_equals_oracle_on_random_worlds_through_strips(seed, joints):
     cut into tiny strips: the soft solvers take the persistent strip step when the world has no joints, the strip
     launches or the colour batches otherwise -- every path bit-exact in the reported order."""
     from solver2d_amd import hip
-    from tests.test_gpu_parity import gpu_vs_oracle_loose
 
     world = fuzz_worlds.random_world(seed + 100, n_bodies=60 + 9 * seed, n_contacts=140 + 25 * seed, n_joints=joints)
     with hip.Solver(0) as gpu:
@@ -65,39 +65,6 @@ def test_gpu_equals_oracle_on_random_worlds_through_strips(seed, joints):
                     gpu_vs_oracle_loose(gpu, p, world, "fuzz strips seed %d %s warm=%d any=%d" % (seed, solver_name, warm, any_solver))
 
 
-def perturbed_pyramid(seed, base=36):
-    """The pyramid's contact graph (long BFS diameter, degree <= 6: strips and the persistent kernel apply) with
-    randomised numbers: velocities, impulses, anchors, separations, one-point contacts, a few inactive contacts,
-    kinematic and static bodies in the pile."""
-    from solver2d_amd import synthetic
-    rng = np.random.default_rng(1000 + seed)
-    bodies, contacts, joints = common.copy3(synthetic.pyramid(base))
-    nb, nc = len(bodies), len(contacts)
-    bodies["linearVelocity"] += rng.normal(0.0, 0.5, (nb, 2)).astype(np.float32)
-    bodies["angularVelocity"] += rng.normal(0.0, 0.5, nb).astype(np.float32)
-    ang = rng.normal(0.0, 0.05, nb).astype(np.float32)
-    bodies["rot"][:, 0], bodies["rot"][:, 1] = np.sin(ang), np.cos(ang)
-    bodies["linearDamping"] = rng.uniform(0.0, 0.2, nb).astype(np.float32)
-    for i in rng.choice(np.arange(1, nb), size=6, replace=False):
-        bodies["type"][i] = wire.BODY_KINEMATIC if i % 2 else wire.BODY_STATIC
-        bodies["mass"][i] = bodies["invMass"][i] = bodies["I"][i] = bodies["invI"][i] = 0.0
-        if bodies["type"][i] == wire.BODY_STATIC:
-            bodies["linearVelocity"][i] = 0.0
-            bodies["angularVelocity"][i] = 0.0
-    pts = contacts["points"]
-    pts["normalImpulse"] = rng.uniform(0.0, 2.0, pts["normalImpulse"].shape).astype(np.float32)
-    pts["tangentImpulse"] = rng.normal(0.0, 0.3, pts["tangentImpulse"].shape).astype(np.float32)
-    pts["separation"] += rng.normal(0.0, 0.01, pts["separation"].shape).astype(np.float32)
-    pts["localAnchorA"] += rng.normal(0.0, 0.02, pts["localAnchorA"].shape).astype(np.float32)
-    pts["localAnchorB"] += rng.normal(0.0, 0.02, pts["localAnchorB"].shape).astype(np.float32)
-    contacts["friction"] = rng.uniform(0.0, 1.0, nc).astype(np.float32)
-    if seed % 2:
-        one = rng.random(nc) < 0.3
-        contacts["pointCount"][one & (contacts["pointCount"] == 2)] = 1
-        contacts["pointCount"][rng.random(nc) < 0.03] = 0
-    return bodies, contacts, joints
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("solver_name", ["TGS_Soft", "SoftStep", "PGS_Soft"])
 def test_persistent_strip_step_on_perturbed_pyramids(solver_name):
@@ -106,7 +73,6 @@ def test_persistent_strip_step_on_perturbed_pyramids(solver_name):
     bit-exact; most of them must take the persistent kernel (greedy colouring sometimes needs a 7th colour, which
     sends that world to the multi-launch strip path)."""
     from solver2d_amd import hip
-    from tests.test_gpu_parity import gpu_vs_oracle_loose
 
     vel, pos = common.DEFAULT_ITERS[solver_name]
     persistent, two_point, general = 0, 0, 0
@@ -137,7 +103,6 @@ def test_moving_read_only_bodies_shared_between_strips(solver_name):
     while the owner was writing them in the same launch (a race: different bits from run to run).  Such partitions are
     now only run by the one-launch persistent kernel, else the island goes back to colour batches."""
     from solver2d_amd import hip
-    from tests.test_gpu_parity import gpu_vs_oracle_loose
 
     seed = 205
     world = fuzz_worlds.random_world(seed, n_bodies=40 + 11 * (seed % 9), n_contacts=90 + 31 * (seed % 7), n_joints=0)
@@ -163,7 +128,6 @@ def test_written_bodies_outside_every_strip(strip_bodies):
     body whose rot is not a fixed point of the normalisation is WRITTEN by the position sweeps, but it is not one of the
     loose bodies the strip partition walks, so two strips each believed they owned it.  Such a graph gets no strips."""
     from solver2d_amd import hip
-    from tests.test_gpu_parity import gpu_vs_oracle_loose
 
     seed = 259
     world = fuzz_worlds.random_world(seed, n_bodies=40 + 11 * (seed % 9), n_contacts=90 + 31 * (seed % 7), n_joints=(seed % 5) * 2)
@@ -185,7 +149,6 @@ def test_pyramids_with_kinematic_and_massless_bodies_inside():
     they touch boxes of several strips: the persistent kernel keeps a consistent copy per workgroup; where it is not
     eligible the island must be back on colour batches (never on the one-launch-per-sweep strip paths)."""
     from solver2d_amd import hip
-    from tests.test_gpu_parity import gpu_vs_oracle_loose
 
     persistent = other = 0
     for seed in range(100, 112):

@@ -15,13 +15,12 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import actuator_ref as ref, force_field_ref, ray_report_ref, ray_report_world as rw, world_chain
-from tests.test_gpu_step_metrics import download, golden, step_both, upload
-from tests.test_gpu_world_edit import OTHER_KEYS, assert_same_world, slots_of
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, OTHER_KEYS, assert_same_world, download, motorised, refuses, slots_of, step_both, upload
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 STEPS = 12
 F = np.float32
 FORCE, THRUST, LINEAR, ANGULAR, MOTOR, SERVO, MOUSE = range(1, 8)
@@ -33,15 +32,6 @@ def assert_states(got, want, what):
         bad = [n for n in got.dtype.names if got[n].tobytes() != want[n].tobytes()]
         rows = np.flatnonzero([got[i].tobytes() != want[i].tobytes() for i in range(len(got))])
         raise AssertionError("%s: states differ in %s, first rows %s: %s / %s" % (what, bad, rows[:3].tolist(), got[rows[:2]], want[rows[:2]]))
-
-
-def motorised(world, torque=40.0):
-    """A copy whose revolute joints have their motors on"""
-    out = world_chain.copy_world(world)
-    rev = out["joints"]["type"] == wire.JOINT_REVOLUTE
-    out["joints"]["enableMotor"][rev] = 1
-    out["joints"]["maxMotorTorque"][rev] = torque
-    return out
 
 
 def pass_and_step(s, params, ref_world, actuators, actions, what, world=None):
@@ -367,9 +357,7 @@ def test_errors():
             s.world_actuator_states()
         upload(s, world)
         s.world_set_actions(actions)
-        for call in (s.world_actuator_states, s.world_actuator_counts):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                call()  # no step since the upload
+        refuses(s, E_STATE, ("world_actuator_states", "world_actuator_counts"))  # no step since the upload
         # per call
         many = np.zeros(wire.MAX_ACTUATORS + 1, dtype=wire.actuator_dtype)
         many[:] = good[1]

@@ -3,102 +3,25 @@ _islands / _body_summary; solver2d_amd/csrc/body_report.hip) against its numpy s
 tests/world_chain.py, stepped in the contact and joint orders the device reports: every record, both lists, every island and the summary
 equal byte for byte, every step."""
 import ctypes
-import glob
-import os
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
 from tests import body_report_ref as ref, body_report_world, common, contact_report_ref, joint_report_ref, shape_report_ref, world_chain
-from tests.test_gpu_world import _create_contacts
-from tests.world_chain import oracle_find_pairs, oracle_world_step, rain_world
+from tests.body_report_world import assert_body_report_equals_reference, thresholds_of
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, download, refuses, step_both, upload
+from tests.world_chain import _create_contacts, golden, oracle_find_pairs, oracle_world_step, rain_world
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 STEPS = 12
 f32 = np.float32
 ALL, NO_FILTER = wire.BODY_REPORT_ALL, wire.BODY_REPORT_STATES | wire.BODY_REPORT_REST | wire.BODY_REPORT_ISLANDS
 
 
-def golden(name):
-    """(params, world) of tests/golden/world_<name>_step*.npz"""
-    (path,) = glob.glob(os.path.join(GOLDEN, "world_%s_step*.npz" % name))
-    d = np.load(path)
-    return world_chain.params_of(d), world_chain.load_world(d)
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
-
-
-def step_both(s, params, ref_world):
-    """One s2amd_world_step and the same step of the oracle chain in the device's orders; returns the step's info."""
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
-
-
-def thresholds_of(linear, dt):
-    return (f32(linear), f32(f32(linear) * f32(3.4906585)), f32(3) * f32(dt))
-
-
 def new_totals():
     return {"rested": 0, "woke": 0, "rested_high": 0, "woke_high": 0, "islands": [], "largest": 0, "spanning": 0, "records": 0, "unmoved": 0}
-
-
-def assert_records_equal(got, want, what):
-    assert len(got) == len(want), "%s: %d records, reference %d" % (what, len(got), len(want))
-    if got.tobytes() != want.tobytes():
-        bad = [n for n in got.dtype.names if got[n].tobytes() != want[n].tobytes()]
-        rows = np.flatnonzero([got[i].tobytes() != want[i].tobytes() for i in range(len(got))])
-        raise AssertionError("%s: records differ in %s, first rows %s: %s / %s" % (what, bad, rows[:3].tolist(), got[rows[:2]], want[rows[:2]]))
-
-
-def assert_body_report_equals_reference(s, state, world, thresholds, dt, what, flags=ALL, totals=None):
-    """The four getters against the reference statement on `world` (the oracle chain after the step); `state` moves on by one step."""
-    step = ref.advance(state, world, thresholds, dt)
-    island = island_states = None
-    if flags & wire.BODY_REPORT_ISLANDS:
-        island, island_states = ref.islands(world, step)
-        assert_records_equal(s.world_islands(expected=max(len(island_states), 1)), island_states, what + ": islands")
-    if flags & wire.BODY_REPORT_STATES:
-        want = ref.states(world, step, bool(flags & wire.BODY_REPORT_MOVED_ONLY), island, island_states)
-        assert_records_equal(s.world_body_states(expected=max(len(want), 1)), want, what + ": states")
-    if flags & wire.BODY_REPORT_REST:
-        want_rested, want_woke = ref.events(step)
-        rested, woke = s.world_body_rest_events()
-        assert rested.tolist() == want_rested.tolist(), what + ": rested"
-        assert woke.tolist() == want_woke.tolist(), what + ": woke"
-    want_summary = ref.summary(world, step, island_states)
-    summary = s.world_body_summary()
-    assert summary.tobytes() == want_summary.tobytes(), "%s: summary %s, reference %s" % (what, summary, want_summary)
-    if totals is not None:
-        # (counted on the reference chain of the run)
-        rested, woke = ref.events(step)
-        totals["rested"] += len(rested)
-        totals["woke"] += len(woke)
-        totals["rested_high"] += int((rested >= 256).sum())
-        totals["woke_high"] += int((woke >= 256).sum())
-        totals["records"] += int(step["reported"].sum())
-        totals["unmoved"] += int((step["reported"] & ~step["moved"]).sum())
-        totals["last_moved"] = step["moved"]
-        if island_states is not None:
-            totals["islands"].append(len(island_states))
-            totals["largest"] = max(totals["largest"], int(island_states["bodyCount"].max()) if len(island_states) else 0)
-            low = set(island[:256][island[:256] >= 0].tolist())
-            totals["spanning"] = max(totals["spanning"], len(low & set(island[256:][island[256:] >= 0].tolist())))
-    return step
 
 
 def run_chain(s, params, world, thresholds, what, steps=STEPS, flags=ALL):
@@ -238,9 +161,7 @@ def test_report_off_changes_nothing_and_the_getters_refuse():
         on.world_set_rest_thresholds(*thresholds)
         off.world_set_rest_thresholds(*thresholds)  # thresholds without a flag: nothing to enqueue
         upload(on, world), upload(off, world)
-        for getter in (on.world_body_states, on.world_body_rest_events, on.world_islands, on.world_body_summary):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # no step since the upload
+        refuses(on, E_STATE, ("world_body_states", "world_body_rest_events", "world_islands", "world_body_summary"))  # no step since the upload
         launches_compared = 0
         for step in range(STEPS):
             a, b = on.world_step(params), off.world_step(params)
@@ -330,17 +251,13 @@ def test_capacity_errors_thresholds_off_and_on_and_a_second_upload():
         assert int((state["timer"] > 0).sum()) >= 30
         s.world_set_body_report(0)
         step_both(s, params, ref_world)  # advances nothing
-        for getter in (s.world_body_summary, s.world_body_states):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_body_summary", "world_body_states"))
         s.world_set_body_report(wire.BODY_REPORT_REST)
         state = ref.new_state(ref_world)
         step_both(s, params, ref_world)
         step = assert_body_report_equals_reference(s, state, ref_world, loose, params.dt, "off and on", wire.BODY_REPORT_REST)
         assert len(ref.events(step)[0]) >= 30  # (everything still or slow has a timer of dt again: rested under `seconds` = dt)
-        for getter in (s.world_body_states, s.world_islands):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # not this step's flags
+        refuses(s, E_STATE, ("world_body_states", "world_islands"))  # not this step's flags
 
         # a second upload with other capacities: 42 body slots instead of 640; flags and thresholds hold across it
         params2, world2 = golden("mixed24_PGS")

@@ -8,22 +8,12 @@ import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import contact_query_ref as ref, contact_query_world as cw, scene_query_world as sq, world_chain
+from tests import contact_query_ref as ref, contact_query_world as cw, resident, scene_query_world as sq, world_chain
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, download, upload
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 STEPS = 12
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
 
 
 def ask(s, queries):
@@ -63,12 +53,7 @@ def ask_raw(s, queries):
 
 
 def assert_equal_bytes(got, want, what):
-    for key in cw.RESULT_KEYS:
-        g, w = np.ascontiguousarray(got[key]), np.ascontiguousarray(want[key])
-        assert g.dtype == w.dtype and g.shape == w.shape, "%s: %s: %r %r / %r %r" % (what, key, g.dtype, g.shape, w.dtype, w.shape)
-        if g.tobytes() != w.tobytes():
-            bad = np.nonzero([a.tobytes() != b.tobytes() for a, b in zip(g, w)])[0]
-            raise AssertionError("%s: %s differs at %s: got %r, want %r" % (what, key, bad[:8], g[bad[:2]], w[bad[:2]]))
+    resident.assert_equal_bytes(got, want, what, cw.RESULT_KEYS)
 
 
 @pytest.mark.parametrize("name", cw.FIXTURES)

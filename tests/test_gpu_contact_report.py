@@ -8,22 +8,11 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, contact_report_ref as ref, world_chain
-from tests.test_gpu_world import _create_contacts
 from tests.world_chain import oracle_find_pairs, oracle_world_step, rain_world
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, download, refuses, upload
+from tests.world_chain import _create_contacts
 
 pytestmark = pytest.mark.gpu
-
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
 
 
 def assert_report_equals_reference(s, prev, world, what, totals=None, status=None):
@@ -110,9 +99,7 @@ def test_report_off_changes_nothing_and_the_getters_refuse():
     world = rain_world(3, 120)
     keys = ("separatedCount", "activeContacts", "graphChanged", "movedCount")
     with hip.Solver(0) as on, hip.Solver(0) as off:
-        for getter in (off.world_touch_events, off.world_touching, off.world_body_sums):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # no resident world
+        refuses(off, E_STATE, ("world_touch_events", "world_touching", "world_body_sums"))  # no resident world
         on.world_set_report(wire.REPORT_ALL)
         upload(on, world), upload(off, world)
         moved = True
@@ -130,9 +117,7 @@ def test_report_off_changes_nothing_and_the_getters_refuse():
             assert [a[k] for k in keys] == [b[k] for k in keys], "step %d: %r / %r" % (step, a, b)
             moved = a["movedCount"] > 0
             on.world_touch_events(), on.world_touching(), on.world_body_sums()
-            for getter in (off.world_touch_events, off.world_touching, off.world_body_sums):
-                with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                    getter()
+            refuses(off, E_STATE, ("world_touch_events", "world_touching", "world_body_sums"))
             (wa, sa), (wb, sb) = download(on, world), download(off, world)
             assert np.array_equal(sa, sb), "step %d: status" % step
             for k in world_chain.WORLD_KEYS:
@@ -156,14 +141,10 @@ def test_flag_subsets_and_unknown_bits():
         oracle_world_step(params, ref_world, contact_order=s.contact_order()[0])
         began, ended = s.world_touch_events()
         assert began.tolist() == [] and ended.tolist() == []
-        for getter in (s.world_touching, s.world_body_sums):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_touching", "world_body_sums"))
         # a flag set between two steps takes effect from the next step
         s.world_set_report(wire.REPORT_ALL)
-        for getter in (s.world_touching, s.world_body_sums):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_touching", "world_body_sums"))
         prev = ref.touching_mask(ref_world)
         s.world_step(params)
         oracle_world_step(params, ref_world, contact_order=s.contact_order()[0])
@@ -174,9 +155,7 @@ def test_flag_subsets_and_unknown_bits():
         s.world_step(params)
         oracle_world_step(params, ref_world, contact_order=s.contact_order()[0])
         assert s.world_body_sums().tobytes() == ref.body_sums(ref_world).tobytes()
-        for getter in (s.world_touch_events, s.world_touching):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_touch_events", "world_touching"))
 
 
 def test_capacity_errors_set_the_counts_and_consume_nothing():

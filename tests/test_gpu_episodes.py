@@ -12,14 +12,12 @@ import pytest
 
 from solver2d_amd import hip, wire
 from tests import episode_ref as ref, grid_report_world as gw, sensor_report_world as sw, world_chain
-from tests.test_gpu_actuators import motorised
-from tests.test_gpu_observers import down_ray, every_kind, packed
-from tests.test_gpu_step_metrics import download, golden, step_both, upload
-from tests.test_gpu_world_edit import slots_of
+from tests.resident import (E_CAPACITY, E_INVALID, E_STATE, assert_same_bytes, down_ray, download, every_kind, motorised, packed, refuses, slots_of,
+                            step_both, upload)
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 F = np.float32
 ALL = wire.EPISODE_REPORT_ALL
 STEP, STATES, RULE_STATES, EVENTS = wire.EPISODE_REPORT_STEP, wire.EPISODE_REPORT_STATES, wire.EPISODE_REPORT_RULE_STATES, wire.EPISODE_REPORT_EVENTS
@@ -30,22 +28,15 @@ GETTERS = ("world_episode_rewards", "world_episode_flags", "world_episode_states
 rule = wire.episode_rule
 
 
-def same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
-    if got.tobytes() != want.tobytes():
-        rows = np.flatnonzero([got[i].tobytes() != want[i].tobytes() for i in range(len(got))])
-        raise AssertionError("%s differ, first rows %s: %s / the statement %s" % (what, rows[:3].tolist(), got[rows[:2]], want[rows[:2]]))
-
-
 def expect(s, acc, rules, agents, limits, what, obs_on=True, dims=None):
     """The statement on this step's s.world_observations() (None with the observation report off) against every getter -> its dict"""
     obs = s.world_observations() if obs_on else None
     want = ref.step(acc, obs, rules, agents, limits, dims)
-    same(s.world_episode_rewards(), want["rewards"], what + ": rewards")
-    same(s.world_episode_flags(), want["flags"], what + ": flags")
-    same(s.world_episode_states(), want["states"], what + ": agent states")
-    same(s.world_episode_rule_states(), want["rule_states"], what + ": rule states")
-    same(s.world_episode_events(), want["events"], what + ": events")
+    assert_same_bytes(s.world_episode_rewards(), want["rewards"], what + ": rewards")
+    assert_same_bytes(s.world_episode_flags(), want["flags"], what + ": flags")
+    assert_same_bytes(s.world_episode_states(), want["states"], what + ": agent states")
+    assert_same_bytes(s.world_episode_rule_states(), want["rule_states"], what + ": rule states")
+    assert_same_bytes(s.world_episode_events(), want["events"], what + ": events")
     assert s.world_episode_counts().tolist() == want["counts"].tolist(), what
     return want
 
@@ -233,9 +224,7 @@ def test_differences_over_frames_and_the_rebases():
         # the episode flags at 0: the observers go on, the episodes do not; on again: re-based
         s.world_set_episode_report(0)
         s.world_step(params)
-        for name in GETTERS:
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getattr(s, name)()
+        refuses(s, E_STATE, GETTERS)
         s.world_set_episode_report(ALL)
         acc.rebase()
         want = run(s, acc, 1, "episode flags on again", False)
@@ -399,14 +388,10 @@ def test_getters_and_refusals():
         assert all(len(getattr(s, name)()) == 0 for name in GETTERS[:5]) and s.world_episode_counts().tolist() == [0] * 8  # no list
         s.world_set_episodes(good, 3, limits)  # accepted before any world
         s.world_set_episode_report(ALL)
-        for name in GETTERS:
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getattr(s, name)()  # no resident world
+        refuses(s, E_STATE, GETTERS)  # no resident world
         driven(s, world)
         upload(s, world)
-        for name in GETTERS:
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getattr(s, name)()  # no step since the upload
+        refuses(s, E_STATE, GETTERS)  # no step since the upload
         acc = ref.Accounting(3)
         s.world_set_actions(np.array([2.5, 0.5, -1.5, 0.0], dtype=F))
         s.world_step(params)
@@ -428,8 +413,8 @@ def test_getters_and_refusals():
             with pytest.raises(hip.S2AmdError, match="error %d" % E_INVALID):
                 s.world_set_episodes(wrong, 3, limits)
         # a refused list leaves the previous answers in place
-        same(s.world_episode_states(), before["states"], "after the refusals")
-        same(s.world_episode_rule_states(), before["rule_states"], "after the refusals")
+        assert_same_bytes(s.world_episode_states(), before["states"], "after the refusals")
+        assert_same_bytes(s.world_episode_rule_states(), before["rule_states"], "after the refusals")
         # the getters' arguments
         count = ctypes.c_int32(-7)
         out = np.zeros(3, dtype=F)

@@ -11,16 +11,15 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import body_report_ref, force_field_ref as ref, sensor_report_ref, world_chain
-from tests.test_force_field_host import assert_zoo_condition
-from tests.test_gpu_body_report import assert_body_report_equals_reference, thresholds_of
-from tests.test_gpu_step_metrics import download, golden, step_both, upload
-from tests.test_gpu_world_edit import OTHER_KEYS, assert_same_world
+from tests.body_report_world import assert_body_report_equals_reference, thresholds_of
+from tests.force_field_ref import assert_zoo_condition
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, OTHER_KEYS, assert_same_world, download, step_both, upload
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 # (the cases on a committed fixture of tests/golden/force_fields take its recorded distance outputs and run without the compiled reference)
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 STEPS = 12
 IMPULSE, FALLOFF, DISABLED = wire.FIELD_AS_IMPULSE, wire.FIELD_LINEAR_FALLOFF, wire.FIELD_DISABLED
 

@@ -10,7 +10,7 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, oraclebind, refbind, world_chain
-from tests.test_gpu_parity import check_order_is_valid, gpu_vs_oracle, gpu_vs_oracle_loose
+from tests.parity import check_order_is_valid, gpu_vs_oracle, gpu_vs_oracle_loose
 
 pytestmark = pytest.mark.gpu
 

@@ -11,7 +11,8 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, fuzz_worlds, golden_util
-from tests.test_gpu_parity import gpu_vs_oracle, gpu_vs_oracle_loose
+from tests.fuzz_worlds import perturbed_pyramid
+from tests.parity import gpu_vs_oracle, gpu_vs_oracle_loose
 
 pytestmark = pytest.mark.gpu
 
@@ -117,9 +118,8 @@ def test_golden_worlds_really_ran_on_the_op_interpreter(tiny_strips):
 
 def pile_with_joints(seed, base, joints):
     """The pyramid's contact graph (long BFS diameter: strips apply) with randomised numbers, one-point and inactive contacts,
-    kinematic and static bodies in the pile (tests/test_fuzz.py: perturbed_pyramid) -- plus `joints` revolute and mouse joints with
-    limits, motors and springs (tests/fuzz_worlds.py's mix) between boxes that touch, i.e. inside strips and across seams."""
-    from tests.test_fuzz import perturbed_pyramid
+    kinematic and static bodies in the pile (tests/fuzz_worlds.py: perturbed_pyramid) -- plus `joints` revolute and mouse joints with
+    limits, motors and springs (the same file's mix) between boxes that touch, i.e. inside strips and across seams."""
     rng = np.random.default_rng(7000 + seed)
     bodies, contacts, _ = perturbed_pyramid(seed, base)
     # (a static body whose rot is not a fixed point of the normalisation is written by the position sweeps and can be owned by no

@@ -11,130 +11,15 @@ import pytest
 
 from solver2d_amd import hip, wire
 from tests import grid_report_ref as ref, grid_report_world as gw, sensor_report_world as sw, world_chain
-from tests.world_chain import oracle_world_step
+from tests.grid_report_world import assert_probe, assert_report, assert_statement, assert_structure, getters
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, downloaded_world, refuses, step_both, upload
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 ALL = wire.GRID_REPORT_ALL
 DISABLED, SKIP_STATIC = wire.GRID_SENSOR_DISABLED, wire.GRID_SENSOR_SKIP_STATIC
 GETTERS = {wire.GRID_REPORT_CATEGORIES: "world_grid_categories", wire.GRID_REPORT_SHAPES: "world_grid_shapes",
            wire.GRID_REPORT_OCCUPANCY: "world_grid_occupancy", wire.GRID_REPORT_STATES: "world_grid_states"}
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6]))
-
-
-def refuses(s, code, names=tuple(GETTERS.values())):
-    for name in names:
-        with pytest.raises(hip.S2AmdError, match="error %d" % code):
-            getattr(s, name)()
-
-
-def getters(s):
-    return s.world_grid_categories(), s.world_grid_shapes(), s.world_grid_occupancy(), s.world_grid_states()
-
-
-def plain(world, grids):
-    """Which grids the two exclusions cannot change: fixed in the world or on a body without a live shape, and no SKIP_STATIC"""
-    shapes = world["shapes"]
-    live_bodies = set(shapes["body"][shapes["type"] != wire.SHAPE_FREE].tolist())
-    return np.array([(int(q["body"]) < 0 or int(q["body"]) not in live_bodies) and not (int(q["flags"]) & SKIP_STATIC) for q in grids], dtype=bool)
-
-
-def assert_structure(world, grids, got, what):
-    """What every report satisfies whatever the geometry: sizes, the fixed fields, the states' figures from the arrays"""
-    cats, low, occ, states = got
-    first, total = ref.first_cells(grids)
-    assert len(cats) == len(low) == len(occ) == total and len(states) == len(grids), what
-    assert states["grid"].tolist() == list(range(len(grids))) and states["body"].tobytes() == grids["body"].tobytes(), what
-    assert states["firstCell"].tolist() == first.tolist() and states["cells"].tolist() == (grids["width"] * grids["height"]).tolist(), what
-    assert occ.tobytes() == (low >= 0).astype(np.float32).tobytes() and ((cats != 0) == (low >= 0)).all(), what
-    shapes = world["shapes"]
-    hit = low >= 0
-    assert (shapes["type"][low[hit]] != wire.SHAPE_FREE).all() and ((cats[hit] & shapes["categoryBits"][low[hit]]) != 0).all(), what
-    for g, q in enumerate(grids):
-        mine = low[first[g]: first[g] + int(q["width"]) * int(q["height"])]
-        st = states[g]
-        assert st["occupied"] == (mine >= 0).sum() and st["lowestShape"] == (mine[mine >= 0].min() if (mine >= 0).any() else -1), (what, g)
-        if not st["active"]:
-            assert (mine == -1).all() and st["candidates"] == 0 and st["position"].tobytes() + st["rot"].tobytes() + st["box"].tobytes() == bytes(32), (what, g)
-        else:
-            own = int(q["body"])
-            assert own < 0 or (shapes["body"][mine[mine >= 0]] != own).all(), (what, g)  # a mounted grid never sees its own body
-            if int(q["flags"]) & SKIP_STATIC:
-                assert (world["bodies"]["type"][shapes["body"][mine[mine >= 0]]] != wire.BODY_STATIC).all(), (what, g)
-
-
-def assert_probe(s, world, grids, got, what):
-    """The device's own s2amd_world_point_probe of the statement's cell points, folded: the arrays of every plain grid"""
-    cats, low, occ, states = got
-    first, total = ref.first_cells(grids)
-    active = np.array([ref.cell_points(world, q)[0] for q in grids], dtype=bool)
-    assert states["active"].tolist() == active.astype(int).tolist(), what
-    points, index = ref.probes_of(world, grids)
-    if len(points) == 0:
-        return
-    offsets, flat = s.world_point_probe(points, expected=4 * len(points) + 64)
-    pc, pl, po = ref.fold_probe(world, total, index, offsets, flat)
-    keep = np.zeros(total, dtype=bool)
-    ok = plain(world, grids)
-    for g, q in enumerate(grids):
-        if ok[g] or not active[g]:
-            keep[first[g]: first[g] + int(q["width"]) * int(q["height"])] = True
-    assert cats[keep].tobytes() == pc[keep].tobytes(), what
-    assert low[keep].tobytes() == pl[keep].tobytes(), what
-    assert occ[keep].tobytes() == po[keep].tobytes(), what
-    # ... and an exclusion only ever removes hits
-    assert ((cats & ~pc) == 0).all() and ((low >= pl) | (low < 0)).all(), what
-
-
-def assert_statement(world, grids, got, what, period=None):
-    """The statement's bytes where the reference is built; a list that repeats its first `period` grids is compared on one period"""
-    if not ref.available():
-        return
-    cats, low, occ, states = got
-    n = len(grids) if period is None or period >= len(grids) else period
-    if n < len(grids):
-        assert all(grids[i].tobytes() == grids[i % n].tobytes() for i in range(len(grids)))
-    wc, wl, wo, ws = ref.report(world, grids[:n])
-    cells = len(wc)
-    for k in range(0, len(grids), n):
-        m = min(n, len(grids) - k)
-        c = int(ws["firstCell"][m - 1] + ws["cells"][m - 1])
-        at = (k // n) * cells
-        assert cats[at: at + c].tobytes() == wc[:c].tobytes() and low[at: at + c].tobytes() == wl[:c].tobytes() and occ[at: at + c].tobytes() == wo[:c].tobytes(), (what, k)
-        want = ws[:m].copy()
-        want["grid"] += k
-        want["firstCell"] += at
-        if states[k: k + m].tobytes() != want.tobytes():
-            bad = [f for f in want.dtype.names if states[k: k + m][f].tobytes() != want[f].tobytes()]
-            raise AssertionError("%s: states of period %d differ in %s: %s / %s" % (what, k, bad, states[k: k + m][:2], want[:2]))
-
-
-def assert_report(s, world, grids, what, period=None, statement=True):
-    resident = download(s, world)
-    got = getters(s)
-    assert_structure(resident, grids, got, what)
-    assert_probe(s, resident, grids, got, what)
-    if statement:
-        assert_statement(resident, grids, got, what, period)
-    return got
-
-
-def step_both(s, params, ref_world):
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
 
 
 @pytest.mark.parametrize("scene,fast", [(scene, fast) for scene in gw.SCENES for fast in (False, True)])
@@ -150,11 +35,11 @@ def test_recorded_scenes_every_step(scene, fast):
         s.world_set_grid_sensors(grids)
         s.world_set_grid_report(ALL)
         upload(s, world)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
         for k in range(gw.STEPS):
             step_both(s, params, ref_world)
             what = "%s step %d" % (scene, k)
-            resident = download(s, world)
+            resident = downloaded_world(s, world)
             got = getters(s)
             assert_structure(resident, grids, got, what)
             assert_probe(s, resident, grids, got, what)
@@ -189,7 +74,7 @@ def test_each_flag_alone_and_all(flags):
                 s.world_export_grid_occupancy(0, 0)
         s.world_set_grid_report(0)
         s.world_step(params)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
 
 
 def test_capacity_protocol_and_export():
@@ -319,7 +204,7 @@ def test_inactive_grids_leave_the_others_alone():
         both = np.concatenate([grids, np.array([on_free], dtype=wire.grid_sensor_dtype)])
         upload(s, world)
         s.world_set_grid_sensors(both)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
         s.world_step(params)
         got = assert_report(s, world, both, "free body")
         assert got[3]["active"][-1] == 0 and got[1][: len(base[1])].tobytes() == base[1].tobytes() and got[0][: len(base[0])].tobytes() == base[0].tobytes()
@@ -362,7 +247,7 @@ def test_list_replaced_cleared_and_voided():
     world, grids = gw.scene("pyramid")
     params = sw.params()
     with hip.Solver(0) as s:
-        refuses(s, E_STATE)  # no world
+        refuses(s, E_STATE, GETTERS.values())  # no world
         for bad in (16, -1):
             with pytest.raises(hip.S2AmdError, match="error %d" % E_INVALID):
                 s.world_set_grid_report(bad)
@@ -387,12 +272,12 @@ def test_list_replaced_cleared_and_voided():
         # replaced: void until the next step
         reversed_list = np.ascontiguousarray(grids[::-1])
         s.world_set_grid_sensors(reversed_list)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
         s.world_step(params)
         assert_report(s, world, reversed_list, "reversed")
         # cleared
         s.world_set_grid_sensors(np.zeros(0, dtype=wire.grid_sensor_dtype))
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
         s.world_step(params)
         assert [len(x) for x in getters(s)] == [0, 0, 0, 0]
         s.world_set_grid_sensors(grids)
@@ -401,10 +286,10 @@ def test_list_replaced_cleared_and_voided():
         # turning on and an upload void
         s.world_set_grid_report(0)
         s.world_set_grid_report(ALL)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
         s.world_step(params)
         upload(s, world)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS.values())
 
 
 def test_the_report_writes_nothing_resident():
@@ -420,7 +305,7 @@ def test_the_report_writes_nothing_resident():
             for _ in range(gw.STEPS):
                 s.world_step(params)
             if flags == 0:
-                refuses(s, E_STATE)
-            out.append(download(s, world))
+                refuses(s, E_STATE, GETTERS.values())
+            out.append(downloaded_world(s, world))
     for key in world_chain.WORLD_KEYS:
         assert out[0][key].tobytes() == out[1][key].tobytes(), key

@@ -17,7 +17,7 @@ import pytest
 
 from solver2d_amd import hip, wire
 from tests import common, world_chain
-from tests.test_gpu_world import _create_contacts
+from tests.world_chain import _create_contacts
 
 pytestmark = pytest.mark.gpu
 

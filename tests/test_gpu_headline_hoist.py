@@ -9,7 +9,7 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, oraclebind
-from tests.test_gpu_selfstrips import resident_vs_oracle
+from tests.parity import resident_vs_oracle
 
 pytestmark = pytest.mark.gpu
 

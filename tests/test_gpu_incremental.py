@@ -8,40 +8,9 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, oraclebind
-from tests.test_gpu_parity import gpu_vs_oracle, gpu_vs_oracle_loose
+from tests.parity import _artificial_contact, _with_spare_slots, gpu_vs_oracle, gpu_vs_oracle_loose
 
 pytestmark = pytest.mark.gpu
-
-
-def _with_spare_slots(state, spare):
-    b, c, j = state
-    free = np.zeros(spare, dtype=wire.contact_dtype)
-    free["bodyA"], free["bodyB"], free["constraintIndex"] = -1, -1, -1  # free pool slots as the reference binding packs them
-    return b, np.concatenate([c, free]), j
-
-
-def _artificial_contact(rng, bodies, template, exclude):
-    """A two- or one-point manifold between two dynamic boxes that share no contact yet (the geometry is made up: this
-    is a solver input, not a scene)."""
-    dyn = np.flatnonzero(bodies["type"] == wire.BODY_DYNAMIC)
-    while True:
-        a, b = (int(x) for x in rng.choice(dyn, size=2, replace=False))
-        if (min(a, b), max(a, b)) not in exclude:
-            break
-    exclude.add((min(a, b), max(a, b)))
-    c = template.copy()
-    c["bodyA"], c["bodyB"] = a, b
-    c["pointCount"] = int(rng.integers(1, 3))
-    ang = rng.uniform(0, 2 * np.pi)
-    c["normal"] = (np.cos(ang), np.sin(ang))
-    c["friction"] = rng.uniform(0.2, 0.9)
-    for p in range(2):
-        c["points"][p]["localAnchorA"] = rng.uniform(-0.5, 0.5, 2)
-        c["points"][p]["localAnchorB"] = rng.uniform(-0.5, 0.5, 2)
-        c["points"][p]["separation"] = rng.uniform(-0.02, 0.01)
-        c["points"][p]["normalImpulse"] = 0.0
-        c["points"][p]["tangentImpulse"] = 0.0
-    return c
 
 
 @pytest.mark.parametrize("solver_name", wire.SOLVER_NAMES)

@@ -13,8 +13,7 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, golden_util
-from tests.test_gpu_incremental import _artificial_contact, _with_spare_slots
-from tests.test_gpu_parity import gpu_vs_oracle, gpu_vs_oracle_loose
+from tests.parity import _artificial_contact, _with_spare_slots, gpu_vs_oracle, gpu_vs_oracle_loose
 
 pytestmark = pytest.mark.gpu
 

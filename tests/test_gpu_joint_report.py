@@ -3,47 +3,18 @@ _joint_summary; solver2d_amd/csrc/joint_report.hip) against its numpy statement 
 tests/world_chain.py, stepped in the contact and joint orders the device reports: every list, every record, every sum and the summary
 equal byte for byte, every step."""
 import ctypes
-import glob
-import os
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, contact_report_ref, joint_report_ref as ref, world_chain
-from tests.world_chain import oracle_world_step
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, download, refuses, step_both, upload
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 STEPS = 12
-
-
-def golden(name):
-    """(params, world) of tests/golden/world_<name>_step*.npz"""
-    (path,) = glob.glob(os.path.join(GOLDEN, "world_%s_step*.npz" % name))
-    d = np.load(path)
-    return world_chain.params_of(d), world_chain.load_world(d)
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
-
-
-def step_both(s, params, ref_world):
-    """One s2amd_world_step and the same step of the oracle chain in the device's orders; returns the step's info."""
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
 
 
 def new_totals():
@@ -260,23 +231,17 @@ def test_flag_subsets_unknown_bits_and_timing():
                 s.world_set_joint_report(bad)
         s.world_set_joint_report(wire.JOINT_REPORT_LIMITS)
         upload(s, world)
-        for getter in (s.world_joint_limit_events, s.world_joint_summary, s.world_joint_states):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # no step has run since the flag was set
+        refuses(s, E_STATE, ("world_joint_limit_events", "world_joint_summary", "world_joint_states"))  # no step has run since the flag was set
         prev = ref.limit_mask(ref_world["joints"])
         step_both(s, params, ref_world)
         want_began, want_ended = ref.events(prev, ref_world)
         began, ended = s.world_joint_limit_events()
         assert began.tolist() == want_began.tolist() and ended.tolist() == want_ended.tolist()
         assert s.world_joint_summary().tobytes() == ref.summary(ref_world).tobytes()  # any flag will do
-        for getter in (s.world_joint_states, s.world_body_joint_sums):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_joint_states", "world_body_joint_sums"))
         # a flag set between two steps takes effect from the next step
         s.world_set_joint_report(wire.JOINT_REPORT_ALL)
-        for getter in (s.world_joint_states, s.world_body_joint_sums):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_joint_states", "world_body_joint_sums"))
         prev = ref.limit_mask(ref_world["joints"])
         step_both(s, params, ref_world)
         assert_joint_report_equals_reference(s, prev, ref_world, "all flags from the second step")
@@ -284,9 +249,7 @@ def test_flag_subsets_unknown_bits_and_timing():
         s.world_set_joint_report(wire.JOINT_REPORT_BODY_SUMS)
         step_both(s, params, ref_world)
         assert s.world_body_joint_sums().tobytes() == ref.body_sums(ref_world).tobytes()
-        for getter in (s.world_joint_states, s.world_joint_limit_events):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_joint_states", "world_joint_limit_events"))
         s.world_set_joint_report(wire.JOINT_REPORT_ALL)
         prev = ref.limit_mask(ref_world["joints"])
         step_both(s, params, ref_world)

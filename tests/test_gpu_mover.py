@@ -6,23 +6,13 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import mover_ref as ref, mover_world as mw, scene_query_world as sq, shape_cast_world as cw, world_chain
+from tests.resident import E_INVALID, E_STATE, assert_equal_bytes, download, upload
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE = -1, -4
 STEPS = 12
 f32 = np.float32
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
 
 
 def new_results(n):
@@ -42,15 +32,6 @@ def ask_raw(s, movers, planes=True):
     results, out = new_results(len(movers)), new_planes(len(movers)) if planes else None
     assert s._L.s2amd_world_move_shapes(s._h, wire.as_ptr(movers), len(movers), wire.as_ptr(results), wire.as_ptr(out) if planes else None) == 0
     return {"results": results, "planes": out.reshape(len(movers), 8)} if planes else {"results": results}
-
-
-def assert_equal_bytes(got, want, what):
-    for key in got:
-        g, w = np.ascontiguousarray(got[key]), np.ascontiguousarray(want[key])
-        assert g.dtype == w.dtype and g.shape == w.shape, "%s: %s: %r %r / %r %r" % (what, key, g.dtype, g.shape, w.dtype, w.shape)
-        if g.tobytes() != w.tobytes():
-            bad = np.nonzero((g != w).reshape(len(g), -1).any(axis=1))[0]
-            raise AssertionError("%s: %s differs at %s: got %r, want %r" % (what, key, bad[:8], g[bad[:2]], w[bad[:2]]))
 
 
 @pytest.mark.parametrize("name", mw.FIXTURES)

@@ -9,7 +9,7 @@ import pytest
 
 from solver2d_amd import hip, wire
 from tests import golden_util, oraclebind, refbind
-from tests.test_narrowphase_oracle import compare_narrowphase
+from tests.parity import compare_narrowphase
 
 pytestmark = pytest.mark.gpu
 

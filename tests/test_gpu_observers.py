@@ -11,30 +11,20 @@ import numpy as np
 import pytest
 
 from solver2d_amd import hip, synthetic, wire
-from tests import actuator_ref, body_report_ref, contact_report_ref, joint_report_ref, observer_ref as ref, ray_report_world as rw, shape_report_ref, world_chain
+from tests import actuator_ref, body_report_ref, contact_report_ref, joint_report_ref, observer_ref as ref, shape_report_ref, world_chain
 from tests import grid_report_world as gw, sensor_report_world as sw
-from tests.test_gpu_actuators import motorised
-from tests.test_gpu_grid_report import assert_report as assert_grid_report
-from tests.test_gpu_step_metrics import assert_metrics_equal_reference, download, golden, step_both, upload
-from tests.test_gpu_world_edit import assert_same_world, slots_of
+from tests.grid_report_world import assert_report as assert_grid_report
+from tests.resident import (E_CAPACITY, E_INVALID, E_STATE, assert_metrics_equal_reference, assert_same_world, down_ray, download, every_kind, motorised, packed,
+                            refuses, slots_of, step_both, upload)
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 F = np.float32
 VECTOR, STATES = wire.OBSERVATION_REPORT_VECTOR, wire.OBSERVATION_REPORT_STATES
 BOTH = VECTOR | STATES
 POINT, ROTATION, ANGLE, LINEAR, ANGULAR, REV_ANGLE, REV_SPEED, REV_IMPULSE, CONTACT, RAY, ACTION = range(1, 12)
 RELATIVE, DISABLED = wire.OBSERVER_RELATIVE, wire.OBSERVER_DISABLED
-
-
-def packed(records):
-    """(kind, target, keyword arguments) triples -> the list with channels packed in order, and the channel count"""
-    out, channel = [], 0
-    for kind, target, kw in records:
-        out.append(wire.observer(kind, target, channel, **kw))
-        channel += wire.OBSERVER_WIDTH[kind]
-    return wire.observer_list(out), channel
 
 
 def assert_states(got, want, what):
@@ -59,25 +49,6 @@ def expect(s, after, observers, history, what, sums=False, ranges=False, rays=0,
         assert_states(s.world_observer_states(), want_states, what)
     assert s.world_observer_counts().tolist() == counts.tolist(), what
     return vector, want_states, counts, frames
-
-
-def down_ray(world, body):
-    x = float(world["bodies"]["position"][body][0])
-    return rw.make_ray((x, 60.0), (x, -60.0))
-
-
-def every_kind(world):
-    """The eleven kinds on mixed24; the contact observer sits on the body the plain oracle step presses hardest"""
-    at = slots_of(world)
-    d, rev = at["dynamic"], at["revolute"]
-    probe = world_chain.copy_world(world)
-    world_chain.oracle_world_step(golden("mixed24_PGS")[0], probe)
-    sums = contact_report_ref.body_sums(probe)
-    pressed = int(d[np.argmax(sums["normalImpulse"][d])])
-    return packed([(POINT, d[0], dict(frame=d[1], local=(0.25, -0.5), gain=0.5)), (ROTATION, d[2], dict(frame=d[3])), (ANGLE, d[4], dict(frame=d[5], gain=2.0)),
-                   (LINEAR, d[6], dict(frame=d[7], flags=RELATIVE, gain=0.25, lower=-1.0, upper=1.0)), (ANGULAR, d[8], dict(frame=d[9], flags=RELATIVE, bias=0.125)),
-                   (REV_ANGLE, rev[0], dict(gain=-1.0)), (REV_SPEED, rev[1], dict(gain=0.5)), (REV_IMPULSE, rev[0], dict(gain=10.0)),
-                   (CONTACT, pressed, dict(gain=0.5, bias=0.25)), (RAY, 0, dict(gain=0.01)), (ACTION, 1, dict(bias=1.0))])
 
 
 @pytest.mark.parametrize("fast", [False, True], ids=["libs2amd", "libs2amd_fast"])
@@ -411,9 +382,7 @@ def test_errors():
         assert s.world_observations().shape == (0, 0) and len(s.world_observer_states()) == 0 and s.world_observer_counts().tolist() == [0, 0, 0, 0]
         s.world_set_observers(good, channels, 2)  # accepted before any world
         s.world_set_observation_report(BOTH)
-        for call in (s.world_observations, s.world_observer_states, s.world_observer_counts):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                call()  # no resident world
+        refuses(s, E_STATE, ("world_observations", "world_observer_states", "world_observer_counts"))  # no resident world
         upload(s, world)
         buf = s.device_alloc(4 * 2 * channels)
         try:

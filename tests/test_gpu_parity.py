@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from solver2d_amd import hip, synthetic, wire
-from tests import common, golden_util, oraclebind
+from tests import common, golden_util
+from tests.parity import gpu_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -23,60 +24,6 @@ def solver():
     s = hip.Solver(0)
     yield s
     s.close()
-
-
-def check_order_is_valid(order, offsets, contacts, bodies, colourless=False):
-    """Every active contact appears exactly once; inside one colour batch no dynamic body repeats (s2Solve_Jacobi's contact
-    pass writes no body -- solve_jacobi.c:21-132 accumulates per-constraint deltas -- so its sweep is one batch in pool
-    order and has no colours to check)."""
-    active = np.flatnonzero(contacts["pointCount"] > 0)
-    assert sorted(order.tolist()) == active.tolist()
-    assert offsets[0] == 0 and offsets[-1] == len(order)
-    if colourless:
-        return
-    movable = (bodies["invMass"] != 0) | (bodies["invI"] != 0)
-    for c in range(len(offsets) - 1):
-        ids = order[offsets[c]:offsets[c + 1]]
-        touched = np.concatenate([contacts["bodyA"][ids], contacts["bodyB"][ids]])
-        touched = touched[movable[touched]]
-        assert len(np.unique(touched)) == len(touched), "colour %d reuses a dynamic body" % c
-
-
-def gpu_vs_oracle(solver, params, pre, what):
-    got = common.copy3(pre)
-    solver.solve(params, *got)
-    order, offsets = solver.contact_order()
-    jorder, joffsets = solver.joint_order()
-    check_order_is_valid(order, offsets, pre[1], pre[0], colourless=params.solverType == wire.SOLVER_ID["Jacobi"])
-    want = common.copy3(pre)
-    oraclebind.solve(params, *want, contact_order=order, joint_order=jorder)
-    common.compare_exact(got, want, what)
-    return got
-
-
-def gpu_vs_oracle_loose(solver, params, pre, what):
-    """gpu_vs_oracle for arbitrary inputs: NaN == NaN bitwise is still required, but the colour check
-    uses the library's own notion of a writable body (rotated statics count for position solvers)."""
-    got = common.copy3(pre)
-    solver.solve(params, *got)
-    order, offsets = solver.contact_order()
-    jorder, _ = solver.joint_order()
-    active = np.flatnonzero(pre[1]["pointCount"] > 0)
-    assert sorted(order.tolist()) == active.tolist()
-    assert offsets[0] == 0 and offsets[-1] == len(order)
-    if params.solverType != wire.SOLVER_ID["Jacobi"]:
-        # no colour holds two constraints on one body its sweeps write (s2amd_get_writable_bodies: the library's own rule, which for
-        # the position passes counts a rotated static body as written -- solve_common.c:383-392)
-        writable, _cls = solver.writable_bodies(len(pre[0]))
-        a, b = pre[1]["bodyA"][order], pre[1]["bodyB"][order]
-        colour = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
-        touched = np.concatenate([a, b]).astype(np.int64)
-        keys = np.concatenate([colour, colour]).astype(np.int64)[writable[touched] != 0] * (len(pre[0]) + 1) + touched[writable[touched] != 0]
-        assert len(np.unique(keys)) == len(keys), "%s: a colour holds two constraints on one writable body" % what
-    want = common.copy3(pre)
-    oraclebind.solve(params, *want, contact_order=order, joint_order=jorder)
-    common.compare_exact(got, want, what)
-    return got
 
 
 @pytest.mark.parametrize("path", FILES, ids=[os.path.basename(p)[:-4] for p in FILES])

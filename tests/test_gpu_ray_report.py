@@ -10,38 +10,13 @@ import pytest
 
 from solver2d_amd import hip, wire
 from tests import ray_report_ref as ref, ray_report_world as rw, sensor_report_world as sw, world_chain
-from tests.world_chain import oracle_world_step
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, downloaded_world, refuses, step_both, upload
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 ALL = wire.RAY_REPORT_ALL
 DISABLED, SKIP_STATIC = wire.RAY_SENSOR_DISABLED, wire.RAY_SENSOR_SKIP_STATIC
 GETTERS = ("world_ray_states", "world_ray_ranges", "world_ray_events")
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6]))
-
-
-def step_both(s, params, ref_world):
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
-
-
-def refuses(s, code, getters=GETTERS):
-    for name in getters:
-        with pytest.raises(hip.S2AmdError, match="error %d" % code):
-            getattr(s, name)()
 
 
 def c_getters(s, count):
@@ -151,7 +126,7 @@ def test_recorded_scenes_every_step(scene, fast):
             assert s.world_ray_events().tobytes() == fx["events_%d" % k].tobytes(), what
             before = now
         if not fast:
-            world_chain.assert_device_equals_oracle(download(s, world), ref_world, scene)
+            world_chain.assert_device_equals_oracle(downloaded_world(s, world), ref_world, scene)
 
 
 def test_agreement_with_the_one_shot_call():
@@ -177,7 +152,7 @@ def test_agreement_with_the_one_shot_call():
             s.world_set_ray_sensors(rays)
             for k in range(2):
                 s.world_step(params)
-                now = download(s, world)
+                now = downloaded_world(s, world)
                 states = s.world_ray_states()
                 kept = assert_one_shot(s, now, rays, states, "%s rays, step %d" % (what, k))
                 if what == "fixed":
@@ -222,7 +197,7 @@ def run_sweep(slots, count, steps=2):
         before = ref.hits(world, rays[:8]) if ref.available() else None
         for k in range(steps):
             s.world_step(params)
-            now = download(s, world)
+            now = downloaded_world(s, world)
             if before is None:
                 before = s.world_ray_states()["shapeBefore"][:8].tolist()  # (no reference here: the structure and the one-shot call only)
             full = [before[i % 8] for i in range(count)]
@@ -279,7 +254,7 @@ def test_the_chunk_box_decides_nothing():
                 s.world_step(params)
                 states, ranges, events = s.world_ray_states(), s.world_ray_ranges(), s.world_ray_events(expected=1024)
                 if k == 0:
-                    assert_one_shot(s, download(s, world), base[order], states, "order %d" % len(answers))
+                    assert_one_shot(s, downloaded_world(s, world), base[order], states, "order %d" % len(answers))
                 undone = np.zeros(1024, dtype=wire.ray_state_dtype)
                 undone[order] = states
                 assert states["ray"].tolist() == list(range(1024))
@@ -333,7 +308,7 @@ def test_lifecycle_set_rays_uploads_flags_and_errors():
         n, out = ctypes.c_int32(-7), np.full(64, -1, dtype=np.int32)
         # no resident world
         assert L.s2amd_world_ray_events(h, wire.as_ptr(out), 4, ctypes.byref(n)) == E_STATE and n.value == -7 and (out == -1).all()
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS)
         for bad in (8, -1):
             with pytest.raises(hip.S2AmdError, match="error %d" % E_INVALID):
                 s.world_set_ray_report(bad)
@@ -351,7 +326,7 @@ def test_lifecycle_set_rays_uploads_flags_and_errors():
         wrong[0]["body"] = len(world["bodies"])
         with pytest.raises(hip.S2AmdError, match="error %d" % E_INVALID):
             s.world_set_ray_sensors(wrong)  # a body outside the resident world: refused, the old list stands
-        refuses(s, E_STATE)  # no step since the upload
+        refuses(s, E_STATE, GETTERS)  # no step since the upload
         before = fx["before"].tolist()
         step_both(s, params, ref_world)
         assert s.world_ray_events().tobytes() == fx["events_0"].tobytes()
@@ -366,13 +341,13 @@ def test_lifecycle_set_rays_uploads_flags_and_errors():
         s.world_set_ray_report(0)  # flags 0: the last report stands, as with the other reports
         assert s.world_ray_states()["shape"].tolist() == before
         s.world_set_ray_report(ALL)  # turned on again: "before" re-based, the last report void
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS)
         # a new list between steps: the caller's act raises no events, and the last step's report is void
         moved = np.concatenate([rays[::-1], rays[:3]])
         moved["p1"][moved["body"] < 0] += np.float32((0.15, -0.1))
         s.world_set_ray_sensors(moved)
-        refuses(s, E_STATE)
-        now = download(s, world)
+        refuses(s, E_STATE, GETTERS)
+        now = downloaded_world(s, world)
         shapes = ref.hits(now, moved) if ref.available() else None
         step_both(s, params, ref_world)
         if shapes is None:
@@ -382,7 +357,7 @@ def test_lifecycle_set_rays_uploads_flags_and_errors():
         before = assert_report(s, ref_world, moved, before, "the new list, step 1")
         # cleared: nothing to report, and the getters say so
         s.world_set_ray_sensors(moved[:0])
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS)
         step_both(s, params, ref_world)
         assert_report(s, ref_world, moved[:0], [], "no rays")
         s.world_set_ray_sensors(moved)
@@ -393,14 +368,14 @@ def test_lifecycle_set_rays_uploads_flags_and_errors():
         on_link = moved["body"] >= len(world2["bodies"])
         assert on_link.sum() >= 8
         upload(s, world2)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS)
         before = None
         for k in range(3):
             s.world_step(params)
             states = s.world_ray_states()
             before = states["shapeBefore"].tolist() if before is None else before
             assert (states["active"][on_link] == 0).all() and states["active"][~on_link].sum() >= 3
-            before = assert_report(s, download(s, world2), moved, before, "after the upload of another world, step %d" % k)
+            before = assert_report(s, downloaded_world(s, world2), moved, before, "after the upload of another world, step %d" % k)
 
 
 def test_a_body_freed_under_a_ray_turns_the_ray_inactive():
@@ -419,19 +394,19 @@ def test_a_body_freed_under_a_ray_turns_the_ray_inactive():
             s.world_step(params)
         states = s.world_ray_states()
         assert (states["active"][mounted] == 1).all() and (states["shape"][mounted] >= 0).all()
-        freed = download(s, world)
+        freed = downloaded_world(s, world)
         freed["bodies"]["type"][ball] = wire.BODY_FREE
         on_ball = freed["shapes"]["body"] == ball
         freed["shapes"]["type"][on_ball], freed["shapes"]["body"][on_ball] = wire.SHAPE_FREE, -1
         upload(s, freed)
-        refuses(s, E_STATE)
+        refuses(s, E_STATE, GETTERS)
         s.world_step(params)
         states, events = s.world_ray_states(), s.world_ray_events()
         idle = states[mounted]
         assert (idle["active"] == 0).all() and (idle["shape"] == -1).all() and (idle["shapeBefore"] == -1).all()
         assert idle["fraction"].tobytes() == rays["maxFraction"][mounted].tobytes() and idle["p1"].tobytes() == bytes(64) and idle["p2"].tobytes() == bytes(64)
         assert not np.isin(events["ray"], mounted).any()
-        assert_report(s, download(s, freed), rays, states["shapeBefore"].tolist(), "the ball freed")
+        assert_report(s, downloaded_world(s, freed), rays, states["shapeBefore"].tolist(), "the ball freed")
 
 
 def test_flags_zero_is_a_solver_that_never_heard_of_rays():
@@ -452,8 +427,8 @@ def test_flags_zero_is_a_solver_that_never_heard_of_rays():
             if (sa["structureBuilds"], sa["asyncBuildsAdopted"]) == (sb["structureBuilds"], sb["asyncBuildsAdopted"]):
                 assert sa["kernelLaunches"] == sb["kernelLaunches"] and sa["solveLaunches"] == sb["solveLaunches"], "step %d: %r / %r" % (step, sa, sb)
                 compared += 1
-            refuses(on, E_STATE)
-            wa, wb = download(on, world), download(off, world)
+            refuses(on, E_STATE, GETTERS)
+            wa, wb = downloaded_world(on, world), downloaded_world(off, world)
             for k in world_chain.WORLD_KEYS:
                 assert np.ascontiguousarray(wa[k]).tobytes() == np.ascontiguousarray(wb[k]).tobytes(), "step %d: %s" % (step, k)
         assert compared >= 3
@@ -494,13 +469,13 @@ def test_together_with_the_older_facilities():
         before = None
         for k in range(5):
             a.world_step(params), b.world_step(params)
-            now = download(a, world)
+            now = downloaded_world(a, world)
             states = a.world_ray_states()
             before = states["shapeBefore"].tolist() if before is None else before
             before = assert_report(a, now, rays, before, "everything on, step %d" % k, raw=k == 0)
             got, want = others(a), others(b)
             assert len(got) == len(want) and [i for i in range(len(got)) if got[i] != want[i]] == [], "step %d" % k
-            theirs = download(b, world)
+            theirs = downloaded_world(b, world)
             for key in world_chain.WORLD_KEYS:
                 assert np.ascontiguousarray(now[key]).tobytes() == np.ascontiguousarray(theirs[key]).tobytes(), "step %d: %s" % (k, key)
         assert sum(1 for x in before if x >= 0) >= 3

@@ -11,7 +11,7 @@ import pytest
 
 from solver2d_amd import wire
 from tests import common
-from tests.test_islands_dist import _free_port, _merging_script, _spare
+from tests.merging_world import _free_port, _merging_script, _spare
 
 pytestmark = pytest.mark.gpu
 

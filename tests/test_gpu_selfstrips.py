@@ -9,26 +9,9 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, oraclebind
+from tests.parity import _resident_states, resident_vs_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def resident_vs_oracle(s, params, pre, steps, what, launches=None):
-    """`steps` consecutive resident steps, every one compared with the oracle swept in the device's order; returns the final state"""
-    s.upload(*pre)
-    want = common.copy3(pre)
-    seen = []
-    for step in range(steps):
-        s.step_resident(params)
-        order, _ = s.contact_order()
-        oraclebind.solve(params, *want, contact_order=order)
-        got = common.copy3(pre)
-        s.download(*got)
-        common.compare_exact(got, want, "%s step %d" % (what, step))
-        seen.append(s.stats()["kernelLaunches"])
-    if launches is not None:
-        assert seen[1:] == [launches] * (steps - 1), seen
-    return want
 
 
 TGS = wire.StepParams.make("TGS_Soft", 1.0 / 60.0, 8, 4, True)
@@ -162,7 +145,6 @@ def test_a_dead_hand_off_under_async_drops_the_steps_behind_it():
 def test_four_hundred_one_launch_steps_against_the_multi_launch_path():
     """The hand-off buffers are cleared by the kernel itself now (no epilogue launch): 400 consecutive steps, the bits of the
     multi-launch strip path at every checkpoint."""
-    from tests.test_gpu_strips import _resident_states
     checkpoints = {2, 77, 200, 400}
     a = _resident_states(dict(ONE, persist=1), 400, checkpoints)
     b = _resident_states({"persist": 0}, 400, checkpoints)

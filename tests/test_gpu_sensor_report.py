@@ -9,30 +9,11 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import sensor_report_ref as ref, sensor_report_world as sw, world_chain
-from tests.world_chain import oracle_world_step
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, downloaded_world, refuses, step_both, upload
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
 ALL = wire.SENSOR_REPORT_ALL
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6]))
-
-
-def step_both(s, params, ref_world):
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
 
 
 def device_lists(s, world, sensors):
@@ -153,7 +134,7 @@ def test_recorded_scenes_every_step(scene, fast, list_capacity):
             before = now
         assert summed == before
         if not fast:
-            world_chain.assert_device_equals_oracle(download(s, world), ref_world, scene)
+            world_chain.assert_device_equals_oracle(downloaded_world(s, world), ref_world, scene)
 
 
 def run_sweep(slots, count, steps=2, list_capacity=256):
@@ -179,7 +160,7 @@ def run_sweep(slots, count, steps=2, list_capacity=256):
             seen["left"] += sum(len(set(b) - set(n)) for b, n in zip(before, now))
             seen["inside"] += sum(len(n) for n in now)
             before = now
-        world_chain.assert_device_equals_oracle(download(s, world), ref_world, "%d slots" % slots)
+        world_chain.assert_device_equals_oracle(downloaded_world(s, world), ref_world, "%d slots" % slots)
     return seen, before
 
 
@@ -247,9 +228,7 @@ def test_lifecycle_set_sensors_uploads_flags_and_errors():
         want_entered, want_left = ref.events(before, now, ref_world, sensors)
         entered, left = s.world_sensor_events()
         assert entered.tobytes() == want_entered.tobytes() and left.tobytes() == want_left.tobytes()
-        for getter in (s.world_sensor_inside, s.world_sensor_states):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # their flags were not set before the step
+        refuses(s, E_STATE, ("world_sensor_inside", "world_sensor_states"))  # their flags were not set before the step
         s.world_set_sensor_report(ALL)
         with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
             s.world_sensor_inside()  # a flag set between two steps takes effect from the next step
@@ -270,9 +249,7 @@ def test_lifecycle_set_sensors_uploads_flags_and_errors():
         # no getter reads lists that were never written; the next step's bytes are the same under every value
         for flags, capacity in ((0, 65536), (ALL, 1), (ALL, 65536), (0, 0), (ALL, 0)):
             s.world_set_sensor_report(flags, capacity)
-            for getter in (s.world_sensor_inside, s.world_sensor_events, s.world_sensor_states):
-                with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                    getter()
+            refuses(s, E_STATE, ("world_sensor_inside", "world_sensor_events", "world_sensor_states"))
             if flags:
                 before = now
                 step_both(s, params, ref_world)
@@ -336,10 +313,8 @@ def test_flags_zero_is_a_solver_that_never_heard_of_sensors():
             if (sa["structureBuilds"], sa["asyncBuildsAdopted"]) == (sb["structureBuilds"], sb["asyncBuildsAdopted"]):
                 assert sa["kernelLaunches"] == sb["kernelLaunches"] and sa["solveLaunches"] == sb["solveLaunches"], "step %d: %r / %r" % (step, sa, sb)
                 compared += 1
-            for getter in (on.world_sensor_inside, on.world_sensor_events, on.world_sensor_states):
-                with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                    getter()
-            wa, wb = download(on, world), download(off, world)
+            refuses(on, E_STATE, ("world_sensor_inside", "world_sensor_events", "world_sensor_states"))
+            wa, wb = downloaded_world(on, world), downloaded_world(off, world)
             for k in world_chain.WORLD_KEYS:
                 assert np.ascontiguousarray(wa[k]).tobytes() == np.ascontiguousarray(wb[k]).tobytes(), "step %d: %s" % (step, k)
         assert compared >= 3

@@ -3,48 +3,19 @@ _shape_summary; solver2d_amd/csrc/shape_report.hip) against its numpy statement 
 tests/world_chain.py, stepped in the contact and joint orders the device reports: every record, both lists and the summary equal byte
 for byte, every step."""
 import ctypes
-import glob
-import os
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
 from tests import common, contact_report_ref, joint_report_ref, shape_report_ref as ref, shape_report_world, world_chain
-from tests.world_chain import oracle_world_step
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, download, refuses, step_both, upload
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 STEPS = 12
 f32 = np.float32
-
-
-def golden(name):
-    """(params, world) of tests/golden/world_<name>_step*.npz"""
-    (path,) = glob.glob(os.path.join(GOLDEN, "world_%s_step*.npz" % name))
-    d = np.load(path)
-    return world_chain.params_of(d), world_chain.load_world(d)
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
-
-
-def step_both(s, params, ref_world):
-    """One s2amd_world_step and the same step of the oracle chain in the device's orders; returns the step's info."""
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
 
 
 def middle_third(world):
@@ -286,9 +257,7 @@ def test_flag_subsets_unknown_bits_bad_views_and_timing():
         s.world_set_shape_view(view)
         s.world_set_shape_report(wire.SHAPE_REPORT_VIEW)
         upload(s, world)
-        for getter in (s.world_shape_view_events, s.world_shape_summary, s.world_shape_draws):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # no step has run since the flag was set
+        refuses(s, E_STATE, ("world_shape_view_events", "world_shape_summary", "world_shape_draws"))  # no step has run since the flag was set
         prev = ref.in_view(ref_world, view)
         step_both(s, params, ref_world)
         want_entered, want_left = ref.events(prev, ref_world, view)
@@ -309,9 +278,7 @@ def test_flag_subsets_unknown_bits_bad_views_and_timing():
         for _ in range(3):
             step_both(s, params, ref_world)
         assert s.world_shape_summary().tobytes() == ref.summary(ref_world, view).tobytes()
-        for getter in (s.world_shape_draws, s.world_shape_view_events):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_shape_draws", "world_shape_view_events"))
         s.world_set_shape_report(wire.SHAPE_REPORT_ALL)
         prev = ref.in_view(ref_world, view)
         step_both(s, params, ref_world)

@@ -16,7 +16,7 @@ import pytest
 
 from solver2d_amd import hip, islands as isl, synthetic, wire
 from tests import common, oraclebind
-from tests.test_islands_dist import _merging_script, _spare
+from tests.merging_world import _merging_script, _spare
 
 pytestmark = pytest.mark.gpu
 

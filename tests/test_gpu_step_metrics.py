@@ -3,63 +3,19 @@ their numpy statement (tests/step_metrics_ref.py) on the oracle chain of tests/w
 device reports: after every step the record equals the statement byte for byte, after the run the history is the records in order and the
 downloaded world is the oracle's."""
 import ctypes
-import glob
-import os
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
 from tests import body_report_ref, body_report_world, common, contact_report_ref, joint_report_ref, shape_report_ref, step_metrics_ref as ref, world_chain
-from tests.test_gpu_world import _create_contacts
-from tests.world_chain import oracle_find_pairs, oracle_world_step
+from tests.resident import E_CAPACITY, E_INVALID, E_STATE, assert_metrics_equal_reference, assert_record, download, refuses, step_both, upload
+from tests.world_chain import _create_contacts, golden, oracle_find_pairs, oracle_world_step
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE, E_CAPACITY = -1, -4, -5
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ALL = wire.METRICS_ALL
 f32 = np.float32
-
-
-def golden(name):
-    """(params, world) of tests/golden/world_<name>_step*.npz"""
-    (path,) = glob.glob(os.path.join(GOLDEN, "world_%s_step*.npz" % name))
-    d = np.load(path)
-    return world_chain.params_of(d), world_chain.load_world(d)
-
-
-def upload(s, world):
-    s.world_upload(*[world[k] for k in world_chain.WORLD_KEYS])
-
-
-def download(s, world):
-    out = world_chain.copy_world(world)
-    res = s.world_download(*[out[k] for k in world_chain.WORLD_KEYS])
-    return dict(zip(world_chain.WORLD_KEYS, res[:6])), res[6]
-
-
-def step_both(s, params, ref_world):
-    """One s2amd_world_step and the same step of the oracle chain in the device's orders; returns the step's info."""
-    info = s.world_step(params)
-    order, _ = s.contact_order()
-    jorder, _ = s.joint_order()
-    oracle_world_step(params, ref_world, contact_order=order, joint_order=jorder)
-    return info
-
-
-def assert_record(got, want, what):
-    assert got.dtype == wire.step_metrics_dtype
-    if not ref.same_record(got, want):
-        bad = [n for n in got.dtype.names if np.asarray(got[n]).tobytes() != np.asarray(want[n]).tobytes()]
-        raise AssertionError("%s: the record differs in %s: %s / reference %s" % (what, bad, got, want))
-
-
-def assert_metrics_equal_reference(s, ref_world, params, flags, step, what):
-    """s2amd_world_metrics against the statement on `ref_world` (the oracle chain after the step); returns the reference record"""
-    want = ref.record(ref_world, params, flags, step)
-    assert_record(s.world_metrics(), want, what)
-    return want
 
 
 def run_chain(s, params, world, what, steps, flags=ALL):
@@ -183,9 +139,7 @@ def test_ring_wraps_restarts_and_refuses_small_buffers():
         # a step with flags 0 in the middle: nothing recorded, both getters refuse; turning the recorder on again restarts it at step 0
         s.world_set_metrics(0, 0)
         step_both(s, params, ref_world)
-        for getter in (s.world_metrics, s.world_metrics_history):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()
+        refuses(s, E_STATE, ("world_metrics", "world_metrics_history"))
         s.world_set_metrics(ALL, 5)
         assert len(s.world_metrics_history()) == 0
         with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
@@ -311,22 +265,16 @@ def test_nothing_else_moves():
 def test_errors():
     params, world = golden("mixed24_PGS")
     with hip.Solver(0) as s:
-        for getter in (s.world_metrics, s.world_metrics_history):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # no resident world
+        refuses(s, E_STATE, ("world_metrics", "world_metrics_history"))  # no resident world
         for flags, length in ((8, 4), (-1, 4), (16 | ALL, 4), (ALL, 0), (ALL, 4097), (wire.METRICS_BODIES, -1)):
             with pytest.raises(hip.S2AmdError, match="error %d" % E_INVALID):
                 s.world_set_metrics(flags, length)
         s.world_set_metrics(0, 0)      # the length is ignored with flags 0
         s.world_set_metrics(0, 99999)
         upload(s, world)
-        for getter in (s.world_metrics, s.world_metrics_history):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # the recorder is off
+        refuses(s, E_STATE, ("world_metrics", "world_metrics_history"))  # the recorder is off
         s.world_step(params)
-        for getter in (s.world_metrics, s.world_metrics_history):
-            with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
-                getter()  # the flags were 0 before the last step
+        refuses(s, E_STATE, ("world_metrics", "world_metrics_history"))  # the flags were 0 before the last step
         s.world_set_metrics(ALL, 4096)
         with pytest.raises(hip.S2AmdError, match="error %d" % E_STATE):
             s.world_metrics()  # no step since the restart

@@ -11,7 +11,7 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import common, golden_util, oraclebind
-from tests.test_gpu_parity import gpu_vs_oracle, gpu_vs_oracle_loose
+from tests.parity import _resident_states, gpu_vs_oracle, gpu_vs_oracle_loose
 
 pytestmark = pytest.mark.gpu
 
@@ -304,28 +304,6 @@ def test_manifolds_that_lose_and_regain_their_points_cost_the_host_nothing(solve
             assert st["constraintCount"] == int((state[1]["pointCount"] > 0).sum())
             if step >= 2:  # (the first flip leaves the all-two-points kernel variant: one new launch sequence, seen, captured, replayed)
                 assert st["graphReplayed"] == 1, st
-
-
-def _resident_states(options, steps, checkpoints, base=120, concurrent=None):
-    """Body arrays of a resident base-`base` pyramid after every checkpoint step under `options`."""
-    pre = synthetic.pyramid(base)
-    params = wire.StepParams.make("TGS_Soft", 1.0 / 60.0, 8, 4, True)
-    out = []
-    with hip.Solver(0) as s:
-        for k, v in options.items():
-            s.set_option(k, v)
-        s.set_option("strip_patience", 0)
-        s.upload(*pre)
-        for step in range(1, steps + 1):
-            s.step_resident(params)
-            if concurrent is not None:
-                concurrent()
-            if step in checkpoints:
-                b, c, _j = common.copy3(pre)
-                s.download(b, c, _j)
-                out.append((b.copy(), c["points"].copy()))
-        assert s.stats()["persistent"] == options.get("persist", 1)
-    return out
 
 
 def test_persistent_hand_offs_hold_over_hundreds_of_steps():

@@ -10,6 +10,7 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import world_chain
+from tests.world_chain import _create_contacts
 
 pytestmark = pytest.mark.gpu
 
@@ -128,32 +129,6 @@ def test_world_api_state_errors():
         s.upload(world["bodies"], world["contacts"], world["joints"])
         with pytest.raises(hip.S2AmdError):
             s.world_step(params)  # plain upload: no shapes resident
-
-
-def _live_pairs(world):
-    live = world["pairs"]["shapeA"] >= 0
-    return np.stack([world["pairs"]["shapeA"][live], world["pairs"]["shapeB"][live]], axis=1).astype(np.int32)
-
-
-def _create_contacts(world, new_pairs):
-    """The caller's side of s2CreateContact (src/contact.c:137-203) for worlds of default-friction shapes: first free
-    slot, empty manifold."""
-    slots, contacts, pairs = [], [], []
-    free = np.flatnonzero(world["pairs"]["shapeA"] < 0).tolist()
-    for a, b in new_pairs.tolist():
-        k = free.pop(0)
-        c = np.zeros(1, dtype=wire.contact_dtype)[0]
-        c["bodyA"], c["bodyB"] = world["shapes"]["body"][a], world["shapes"]["body"][b]
-        c["friction"] = 0.6
-        c["constraintIndex"] = -1
-        p = np.zeros(1, dtype=wire.pair_state_dtype)[0]
-        p["shapeA"], p["shapeB"] = a, b
-        world["contacts"][k] = c
-        world["pairs"][k] = p
-        slots.append(k)
-        contacts.append(c)
-        pairs.append(p)
-    return np.array(slots, dtype=np.int32), np.array(contacts, dtype=wire.contact_dtype), np.array(pairs, dtype=wire.pair_state_dtype)
 
 
 def test_world_loop_with_pair_creation():

@@ -11,23 +11,13 @@ import pytest
 
 from solver2d_amd import hip, synthetic, wire
 from tests import body_report_ref, world_chain, world_edit_ref as ref
-from tests.test_gpu_body_report import assert_body_report_equals_reference, thresholds_of
-from tests.test_gpu_step_metrics import assert_metrics_equal_reference, download, golden, step_both, upload
+from tests.body_report_world import assert_body_report_equals_reference, thresholds_of
+from tests.resident import E_INVALID, E_STATE, OTHER_KEYS, assert_metrics_equal_reference, assert_same_world, download, slots_of, step_both, upload
+from tests.world_chain import golden
 
 pytestmark = pytest.mark.gpu
 
-E_INVALID, E_STATE = -1, -4
-OTHER_KEYS = ("contacts", "shapes", "pairs", "origins")
 STEPS = 12
-
-
-def assert_same_world(got, want, what, keys=world_chain.WORLD_KEYS):
-    for k in keys:
-        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
-        if a.tobytes() != b.tobytes():
-            bad = [n for n in a.dtype.names if a[n].tobytes() != b[n].tobytes()] if a.dtype.names else []
-            rows = np.flatnonzero([a[i].tobytes() != b[i].tobytes() for i in range(len(a))])
-            raise AssertionError("%s: %s differ in fields %s, first rows %s" % (what, k, bad, rows[:5].tolist()))
 
 
 def edit_both(s, ref_world, edits, what, want_skipped=True):
@@ -36,14 +26,6 @@ def edit_both(s, ref_world, edits, what, want_skipped=True):
     want = ref.apply(ref_world["bodies"], ref_world["joints"], edits)
     assert skipped == (want if want_skipped else None), "%s: %s edits skipped, the statement skips %d" % (what, skipped, want)
     return want
-
-
-def slots_of(world):
-    b, j = world["bodies"], world["joints"]
-    return {"free": np.flatnonzero(b["type"] == wire.BODY_FREE), "static": np.flatnonzero(b["type"] == wire.BODY_STATIC),
-            "kinematic": np.flatnonzero(b["type"] == wire.BODY_KINEMATIC), "dynamic": np.flatnonzero(b["type"] == wire.BODY_DYNAMIC),
-            "free_joint": np.flatnonzero(j["type"] == wire.JOINT_FREE), "revolute": np.flatnonzero(j["type"] == wire.JOINT_REVOLUTE),
-            "mouse": np.flatnonzero(j["type"] == wire.JOINT_MOUSE)}
 
 
 @pytest.mark.parametrize("fast", [False, True], ids=["libs2amd", "libs2amd_fast"])

@@ -2,19 +2,12 @@
 the box of the statement (tests/grid_report_ref.py), the statement against the scene queries' point probe, the fixtures
 tests/golden/grid_report/*.npz with the condition every scene must meet, the compiler's resource report of the new kernels, and the
 host side under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
-import os
-import re
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from solver2d_amd import hip, wire
-from tests import grid_report_ref as ref, grid_report_world as gw, scene_query_ref, sensor_report_world as sw, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import grid_report_ref as ref, grid_report_world as gw, hostcheck_util, scene_query_ref, sensor_report_world as sw, world_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
 CALLS = ("s2amd_world_set_grid_sensors", "s2amd_world_set_grid_report", "s2amd_world_grid_categories", "s2amd_world_grid_shapes",
          "s2amd_world_grid_occupancy", "s2amd_world_export_grid_occupancy", "s2amd_world_grid_states")
@@ -23,46 +16,19 @@ f32 = np.float32
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
     fields = {"s2amdGridSensor": wire.grid_sensor_dtype, "s2amdGridState": wire.grid_state_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in fields.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, fields)
     assert (wire.GRID_SENSOR_SIZE, wire.GRID_STATE_SIZE) == (64, 64)
 
 
 def test_header_flags_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
-    for define in ("#define S2AMD_MAX_GRID_SENSORS 1024", "#define S2AMD_MAX_GRID_SIDE 256", "#define S2AMD_MAX_GRID_CELLS 1048576",
-                   "#define S2AMD_GRID_SENSOR_DISABLED 1", "#define S2AMD_GRID_SENSOR_SKIP_STATIC 2", "#define S2AMD_GRID_REPORT_CATEGORIES 1",
-                   "#define S2AMD_GRID_REPORT_SHAPES 2", "#define S2AMD_GRID_REPORT_OCCUPANCY 4", "#define S2AMD_GRID_REPORT_STATES 8",
-                   "#define S2AMD_API_VERSION 5"):
-        assert re.search(re.escape(define).replace(r"\ ", r"\s+") + r"\b", header), define
+    defines = {"S2AMD_MAX_GRID_SENSORS": 1024, "S2AMD_MAX_GRID_SIDE": 256, "S2AMD_MAX_GRID_CELLS": 1048576, "S2AMD_GRID_SENSOR_DISABLED": 1,
+               "S2AMD_GRID_SENSOR_SKIP_STATIC": 2, "S2AMD_GRID_REPORT_CATEGORIES": 1, "S2AMD_GRID_REPORT_SHAPES": 2, "S2AMD_GRID_REPORT_OCCUPANCY": 4,
+               "S2AMD_GRID_REPORT_STATES": 8, "S2AMD_API_VERSION": 5}
+    hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_GRID_SENSORS, wire.MAX_GRID_SIDE, wire.MAX_GRID_CELLS) == (1024, 256, 1048576)
     assert (wire.GRID_SENSOR_DISABLED, wire.GRID_SENSOR_SKIP_STATIC) == (1, 2)
     assert (wire.GRID_REPORT_CATEGORIES, wire.GRID_REPORT_SHAPES, wire.GRID_REPORT_OCCUPANCY, wire.GRID_REPORT_STATES, wire.GRID_REPORT_ALL) == (1, 2, 4, 8, 15)
     assert wire.API_VERSION == 5 and wire.RAY_REPORT_ALL == 7 and wire.MAX_RAY_SENSORS == 16384  # the other flag spaces and the API version are untouched
-    for method in ("world_set_grid_sensors", "world_set_grid_report", "world_grid_categories", "world_grid_shapes", "world_grid_occupancy",
-                   "world_export_grid_occupancy", "world_grid_states"):
-        assert callable(getattr(hip.Solver, method))
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 def test_cell_point_formula_by_hand():
@@ -180,40 +146,15 @@ def test_displacements_are_what_they_say():
 def test_kernels_use_no_scratch():
     """hipcc's own report for grid_report.hip (make resources-grid-report), through tools/kernel_resources.py: every kernel of the file is
     there, none has a private frame or spills"""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-grid-report"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_grid_report.txt"))
-    for kernel in ("gridPoseKernel", "gridCandidatesKernel", "gridRasterKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r
-    for r in rows:
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
+    kernels = dict.fromkeys(("gridPoseKernel", "gridCandidatesKernel", "gridRasterKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-grid-report", "resources_grid_report.txt", kernels, floor=4, every_row=True)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_grid_report_host_code_under_asan_and_ubsan(tmp_path):
     """The setter with good and bad lists -> every flag combination 0..15 -> every getter (the device export among them) with too-small,
     exact and ample heap buffers of exactly the size passed -> the list replaced and cleared between steps -> uploads with other
     capacities, worlds without shape slots among them -> destroy, for 0, 1, 257 and 1,024 grids, a list at exactly S2AMD_MAX_GRID_CELLS
     and one a cell over, on the sanitizer build of tests/test_hostcheck.py (kernels never run there: what is checked is that the host
     code touches only memory it owns)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "grid_report_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "grid_report_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "GRID REPORT MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "grid_report_main.cpp", "GRID REPORT MAIN OK", timeout=600)

@@ -6,30 +6,23 @@ import subprocess
 import sys
 
 import numpy as np
-import pytest
 
-from solver2d_amd import hip, wire
-from tests import joint_report_ref as ref
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import hostcheck_util, joint_report_ref as ref
+from tests.hostcheck_util import HOSTCHECK, asan_runtime as _asan_runtime
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
 
 def test_joint_report_struct_sizes_match_header(tmp_path):
-    src = tmp_path / "sz.c"
-    src.write_text('#include "solver2d_amd.h"\n#include <stdio.h>\nint main(){printf("%zu %zu %zu\\n",'
-                   'sizeof(s2amdJointState),sizeof(s2amdBodyJointSum),sizeof(s2amdJointSummary));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert sizes == [wire.joint_state_dtype.itemsize, wire.body_joint_sum_dtype.itemsize, wire.joint_summary_dtype.itemsize] == [64, 16, 32]
+    hostcheck_util.assert_struct_layout(tmp_path, {"s2amdJointState": wire.joint_state_dtype, "s2amdBodyJointSum": wire.body_joint_sum_dtype,
+                                                   "s2amdJointSummary": wire.joint_summary_dtype})
+    assert [wire.joint_state_dtype.itemsize, wire.body_joint_sum_dtype.itemsize, wire.joint_summary_dtype.itemsize] == [64, 16, 32]
 
 
 def test_joint_report_exports_and_flags():
-    for name in ("s2amd_world_set_joint_report", "s2amd_world_joint_states", "s2amd_world_joint_limit_events", "s2amd_world_body_joint_sums",
-                 "s2amd_world_joint_summary"):
-        assert name in hip.EXPORTS
+    hostcheck_util.assert_header_and_bindings(("s2amd_world_set_joint_report", "s2amd_world_joint_states", "s2amd_world_joint_limit_events",
+                                               "s2amd_world_body_joint_sums", "s2amd_world_joint_summary"))
     assert (wire.JOINT_REPORT_STATES, wire.JOINT_REPORT_LIMITS, wire.JOINT_REPORT_BODY_SUMS, wire.JOINT_REPORT_ALL) == (1, 2, 4, 7)
     assert wire.REPORT_ALL == 7 and wire.API_VERSION == 5  # the contact report's flag space and the API version are untouched
 
@@ -122,7 +115,7 @@ def test_limits_need_the_flag_and_the_gap_its_rules():
     assert (int(m["liveJoints"]), int(m["revoluteJoints"]), int(m["maxGapSlot"]), float(m["maxGapSquared"])) == (1, 0, -1, -1.0)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_joint_report_host_code_under_asan_and_ubsan():
     """upload -> set_joint_report(all) -> step -> the four getters -> capacity errors -> upload again, on the sanitizer build of
     tests/test_hostcheck.py (kernels never run there: what is checked is that the host code touches only memory it owns)."""

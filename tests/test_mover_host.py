@@ -3,14 +3,12 @@
 sampled geometry, the fixtures tests/golden/mover/*.npz, and the compiler's resource report of the new kernels."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import mover_ref as ref, mover_world as mw, proximity_ref as pref, scene_query_world as sq, shape_cast_ref as cref, shape_cast_world as cw
+from tests import hostcheck_util, mover_ref as ref, mover_world as mw, proximity_ref as pref, scene_query_world as sq, shape_cast_ref as cref, shape_cast_world as cw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
@@ -332,18 +330,7 @@ def test_the_statement_against_sampled_geometry(name):
 def test_the_new_kernels_use_no_scratch():
     """hipcc's own report for mover_query.hip (make resources-mover), through tools/kernel_resources.py: every kernel of the file is
     there, none has a private frame or a spill, and the candidates pass keeps four waves a SIMD beside its 40 KiB of LDS"""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-mover"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_mover_query.txt"))
-    for kernel in ("moverInitKernel", "moverCandidatesKernel", "moverAdvanceKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r
-    for r in rows:
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-    asm = open(os.path.join(csrc, "build", "asm_mover_query.s")).read()
+    kernels = dict.fromkeys(("moverInitKernel", "moverCandidatesKernel", "moverAdvanceKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-mover", "resources_mover_query.txt", kernels, floor=4, every_row=True)
+    asm = open(os.path.join(hostcheck_util.CSRC, "build", "asm_mover_query.s")).read()
     assert "atomic_umin_x2" in asm and not re.search(r"atomic_f?(add|min|max)_f", asm)  # the 64-bit integer minimum and no float atomic

@@ -3,19 +3,13 @@
 through, every status in the stated priority order --, the history rule over a re-base, the setter's validation cases as data, the
 compiler's resource report of the new kernel, and the host side under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a
 stand-alone program, nothing preloaded)."""
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
-from solver2d_amd import hip, wire
-from tests import observer_ref as ref
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import hostcheck_util, observer_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("s2amd_world_set_observers", "s2amd_world_set_observation_report", "s2amd_world_observations", "s2amd_world_export_observations",
          "s2amd_world_export_observations_async", "s2amd_world_observer_states", "s2amd_world_observer_counts")
 F = np.float32
@@ -24,29 +18,11 @@ INF = F(np.inf)
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
     records = {"s2amdObserver": wire.observer_dtype, "s2amdObserverState": wire.observer_state_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in records.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, records)
     assert (wire.OBSERVER_SIZE, wire.OBSERVER_STATE_SIZE) == (64, 32)
 
 
 def test_header_defines_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
     defines = {"S2AMD_MAX_OBSERVERS": wire.MAX_OBSERVERS, "S2AMD_MAX_OBSERVATION_CHANNELS": wire.MAX_OBSERVATION_CHANNELS,
                "S2AMD_MAX_OBSERVATION_FRAMES": wire.MAX_OBSERVATION_FRAMES, "S2AMD_OBSERVER_BODY_POINT": ref.POINT,
                "S2AMD_OBSERVER_BODY_ROTATION": ref.ROTATION, "S2AMD_OBSERVER_BODY_ANGLE": ref.ANGLE, "S2AMD_OBSERVER_BODY_LINEAR_VELOCITY": ref.LINEAR,
@@ -58,21 +34,12 @@ def test_header_defines_and_bindings():
                "S2AMD_OBSERVER_STATUS_SKIPPED": ref.SKIPPED, "S2AMD_OBSERVER_STATUS_SOURCE_OFF": ref.SOURCE_OFF,
                "S2AMD_OBSERVATION_REPORT_VECTOR": wire.OBSERVATION_REPORT_VECTOR, "S2AMD_OBSERVATION_REPORT_STATES": wire.OBSERVATION_REPORT_STATES,
                "S2AMD_API_VERSION": 5}
-    for name, value in defines.items():
-        assert re.search(r"#define\s+%s\s+%d\b" % (name, value), header), name
+    header = hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_OBSERVERS, wire.MAX_OBSERVATION_CHANNELS, wire.MAX_OBSERVATION_FRAMES, wire.API_VERSION) == (16384, 65536, 16, 5)
     assert wire.OBSERVER_WIDTH == {1: 2, 2: 2, 3: 1, 4: 2, 5: 1, 6: 1, 7: 1, 8: 1, 9: 2, 10: 1, 11: 1}
     assert (wire.OBSERVER_BODY_POINT, wire.OBSERVER_ACTION, wire.OBSERVER_STATUS_SOURCE_OFF) == (ref.POINT, ref.ACTION, ref.SOURCE_OFF)
-    for method in ("world_set_observers", "world_set_observation_report", "world_observations", "world_export_observations",
-                   "world_export_observations_async", "world_observer_states", "world_observer_counts"):
-        assert callable(getattr(hip.Solver, method))
     # the actuators' note on how observations leave names the new export
     assert re.search(r"observations leave device to device \(s2amd_world_export_observations,", header)
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 # ---- the statement on hand-made cases ----
@@ -254,21 +221,11 @@ def test_validation_rules_of_the_statement():
 def test_kernels_use_no_scratch():
     """hipcc's own report for observers.hip (make resources-observers), through tools/kernel_resources.py: the kernel of the file is
     there, it has no private frame, spills nothing and uses no LDS."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-observers"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_observers.txt"))
-    for kernel in ("observeKernel", "reportBodyRangesKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r
-    assert len([r for r in rows if "Kernel" in r["mangled"]]) == 2
+    kernels = dict.fromkeys(("observeKernel", "reportBodyRangesKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-observers", "resources_observers.txt", kernels, floor=4, total=2)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_observer_host_code_under_asan_and_ubsan(tmp_path):
     """Every validation rule, the overlap check included, with and without a world and a list, each leaving the old list, its sizes, its
     ring's head and its answers standing -> the list held across uploads -> the ring's head over more steps than frames -> the host
@@ -276,18 +233,4 @@ def test_observer_host_code_under_asan_and_ubsan(tmp_path):
     16 once), across re-bases by upload, replacement and flags and across steps with the flags at 0 -> the getters with too-small and
     exact heap buffers -> destroy, for 0, 1, 65, 257, 1,000 and 16,384 observers, on the sanitizer build of tests/test_hostcheck.py
     (kernels never run there: the program plays the kernel's one write into the row the host chose)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "observers_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "observers_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "OBSERVERS MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "observers_main.cpp", "OBSERVERS MAIN OK", timeout=600)

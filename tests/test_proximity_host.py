@@ -3,14 +3,12 @@ s2ShapeDistance as the statement (tests/proximity_ref.py) calls it pinned to thr
 tests/golden/proximity/*.npz, and the compiler's resource report of the new kernels."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import proximity_ref as ref, proximity_world as pw, scene_query_world as sq
+from tests import hostcheck_util, proximity_ref as ref, proximity_world as pw, scene_query_world as sq
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
@@ -141,16 +139,7 @@ def test_the_statement_refuses_what_the_library_refuses():
 def test_the_new_kernels_use_no_scratch():
     """hipcc's own report for proximity_query.hip (`make resources` compiles it with the files tests/test_kernel_resources.py reads),
     through tools/kernel_resources.py: every kernel of the file is there, none has a private frame or a spill."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-j4", "-C", csrc, "resources"])
-    rows = kernel_resources.parse()
     # (the kernels live in an unnamed namespace: told by their mangled names)
-    for kernel, copies in (("proximityCandidatesKernelILb0E", 1), ("proximityCandidatesKernelILb1E", 1), ("proximityFinishKernel", 1),
-                           ("proximityDistancesKernel", 1), ("listTilePrefixKernel", 1), ("listOffsetsKernel", 1), ("listWriteKernel", 1)):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == copies, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]][-12:])
-        for r in found:
-            assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-            assert r["Occupancy"] >= 3, r  # (the candidate pass: 44 KiB of LDS a workgroup, three workgroups a CU)
+    kernels = {"proximityCandidatesKernelILb0E": 1, "proximityCandidatesKernelILb1E": 1, "proximityFinishKernel": 1, "proximityDistancesKernel": 1,
+               "listTilePrefixKernel": 1, "listOffsetsKernel": 1, "listWriteKernel": 1}
+    hostcheck_util.assert_kernel_resources("resources", None, kernels, floor=3)  # (the candidate pass: 44 KiB of LDS a workgroup, three workgroups a CU)

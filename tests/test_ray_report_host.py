@@ -3,19 +3,13 @@
 every scene must meet, the compiler's resource report of the new kernels, and the host side under ASan + UBSan on the stand-in HIP
 runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
 import ctypes
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from solver2d_amd import hip, wire
-from tests import proximity_ref, ray_report_ref as ref, ray_report_world as rw, scene_query_ref, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import hostcheck_util, proximity_ref, ray_report_ref as ref, ray_report_world as rw, scene_query_ref, world_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
 CALLS = ("s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
          "s2amd_world_ray_events")
@@ -24,42 +18,17 @@ f32 = np.float32
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
     fields = {"s2amdRaySensor": wire.ray_sensor_dtype, "s2amdRayState": wire.ray_state_dtype, "s2amdRayEvent": wire.ray_event_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in fields.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, fields)
     assert (wire.RAY_SENSOR_SIZE, wire.RAY_STATE_SIZE, wire.RAY_EVENT_SIZE) == (48, 64, 16)
 
 
 def test_header_flags_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
-    for define in ("#define S2AMD_MAX_RAY_SENSORS 16384", "#define S2AMD_RAY_SENSOR_DISABLED 1", "#define S2AMD_RAY_SENSOR_SKIP_STATIC 2",
-                   "#define S2AMD_RAY_REPORT_STATES 1", "#define S2AMD_RAY_REPORT_RANGES 2", "#define S2AMD_RAY_REPORT_EVENTS 4", "#define S2AMD_API_VERSION 5"):
-        assert define in header, define
+    defines = {"S2AMD_MAX_RAY_SENSORS": 16384, "S2AMD_RAY_SENSOR_DISABLED": 1, "S2AMD_RAY_SENSOR_SKIP_STATIC": 2, "S2AMD_RAY_REPORT_STATES": 1,
+               "S2AMD_RAY_REPORT_RANGES": 2, "S2AMD_RAY_REPORT_EVENTS": 4, "S2AMD_API_VERSION": 5}
+    hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_RAY_SENSORS, wire.RAY_SENSOR_DISABLED, wire.RAY_SENSOR_SKIP_STATIC) == (16384, 1, 2)
     assert (wire.RAY_REPORT_STATES, wire.RAY_REPORT_RANGES, wire.RAY_REPORT_EVENTS, wire.RAY_REPORT_ALL) == (1, 2, 4, 7)
     assert wire.API_VERSION == 5 and wire.SENSOR_REPORT_ALL == 7 and wire.MAX_SENSORS == 1024  # the other flag spaces and the API version are untouched
-    for method in ("world_set_ray_sensors", "world_set_ray_report", "world_ray_states", "world_ray_ranges", "world_export_ray_ranges", "world_ray_events"):
-        assert callable(getattr(hip.Solver, method))
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 def test_transform_point_by_hand():
@@ -183,40 +152,15 @@ def test_clearance_variations_are_what_they_say():
 def test_kernels_use_no_scratch():
     """hipcc's own report for ray_report.hip (make resources-ray-report), through tools/kernel_resources.py: every kernel of the file is
     there, none has a private frame or spills, and the candidates pass keeps three workgroups a CU beside its 44 KiB of LDS."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-ray-report"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_ray_report.txt"))
-    for kernel in ("rayPoseKernel", "rayReportCandidatesKernel", "rayReportFinishKernelILb0E", "rayReportFinishKernelILb1E", "rayReportEventsKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 3, r
-    for r in rows:
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
+    kernels = dict.fromkeys(("rayPoseKernel", "rayReportCandidatesKernel", "rayReportFinishKernelILb0E", "rayReportFinishKernelILb1E", "rayReportEventsKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-ray-report", "resources_ray_report.txt", kernels, floor=3, every_row=True)
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_ray_report_host_code_under_asan_and_ubsan(tmp_path):
     """The setter with good and bad lists -> every flag combination 0..7 -> every getter (the device export among them) with too-small,
     exact and ample heap buffers of exactly the size passed -> the list replaced and cleared between steps -> uploads with other
     capacities, worlds without shape slots among them -> destroy, for 0, 1, 257 and 16,384 rays, on the sanitizer build of
     tests/test_hostcheck.py (kernels never run there: the program writes the head through the report state's head offset, and what is
     checked is that the host code touches only memory it owns)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "ray_report_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "ray_report_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "RAY REPORT MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "ray_report_main.cpp", "RAY REPORT MAIN OK", timeout=600)

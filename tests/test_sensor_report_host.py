@@ -2,19 +2,12 @@
 (tests/sensor_report_ref.py) against the proximity queries' statement under the composed transform, the fixtures
 tests/golden/sensor_report/*.npz with the condition every scene must meet, the compiler's resource report of the new kernels, and the
 host side under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded)."""
-import os
-import re
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from solver2d_amd import hip, wire
-from tests import proximity_ref, sensor_report_ref as ref, sensor_report_world as sw, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from solver2d_amd import wire
+from tests import hostcheck_util, proximity_ref, sensor_report_ref as ref, sensor_report_world as sw, world_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
 CALLS = ("s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states")
 f32 = np.float32
@@ -22,42 +15,17 @@ f32 = np.float32
 
 def test_struct_sizes_and_offsets_match_the_header(tmp_path):
     fields = {"s2amdSensor": wire.sensor_dtype, "s2amdSensorEvent": wire.sensor_event_dtype, "s2amdSensorState": wire.sensor_state_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in fields.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, fields)
     assert (wire.SENSOR_SIZE, wire.SENSOR_EVENT_SIZE, wire.SENSOR_STATE_SIZE) == (112, 16, 64)
 
 
 def test_header_flags_and_bindings():
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for call in CALLS:
-        assert re.search(r"\bint %s\(s2amdSolver\*" % call, header), call
-        assert call in hip.EXPORTS
-    for define in ("#define S2AMD_MAX_SENSORS 1024", "#define S2AMD_SENSOR_DISABLED 1", "#define S2AMD_SENSOR_SKIP_STATIC 2", "#define S2AMD_SENSOR_REPORT_INSIDE 1",
-                   "#define S2AMD_SENSOR_REPORT_EVENTS 2", "#define S2AMD_SENSOR_REPORT_STATES 4", "#define S2AMD_API_VERSION 5"):
-        assert define in header, define
+    defines = {"S2AMD_MAX_SENSORS": 1024, "S2AMD_SENSOR_DISABLED": 1, "S2AMD_SENSOR_SKIP_STATIC": 2, "S2AMD_SENSOR_REPORT_INSIDE": 1,
+               "S2AMD_SENSOR_REPORT_EVENTS": 2, "S2AMD_SENSOR_REPORT_STATES": 4, "S2AMD_API_VERSION": 5}
+    hostcheck_util.assert_header_and_bindings(CALLS, defines, methods=True, argtypes=True)
     assert (wire.MAX_SENSORS, wire.SENSOR_DISABLED, wire.SENSOR_SKIP_STATIC) == (1024, 1, 2)
     assert (wire.SENSOR_REPORT_INSIDE, wire.SENSOR_REPORT_EVENTS, wire.SENSOR_REPORT_STATES, wire.SENSOR_REPORT_ALL) == (1, 2, 4, 7)
     assert wire.API_VERSION == 5 and wire.SHAPE_REPORT_ALL == 7  # the other flag spaces and the API version are untouched
-    for method in ("world_set_sensors", "world_set_sensor_report", "world_sensor_inside", "world_sensor_events", "world_sensor_states"):
-        assert callable(getattr(hip.Solver, method))
-    if os.path.exists(hip.LIB_PATH) and os.path.exists(hip.FAST_LIB_PATH):
-        for fast in (False, True):
-            lib = hip.load(fast=fast)
-            for call in CALLS:
-                assert getattr(lib, call).argtypes is not None, call
 
 
 def test_mul_transforms_is_the_reference_operation_order():
@@ -178,41 +146,19 @@ def test_sweep_world_is_what_it_says():
 def test_kernels_use_no_scratch():
     """hipcc's own report for sensor_report.hip (make resources-sensor-report), through tools/kernel_resources.py: every kernel of the
     file is there, none has a private frame or spills, and 48 KiB of LDS a workgroup leave the mask pass three workgroups a CU."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-sensor-report"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_sensor_report.txt"))
-    for kernel in ("sensorPoseKernel", "sensorMaskKernelILb0E", "sensorMaskKernelILb1E", "sensorPrefixKernel", "sensorOffsetsKernel", "sensorWriteKernel",
-                   "listTilePrefixKernel", "listOffsetsKernel", "listWriteKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 3, r
-        if "sensorMaskKernel" in kernel:
+    kernels = dict.fromkeys(("sensorPoseKernel", "sensorMaskKernelILb0E", "sensorMaskKernelILb1E", "sensorPrefixKernel", "sensorOffsetsKernel", "sensorWriteKernel",
+                             "listTilePrefixKernel", "listOffsetsKernel", "listWriteKernel"), 1)
+    rows = hostcheck_util.assert_kernel_resources("resources-sensor-report", "resources_sensor_report.txt", kernels, floor=3)
+    for r in rows:
+        if "sensorMaskKernel" in r["mangled"]:
             assert r["VGPRs"] <= 128, r
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_sensor_report_host_code_under_asan_and_ubsan(tmp_path):
     """The setter with good and bad lists -> every flag combination 0..7 with listCapacity 0, 16 and ample -> every getter with
     too-small, exact and ample heap buffers of exactly the size passed, lists in the block and rebuilt by the getter -> the list replaced
     and cleared between steps -> uploads with other capacities, worlds without shape slots among them -> destroy, for 0, 1, 257 and
     1,024 sensors, on the sanitizer build of tests/test_hostcheck.py (kernels never run there: the program writes the head through the
     report state's head offset, and what is checked is that the host code touches only memory it owns)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "sensor_report_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "sensor_report_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "SENSOR REPORT MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "sensor_report_main.cpp", "SENSOR REPORT MAIN OK", timeout=600)

@@ -3,14 +3,12 @@
 geometry, the fixtures tests/golden/shape_cast/*.npz, and the compiler's resource report of the new kernels."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import proximity_ref as pref, scene_query_world as sq, shape_cast_ref as ref, shape_cast_world as cw
+from tests import hostcheck_util, proximity_ref as pref, scene_query_world as sq, shape_cast_ref as ref, shape_cast_world as cw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not ref.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
@@ -188,16 +186,7 @@ def test_the_statement_refuses_what_the_library_refuses():
 def test_the_new_kernels_use_no_scratch():
     """hipcc's own report for shape_cast.hip (make resources-shape-cast), through tools/kernel_resources.py: every kernel of the file is
     there, none has a private frame or a spill, and 48 KiB of LDS a workgroup leave the candidate pass three workgroups a CU."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-shape-cast"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_shape_cast.txt"))
     # (the kernels live in an unnamed namespace: told by their mangled names)
-    for kernel in ("castCandidatesKernelILb0E", "castCandidatesKernelILb1E", "castFinishKernel", "castRecordsKernel", "listTilePrefixKernel",
-                   "listOffsetsKernel", "listWriteKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 3, r
+    kernels = dict.fromkeys(("castCandidatesKernelILb0E", "castCandidatesKernelILb1E", "castFinishKernel", "castRecordsKernel", "listTilePrefixKernel",
+                             "listOffsetsKernel", "listWriteKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-shape-cast", "resources_shape_cast.txt", kernels, floor=3)

@@ -4,37 +4,19 @@ the values written out here, the synthetic world of the GPU test has on the CPU 
 side of the report runs clean under ASan + UBSan on the stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing
 preloaded)."""
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from solver2d_amd import hip, wire
-from tests import common, shape_report_ref as ref, shape_report_world, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from tests import common, hostcheck_util, shape_report_ref as ref, shape_report_world, world_chain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 INF = float("inf")
 
 
 def test_shape_report_struct_sizes_and_offsets_match_header(tmp_path):
     fields = {"s2amdShapeDraw": wire.shape_draw_dtype, "s2amdShapeSummary": wire.shape_summary_dtype}
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){"]
-    want = []
-    for struct, dtype in fields.items():
-        lines.append('printf("%%zu\\n", sizeof(%s));' % struct)
-        want.append(dtype.itemsize)
-        for name in dtype.names:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (struct, name))
-            want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, fields)
     assert (wire.shape_draw_dtype.itemsize, wire.shape_summary_dtype.itemsize) == (128, 64)
     assert wire.shape_draw_dtype.fields["vertices"][1] == 32 and wire.shape_draw_dtype.fields["aabb"][1] == 96
     assert wire.shape_summary_dtype.fields["movableBounds"][1] == 32
@@ -43,13 +25,9 @@ def test_shape_report_struct_sizes_and_offsets_match_header(tmp_path):
 def test_shape_report_exports_and_flags():
     names = ("s2amd_world_set_shape_report", "s2amd_world_set_shape_view", "s2amd_world_shape_draws", "s2amd_world_shape_view_events",
              "s2amd_world_shape_summary")
-    for name in names:
-        assert name in hip.EXPORTS
     assert (wire.SHAPE_REPORT_DRAW, wire.SHAPE_REPORT_VIEW, wire.SHAPE_REPORT_BOUNDS, wire.SHAPE_REPORT_ALL) == (1, 2, 4, 7)
     assert wire.REPORT_ALL == 7 and wire.JOINT_REPORT_ALL == 7 and wire.API_VERSION == 5  # the other flag spaces and the API version are untouched
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for define in ("#define S2AMD_SHAPE_REPORT_DRAW 1", "#define S2AMD_SHAPE_REPORT_VIEW 2", "#define S2AMD_SHAPE_REPORT_BOUNDS 4"):
-        assert define in header
+    hostcheck_util.assert_header_and_bindings(names, {"S2AMD_SHAPE_REPORT_DRAW": 1, "S2AMD_SHAPE_REPORT_VIEW": 2, "S2AMD_SHAPE_REPORT_BOUNDS": 4})
     if os.path.exists(hip.LIB_PATH):
         # (the built library: every function is there to be called)
         lib = hip.load()
@@ -174,23 +152,9 @@ def test_synthetic_world_has_the_events_the_gpu_test_needs():
     assert np.isfinite(world["bodies"]["position"]).all()
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_shape_report_host_code_under_asan_and_ubsan(tmp_path):
     """tests/hostcheck/shape_report_main.cpp, a program of its own: upload -> every flag combination -> a view set, changed and cleared ->
     every getter with too-small, exact and ample buffers -> uploads with other capacities -> destroy, on the sanitizer build of
     tests/test_hostcheck.py (kernels never run there: what is checked is that the host code touches only memory it owns)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "shape_report_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "shape_report_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "SHAPE REPORT MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "shape_report_main.cpp", "SHAPE REPORT MAIN OK", timeout=600)

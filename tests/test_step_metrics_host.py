@@ -3,20 +3,15 @@ reference statement the GPU tests compare against (tests/step_metrics_ref.py) gi
 values written out here, its one summation shape is pinned on a vector on which left-to-right summation gives other bits, the statement
 separates the solvers on the CPU oracle chain as the samples are meant to show, the host side runs clean under ASan + UBSan on the
 stand-in HIP runtime of tests/hostcheck (a stand-alone program, nothing preloaded), and the new kernels use no scratch."""
-import glob
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import step_metrics_ref as ref, world_chain
-from tests.test_hostcheck import HERE as HOSTCHECK, _asan_runtime
+from tests import hostcheck_util, step_metrics_ref as ref, world_chain
+from tests.world_chain import golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 f32 = np.float32
 NAMES = ("s2amd_world_set_metrics", "s2amd_world_metrics", "s2amd_world_metrics_history")
 # the golden worlds tests/test_gpu_step_metrics.py steps
@@ -24,40 +19,19 @@ GPU_WORLDS = ("far_ragdoll_pile0_PGS_Soft", "high_mass_ratio1_PGS_NGS", "tumbler
 FLOAT_SUMS = ("sumPenetration", "sumNormalImpulse", "kineticEnergy", "potentialEnergy", "momentum", "spin", "sumJointGapSquared")
 
 
-def golden(name):
-    (path,) = glob.glob(os.path.join(GOLDEN, "world_%s_step*.npz" % name))
-    d = np.load(path)
-    return world_chain.params_of(d), world_chain.load_world(d)
-
-
 def test_step_metrics_struct_size_and_offsets_match_header(tmp_path):
     dtype = wire.step_metrics_dtype
-    lines = ['#include "solver2d_amd.h"', "#include <stdio.h>", "#include <stddef.h>", "int main(){", 'printf("%zu\\n", sizeof(s2amdStepMetrics));']
-    want = [dtype.itemsize]
-    for name in dtype.names:
-        lines.append('printf("%%zu\\n", offsetof(s2amdStepMetrics, %s));' % name)
-        want.append(dtype.fields[name][1])
-    lines.append("return 0;}")
-    src = tmp_path / "sz.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got == want
+    hostcheck_util.assert_struct_layout(tmp_path, {"s2amdStepMetrics": dtype})
     assert dtype.itemsize == 128 and len(dtype.names) == 24
     assert [dtype.fields[n][1] for n in ("touchingContacts", "minGap", "sumPenetration", "energyBodies", "potentialEnergy", "momentum", "spin",
                                          "revoluteJoints", "sumJointGapSquared", "pad")] == [16, 32, 48, 56, 64, 68, 76, 80, 92, 96]
 
 
 def test_step_metrics_exports_and_flags():
-    for name in NAMES:
-        assert name in hip.EXPORTS
+    hostcheck_util.assert_header_and_bindings(NAMES, {"S2AMD_METRICS_CONTACTS": 1, "S2AMD_METRICS_BODIES": 2, "S2AMD_METRICS_JOINTS": 4, "S2AMD_API_VERSION": 5})
     assert (wire.METRICS_CONTACTS, wire.METRICS_BODIES, wire.METRICS_JOINTS, wire.METRICS_ALL, wire.METRICS_MAX_HISTORY) == (1, 2, 4, 7, 4096)
     # the four reports' flag spaces and the API version are untouched
     assert wire.REPORT_ALL == 7 and wire.JOINT_REPORT_ALL == 7 and wire.SHAPE_REPORT_ALL == 7 and wire.BODY_REPORT_ALL == 15 and wire.API_VERSION == 5
-    header = open(os.path.join(ROOT, "include", "solver2d_amd.h")).read()
-    for define in ("#define S2AMD_METRICS_CONTACTS 1", "#define S2AMD_METRICS_BODIES 2", "#define S2AMD_METRICS_JOINTS 4", "#define S2AMD_API_VERSION 5"):
-        assert define in header
     if os.path.exists(hip.LIB_PATH):
         lib = hip.load()
         for name in NAMES:
@@ -217,43 +191,19 @@ def test_all_sums_are_finite_on_the_worlds_used(name):
         assert int(r["energyBodies"]) > 0
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
+@hostcheck_util.needs_sanitizers
 def test_step_metrics_host_code_under_asan_and_ubsan(tmp_path):
     """tests/hostcheck/step_metrics_main.cpp, a program of its own: every flag combination -> lengths 1, 5 and 4096 -> more steps than the
     ring holds -> both getters with too-small, exact and ample buffers -> restarts by the setter and by an upload -> uploads with other
     capacities -> destroy, on the sanitizer build of tests/test_hostcheck.py (kernels never run there: what is checked is that the host
     code, the wrap split of the history copy included, touches only memory it owns)."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
-    build = os.path.join(HOSTCHECK, "_build")
-    exe = str(tmp_path / "step_metrics_main")
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-Wno-unused-function", "-Wno-unused-value",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-shared-libsan",
-                           "-x", "hip", os.path.join(HOSTCHECK, "step_metrics_main.cpp"), "-o", exe, "-L", build, "-ls2amd_hostcheck",
-                           "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(_asan_runtime())])
-    env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
-    p = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode(errors="replace")
-    assert p.returncode == 0 and "STEP METRICS MAIN OK" in out and "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    hostcheck_util.run_sanitized(tmp_path, "step_metrics_main.cpp", "STEP METRICS MAIN OK", timeout=600)
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_the_new_kernels_use_no_scratch():
     """hipcc's own report for step_metrics.hip (`make resources` compiles it with the files tests/test_kernel_resources.py reads), through
     tools/kernel_resources.py: both kernels are there, neither has a private frame."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    report = os.path.join(csrc, "build", "resources_step_metrics.txt")
-    subprocess.check_call(["make", "-s", "-C", csrc, report])
-    rows = kernel_resources.parse(report)
-    for kernel in ("metricsGatherKernel", "metricsFinishKernel"):
-        # (the kernels live in an unnamed namespace: told by their mangled names)
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, [r["mangled"] for r in rows]
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r  # (nothing here needs many registers: 256 threads, a few dozen VGPRs)
+    # (the kernels live in an unnamed namespace: told by their mangled names; the report file itself is the make target)
+    kernels = {"metricsGatherKernel": 1, "metricsFinishKernel": 1}
+    hostcheck_util.assert_kernel_resources(None, "resources_step_metrics.txt", kernels, floor=4)  # (nothing here needs many registers: 256 threads, a few dozen VGPRs)

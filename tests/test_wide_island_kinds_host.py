@@ -18,10 +18,10 @@ import sys
 
 import pytest
 
+from tests import hostcheck_util
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOSTCHECK = os.path.join(ROOT, "tests", "hostcheck")
-sys.path.insert(0, ROOT)
-from tools import kernel_resources  # noqa: E402
 
 # launch.h: SOFT_TGS 0, SOFT_PGS 1, SOFT_FIXED 3 -- as the demangled names print them.  (kind, rounds) of every form that exists:
 # s2Solve_SoftStep has the six-round form only (wide_kernel.hip: wideIslandVariants)
@@ -98,8 +98,7 @@ def test_option_wide_off_keeps_the_256_thread_island_kernel(cases, world, solver
 def rows():
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("needs hipcc")
-    subprocess.check_call(["make", "-s", "-j4", "-C", os.path.join(ROOT, "solver2d_amd", "csrc"), "resources"])
-    return kernel_resources.parse()
+    return hostcheck_util.kernel_rows("resources", None)
 
 
 def test_every_form_the_island_launch_can_pick_is_register_resident(rows):

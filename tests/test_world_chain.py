@@ -10,6 +10,7 @@ import pytest
 
 from solver2d_amd import wire
 from tests import world_chain
+from tests.world_chain import _create_contacts
 
 # "_k0" fixtures are inputs only (for the GPU loop tests): nothing to replay here
 FILES = [f for f in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "world_*.npz"))) if not f.endswith("_k0.npz")]
@@ -41,7 +42,6 @@ def test_fuzz_world_generators_run_through_the_oracle_chain():
     finite, and creates and destroys contacts (so the GPU tests that use them do compare something)."""
     from solver2d_amd import wire
     from tests import oraclebind, world_chain
-    from tests.test_gpu_world import _create_contacts, _live_pairs
 
     def loop(world, steps):
         params = wire.StepParams.make("TGS_Soft", 1.0 / 60.0, 8, 4, True)

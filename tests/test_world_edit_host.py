@@ -3,14 +3,12 @@
 the statement's skip rules on synthetic records, and the compiler's resource report of the new kernels."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from solver2d_amd import hip, wire
-from tests import refbind, world_edit_ref as ref, world_edit_world as ew
+from tests import hostcheck_util, refbind, world_edit_ref as ref, world_edit_world as ew
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_reference = pytest.mark.skipif(not refbind.available(), reason="oracle/_ref/libs2ref.so (the compiled reference) is absent")
@@ -167,14 +165,5 @@ def test_statement_equals_the_fixtures(name):
 def test_the_new_kernels_use_no_scratch():
     """hipcc's own report for world_edit.hip (make resources-world-edit), through tools/kernel_resources.py: the file's three kernels are
     there, none has a private frame or spills a register."""
-    sys.path.insert(0, ROOT)
-    from tools import kernel_resources
-    csrc = os.path.join(ROOT, "solver2d_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", csrc, "resources-world-edit"])
-    rows = kernel_resources.parse(os.path.join(csrc, "build", "resources_world_edit.txt"))
-    for kernel in ("editDistinctKernel", "editKeysKernel", "editWalkKernel"):
-        found = [r for r in rows if kernel in r["mangled"]]
-        assert len(found) == 1, (kernel, [r["mangled"] for r in rows if "Kernel" in r["mangled"]])
-        r = found[0]
-        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
-        assert r["Occupancy"] >= 4, r
+    kernels = dict.fromkeys(("editDistinctKernel", "editKeysKernel", "editWalkKernel"), 1)
+    hostcheck_util.assert_kernel_resources("resources-world-edit", "resources_world_edit.txt", kernels, floor=4)

@@ -1,12 +1,16 @@
 """One s2World_Step minus pair creation (stage 1) on wire arrays, through the CPU oracle:
 stage 3 update contacts (src/world.c:132-168) -> s2Solve_* (src/world.c:206-256) -> stage 4 refit (src/world.c:259-301).
 The same chain s2amd_world_step runs on the device (solver2d_amd/csrc/world.hip); test infrastructure only."""
+import glob
+import os
+
 import numpy as np
 
 from solver2d_amd import wire
 from tests import oraclebind
 
 WORLD_KEYS = ("bodies", "contacts", "joints", "shapes", "pairs", "origins")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def copy_world(world):
@@ -61,6 +65,34 @@ def params_of(npz):
     p, f = npz["params"], npz["params_f"]
     import ctypes
     return wire.StepParams(int(p[0]), float(f[0]), int(p[1]), int(p[2]), int(p[3]), (ctypes.c_float * 2)(float(f[1]), float(f[2])))
+
+
+def golden(name):
+    """(params, world) of tests/golden/world_<name>_step*.npz"""
+    (path,) = glob.glob(os.path.join(GOLDEN, "world_%s_step*.npz" % name))
+    d = np.load(path)
+    return params_of(d), load_world(d)
+
+
+def _create_contacts(world, new_pairs):
+    """The caller's side of s2CreateContact (src/contact.c:137-203) for worlds of default-friction shapes: first free
+    slot, empty manifold."""
+    slots, contacts, pairs = [], [], []
+    free = np.flatnonzero(world["pairs"]["shapeA"] < 0).tolist()
+    for a, b in new_pairs.tolist():
+        k = free.pop(0)
+        c = np.zeros(1, dtype=wire.contact_dtype)[0]
+        c["bodyA"], c["bodyB"] = world["shapes"]["body"][a], world["shapes"]["body"][b]
+        c["friction"] = 0.6
+        c["constraintIndex"] = -1
+        p = np.zeros(1, dtype=wire.pair_state_dtype)[0]
+        p["shapeA"], p["shapeB"] = a, b
+        world["contacts"][k] = c
+        world["pairs"][k] = p
+        slots.append(k)
+        contacts.append(c)
+        pairs.append(p)
+    return np.array(slots, dtype=np.int32), np.array(contacts, dtype=wire.contact_dtype), np.array(pairs, dtype=wire.pair_state_dtype)
 
 
 def live_view(world):
