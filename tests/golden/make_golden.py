@@ -6,6 +6,10 @@ Each fixture is data only: the wire-format state at s2Solve_* entry ("pre_*") an
 of one s2World_Step of the reference, plus the step parameters.  No reference source text is
 stored.  tests/test_golden.py replays pre -> oracle -> compares bitwise with post, and the GPU
 tests replay pre -> HIP -> compare with the oracle run in the device's colour order.
+
+The fixtures in the folders beside this file have generators of their own, each named in its tests/*_world.py; the narrow phase's
+pose chains and directed cases (tests/golden/narrow_chain/) are written by
+    python -m tests.narrow_chain_world
 """
 import os
 import sys
