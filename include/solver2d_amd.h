@@ -1624,7 +1624,7 @@ int s2amd_world_actuator_counts(s2amdSolver* solver, int32_t counts[4]); /* actu
  * The reference has no observers: the composition is ours, every term the reference's function of that name.  Not offered: sharded
  * worlds; observer lists themselves in device memory; mouse-joint quantities; grid cells in the vector (they have their own export,
  * s2amd_world_export_grid_occupancy); running normalisation statistics.  Rewards and termination are the episode report's, below
- * (s2amd_world_set_episodes); resetting the bodies of a finished agent is what remains. */
+ * (s2amd_world_set_episodes); resetting the bodies of a finished agent is the resets', below them (s2amd_world_set_resets). */
 #define S2AMD_MAX_OBSERVERS 16384
 #define S2AMD_MAX_OBSERVATION_CHANNELS 65536
 #define S2AMD_MAX_OBSERVATION_FRAMES 16
@@ -1723,8 +1723,8 @@ int s2amd_world_observer_counts(s2amdSolver* solver, int32_t counts[4]); /* obse
  *   Cost          the setter groups the static list once, stably by (agent, list index).  A reporting step is two launches -- one lane
  *                 per rule, then one lane per agent walking its contiguous run in order -- and a third, one workgroup, only with
  *                 S2AMD_EPISODE_REPORT_EVENTS.  No float atomics, no sort, no scratch, no memset and no host wait in the step.
- * The reference has no episodes: the statement is ours.  Not offered: resetting the bodies of a finished agent (s2Body_SetTransform is
- * not offered by the edits either: it would move boxes and trees); sharded worlds; rules in device memory; transcendental reward shapes
+ * The reference has no episodes: the statement is ours.  Not offered here: resetting the bodies of a finished agent (that is
+ * s2amd_world_set_resets, below, which reads this pass's flags); sharded worlds; rules in device memory; transcendental reward shapes
  * such as exp or tanh (they cannot be stated bit for bit); discounting; float sums across agents. */
 #define S2AMD_MAX_EPISODE_AGENTS 16384
 #define S2AMD_MAX_EPISODE_RULES 65536
@@ -1792,6 +1792,101 @@ int s2amd_world_episode_states(s2amdSolver* solver, s2amdEpisodeState* out, int3
 int s2amd_world_episode_rule_states(s2amdSolver* solver, s2amdEpisodeRuleState* out, int32_t capacity, int32_t* count); /* in list order */
 int s2amd_world_episode_events(s2amdSolver* solver, s2amdEpisodeEvent* out, int32_t capacity, int32_t* count); /* agents done this step, ascending */
 int s2amd_world_episode_counts(s2amdSolver* solver, int32_t counts[8]); /* rules per status [0..3]; agents done, terminated, truncated, at the time limit [4..7] */
+
+/* (additive, API 5) Resets: the bodies and joints of a finished agent go back to a start state the caller gave, on the device.  A
+ * persistent list of body records and joint records over agents; the pass runs behind the episode pass of a step for the agents whose
+ * episode ended in it, or between steps for the agents a call names.  Nothing is downloaded, uploaded or re-based, and no structure is
+ * built: the boxes, contacts and pair states a teleport invalidates are put right as the reference's own functions would -- stage 4's
+ * box arithmetic (src/world.c:259-297), s2BroadPhase_MoveProxy's "new fat box, into the move buffer" and s2CreateContact's empty
+ * manifold (src/contact.c:137-203).  The reference declares s2Body_SetTransform and never defines it: the composition is ours.
+ *   Trigger       step mode (S2AMD_RESET_ON_EPISODE_END): trigger[a] = episode flags[a] & 3 of this step's episode pass, 0 for a >= the
+ *                 episode list's agents, and 0 for everybody when the episode pass did not run this step (counts[7] = 1, source off, and
+ *                 nothing is enqueued).  One-shot (s2amd_world_reset_agents): the agents listed, or all of them with NULL and
+ *                 S2AMD_RESET_ALL; enqueued like an edit behind the last step, it waits for nothing.
+ *   The pass      stated sequentially (== tests/reset_ref.py); n = the agent's `resets` counter before the pass:
+ *                 1. every body record k of a triggered agent that is not DISABLED: SKIPPED when the slot is beyond the capacity, FREE
+ *                    or STATIC; else position, rot, linearVelocity and angularVelocity come from the record with jitter, deltaPosition,
+ *                    force and torque become +0, every other field is kept, and the body is marked.
+ *                 2. jitter of component c (0, 1 position; 2, 3 linear velocity; 4 angular velocity): h = fmix32(seed + 0x9e3779b9 *
+ *                    (uint32)(8 * k + c)), h = fmix32(h ^ (uint32)n) (MurmurHash3's finaliser), u = (float)(h >> 8) * 2^-24,
+ *                    t = 2 * u - 1 (both exact), value = base + t * jitter: one multiply, one add.  A component whose jitter is 0
+ *                    copies the base's bits, so -0 stays -0.
+ *                 3. origins[body] = position - rotate(rot, localCenter), in stage 4's operation order.
+ *                 4. every live shape of a marked body: the tight box as stage 4 computes it, the fat box = the tight box -+
+ *                    S2_AABB_MARGIN unconditionally, enlarged = 1.  No other shape is touched: their flags stand.
+ *                 5. every live pair slot whose contact has a marked bodyA or bodyB: pointCount, frictionPersisted, normal and both
+ *                    points zero; in the pair state everything but shapeA and shapeB zero.  bodyA, bodyB, friction and constraintIndex
+ *                    are kept.  What stage 3 remembers as "touching after the last step" is not written: the next step compares with
+ *                    it, so a manifold that touches again is no flip, and a pair the teleport parted is found SEPARATED and destroyed
+ *                    by the next stage 3 as always (s2amd_world_separated).
+ *                 6. every joint record of a triggered agent that is not DISABLED: SKIPPED for a slot beyond the capacity or FREE; else
+ *                    impulse, motorImpulse, lowerImpulse and upperImpulse become +0, and with S2AMD_RESET_JOINT_SETTINGS a revolute
+ *                    joint takes enableMotor, enableLimit and motorSpeed, a mouse joint targetA, from the record.  A joint that is not
+ *                    listed is not touched, even when its body is marked.
+ *                 7. resets[a] += 1 for every triggered agent.  counts = {agents reset, bodies applied, bodies skipped, joints applied,
+ *                    joints skipped, shapes moved, contacts emptied, source off}: integers from wave ballots.
+ *   Reports       no report is re-based by a reset: each of the ten still compares the world after this step with the world after the
+ *                 step before, so a contact that touched and is parted by a reset is `ended` in the next step, a teleported shape may
+ *                 enter or leave a view or a sensor, and a body report sees the jump as motion.  The observation ring keeps its frames:
+ *                 the first observation of a new episode is the state one step after the reset, and a DIFFERENCE rule across frames
+ *                 reads the jump in that step.
+ *   Pairs         info.movedCount stays the refit's.  Call s2amd_world_find_pairs when movedCount > 0 or any exported done & 3 was
+ *                 set, and after s2amd_world_reset_agents: the query then runs on the flags as they stand, the resets' included.
+ *   Validation    on the host, before anything is replaced: 0 <= agents <= S2AMD_MAX_RESET_AGENTS, counts within S2AMD_MAX_RESET_BODIES
+ *                 and _JOINTS, records need agents > 0 and a non-NULL list; per record agent in [0, agents), target >= 0, no unknown
+ *                 flag bits (JOINT_SETTINGS is a joint record's), reserved == 0, every float finite, jitters >= 0, and no body slot and
+ *                 no joint slot named twice -- which is what lets the pass run without an ordering rule.  One bad record refuses the
+ *                 call with S2AMD_E_INVALID and the old list stands.  Whether a slot is live is the device's to judge (SKIPPED).  The
+ *                 list holds across uploads; the `resets` counters go to zero at an upload and when the list is replaced.
+ *                 Device trees (s2amd_world_set_tree) and a refit order (s2amd_world_set_refit_order) are the drop-in binding's, where
+ *                 a teleport is a tree remove and insert: s2amd_world_set_resets with a non-empty list returns S2AMD_E_STATE while
+ *                 either is set, and those two setters return S2AMD_E_STATE while a reset list is set.
+ *   Cost          two launches per pass: one lane per record and per agent, then one lane per shape slot and per contact slot, whose
+ *                 waves leave at once when nobody was marked.  No float atomics, no sort, no scratch, no memset and no host wait.
+ *                 With no list, or with the flags at 0 and no one-shot call, a step enqueues nothing.
+ * Not offered: sharded worlds; reset lists or triggers in the caller's device memory; capturing the start state on the device; rotation
+ * jitter (sinf and cosf cannot be stated bit for bit); static bodies; mass or type changes; re-observation after the reset; an episode
+ * rule flag that mutes a rule in an episode's first step. */
+#define S2AMD_MAX_RESET_AGENTS 16384
+#define S2AMD_MAX_RESET_BODIES 65536
+#define S2AMD_MAX_RESET_JOINTS 65536
+#define S2AMD_RESET_DISABLED 1
+#define S2AMD_RESET_JOINT_SETTINGS 2
+#define S2AMD_RESET_ON_EPISODE_END 1
+#define S2AMD_RESET_REPORT_STATES 2
+#define S2AMD_RESET_ALL (-1)
+typedef struct s2amdResetBody /* 64 bytes */
+{
+	int32_t agent;	/* [0, agents) */
+	int32_t body;	/* the body slot */
+	int32_t flags;	/* S2AMD_RESET_DISABLED */
+	float position[2]; /* the centre of mass, as s2amdBody.position */
+	float rot[2];	   /* {s, c} */
+	float linearVelocity[2];
+	float angularVelocity;
+	float positionJitter[2], velocityJitter[2], angularJitter; /* >= 0 */
+	int32_t reserved; /* 0 */
+} s2amdResetBody;
+typedef struct s2amdResetJoint /* 32 bytes */
+{
+	int32_t agent;	/* [0, agents) */
+	int32_t joint;	/* the joint slot */
+	int32_t flags;	/* S2AMD_RESET_DISABLED | S2AMD_RESET_JOINT_SETTINGS */
+	int32_t enableMotor, enableLimit; /* revolute, with JOINT_SETTINGS */
+	float motorSpeed;				  /* revolute, with JOINT_SETTINGS */
+	float targetA[2];				  /* mouse, with JOINT_SETTINGS */
+} s2amdResetJoint;
+typedef struct s2amdResetState /* 16 bytes */
+{
+	int32_t resets;	   /* passes that reset this agent since the list was set and since the last upload */
+	int32_t triggered; /* 1: the last pass reset it */
+	int32_t pad[2];
+} s2amdResetState;
+int s2amd_world_set_resets(s2amdSolver* solver, const s2amdResetBody* bodies, int32_t bodyCount, const s2amdResetJoint* joints, int32_t jointCount, int32_t agents, uint32_t seed); /* replaces everything; agents 0 clears */
+int s2amd_world_set_reset_report(s2amdSolver* solver, int32_t flags); /* S2AMD_RESET_ON_EPISODE_END | S2AMD_RESET_REPORT_STATES */
+int s2amd_world_reset_agents(s2amdSolver* solver, const int32_t* agents, int32_t count); /* the pass between steps; NULL with S2AMD_RESET_ALL: every agent */
+int s2amd_world_reset_states(s2amdSolver* solver, s2amdResetState* out, int32_t capacity, int32_t* count); /* one record per agent, with S2AMD_RESET_REPORT_STATES */
+int s2amd_world_reset_counts(s2amdSolver* solver, int32_t counts[8]); /* of the last pass, either mode */
 
 /* ---- constraint-graph structure on the device (the reference has neither islands nor colours) ----
  * Islands: connected components over the movable bodies (invMass != 0 or invI != 0) joined by active contacts

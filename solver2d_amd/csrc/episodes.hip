@@ -389,6 +389,16 @@ int episodeEnqueue(s2amdSolver* s, const s2amdStepParams*)
 	return S2AMD_OK;
 }
 
+const int* episodeStepFlags(const s2amdSolver* s, int* agents)
+{
+	*agents = s->episodeAgents;
+	if (s->episodeAgents <= 0 || s->episodeReport.stepFlags == 0 || s->dEpisodes.p == nullptr)
+	{
+		return nullptr;
+	}
+	return (const int*)((const char*)s->dEpisodes.p + layoutOf(s).flags);
+}
+
 void episodesRelease(s2amdSolver* s)
 {
 	s->dEpisodes.release();

@@ -333,6 +333,7 @@ struct DeviceTrees;
 void treesFree(s2amdSolver* s);
 void treesForget(s2amdSolver* s);
 bool treesActive(const s2amdSolver* s);
+bool treesAnySet(const s2amdSolver* s); // some tree has been handed over since the last upload (the resets refuse beside them)
 const TreeViews* treesViews(const s2amdSolver* s);
 int treesSyncRefitOrder(s2amdSolver* s);
 int worldWarmPairQuery(s2amdSolver* s); // world.hip

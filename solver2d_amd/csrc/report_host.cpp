@@ -1,5 +1,5 @@
 // The host side that the reports of the resident world share (contact_report.hip, joint_report.hip, shape_report.hip, body_report.hip,
-// step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip, observers.hip, episodes.hip): the table of the ten in step order with its walks, the block carver, the prepare and enqueue preambles, the
+// step_metrics.hip, sensor_report.hip, ray_report.hip, grid_report.hip, observers.hip, episodes.hip) and the resets behind them (resets.hip): the table of the eleven in step order with its walks, the block carver, the prepare and enqueue preambles, the
 // setter skeleton, the one device-to-host copy, and the getter shapes; and the host lifecycle of the lists a caller sets (sensors, fields,
 // rays, grids, actuators, observers, episode rules): the argument check, the two ways a new list goes in, the per-item getter, the copy out and the
 // status counts.  A report supplies its layout, its kernels, its prepare and enqueue bodies, and getters that name their list in terms
@@ -16,7 +16,9 @@ struct ReportFacility
 	int (*enqueue)(s2amdSolver*, const s2amdStepParams*);
 };
 
-// the order of a step: each report is enqueued behind the one before it
+// the order of a step: each report is enqueued behind the one before it.  The first ten read the world; the eleventh, the resets
+// (resets.hip), is the first entry that WRITES it -- the bodies, joints, boxes and contacts of the agents whose episode the tenth found
+// finished -- and therefore comes last: every report of this step has read the world the step left.
 const ReportFacility facilities[] = {
 	{&SolverRest::contactReport, contactReportPrepare, contactReportEnqueue},
 	{&SolverRest::jointReport, jointReportPrepare, jointReportEnqueue},
@@ -28,6 +30,7 @@ const ReportFacility facilities[] = {
 	{&SolverRest::gridReport, gridReportPrepare, gridReportEnqueue},
 	{&SolverRest::observationReport, observationPrepare, observationEnqueue},
 	{&SolverRest::episodeReport, episodePrepare, episodeEnqueue},
+	{&SolverRest::resetReport, resetPrepare, resetEnqueue},
 };
 
 int badArgument()

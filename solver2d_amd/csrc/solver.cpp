@@ -286,6 +286,7 @@ void s2amd_destroy(s2amdSolver* s)
 	actuatorsRelease(s);
 	observersRelease(s);
 	episodesRelease(s);
+	resetsRelease(s);
 	treesFree(s);
 	if (s->hostError)
 	{

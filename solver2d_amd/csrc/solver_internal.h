@@ -640,6 +640,20 @@ struct SolverRest
 	DevBuf dEpisodes;		   // {two sets of eight counts, the rules grouped by agent, first[agents + 1], limits, y, codes, the agent records, rewards, flags, rule states, events}
 	bool episodeFresh = true;  // re-based: the next reporting step takes every agent record as zero
 	long episodePasses = 0;	   // passes since the list was set: pass k counts into set k & 1 and clears the other
+	// resets (resets.hip; s2amd_world_set_resets, s2amd_world_set_reset_report: S2AMD_RESET_*, s2amd_world_reset_agents): the eleventh of a
+	// step, behind the episodes whose flags it reads, and the first that writes the world.  Its ReportState carries the flags alone
+	ReportState resetReport;
+	std::vector<s2amdResetBody> hResetBodies; // the persistent lists as the caller set them: held across uploads
+	std::vector<s2amdResetJoint> hResetJoints;
+	int resetAgents = 0; // 0: no list
+	uint32_t resetSeed = 0;
+	DevBuf dResets;				  // {two sets of eight counts, the body records, the joint records, two sets of agent records, the one-shot trigger}
+	DevBuf dResetMark;			  // one byte per body slot of the resident world: the last pass reset it (zeroed at an upload and by the setter)
+	long resetPasses = 0;		  // passes since the counters went to zero: pass k counts into set k & 1, reads agent records k & 1 and writes the other
+	bool resetCountsKnown = false; // a pass has run (or found its source off) since the list was set and since the last upload
+	bool resetSourceOff = false;  // ... and it was a step whose episode pass did not run: nothing was enqueued
+	int32_t* hostResetStage = nullptr; // the pinned copy of a one-shot call's triggers the device copy reads, and the event of that copy
+	hipEvent_t evResetStaged = nullptr;
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -880,7 +894,7 @@ int fetchPointCounts(s2amdSolver* s);
 // world chain: which pair slots the device has freed (stage 3 separations) -> hContactDead, before a structure rebuild
 int syncDeadSlots(s2amdSolver* s);
 // The reports behind s2amd_world_step.  Each file keeps its layout, kernels, prepare and enqueue; report_host.cpp holds the table of
-// the ten in step order and what their host sides share.
+// the ten in step order, the resets behind them, and what their host sides share.
 //   <x>Prepare   the report's device block for the resident world and its "before" state from the arrays just uploaded
 //   <x>Enqueue   the step's passes on the step's stream, behind stage 4 of the attempt that stands (never part of the captured graph)
 int contactReportPrepare(s2amdSolver* s);
@@ -910,6 +924,12 @@ const float* observationRing(const s2amdSolver* s, int* channels, int* frames, i
 int episodePrepare(s2amdSolver* s); // (episodes.hip: re-bases the accounting; the block is the setter's)
 int episodeEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 void episodesRelease(s2amdSolver* s);
+// What the reset pass reads of the episodes in front of it: the flags word per agent on the device, nullptr when the episode pass did
+// not run this step or no list is set; *agents: the episode list's.
+const int* episodeStepFlags(const s2amdSolver* s, int* agents);
+int resetPrepare(s2amdSolver* s); // (resets.hip: the mark bytes for the world just uploaded, the counters to zero; the block is the setter's)
+int resetEnqueue(s2amdSolver* s, const s2amdStepParams* params);
+void resetsRelease(s2amdSolver* s);
 // What the observation pass reads of the reports in front of it, on the device: nullptr means "not this step" (the source report's
 // stepFlags), and the count is that of the list whether or not it reported.
 const s2amdBodyContactSum* contactReportBodySums(const s2amdSolver* s); // contact_report.hip: bodyCapacity records

@@ -1094,6 +1094,11 @@ bool treesActive(const s2amdSolver* s)
 	return s->trees != nullptr && s->trees->set[0] && s->trees->set[1] && s->trees->set[2];
 }
 
+bool treesAnySet(const s2amdSolver* s)
+{
+	return s->trees != nullptr && (s->trees->set[0] || s->trees->set[1] || s->trees->set[2]);
+}
+
 const TreeViews* treesViews(const s2amdSolver* s)
 {
 	return treesActive(s) ? (const TreeViews*)s->trees->dViews.p : nullptr;
@@ -1229,6 +1234,10 @@ int s2amd_world_set_tree(s2amdSolver* s, int32_t bodyType, const s2amdTreeNode* 
 	if (!s->worldResident)
 	{
 		return fail(S2AMD_E_STATE, "s2amd_world_set_tree called before s2amd_world_upload");
+	}
+	if (s->resetAgents > 0)
+	{
+		return fail(S2AMD_E_STATE, "s2amd_world_set_tree: device trees are not offered together with a reset list (s2amd_world_set_resets)");
 	}
 	HIP_TRY(hipSetDevice(s->device));
 	// what the kernels rely on: links in range and mutual, no flagged internal node (the state stage 2 leaves a tree in)

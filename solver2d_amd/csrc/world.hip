@@ -1115,6 +1115,10 @@ int s2amd_world_set_refit_order(s2amdSolver* s, const int32_t* shapeOrder, int32
 	{
 		return fail(S2AMD_E_INVALID, "bad argument");
 	}
+	if (count > 0 && s->resetAgents > 0)
+	{
+		return fail(S2AMD_E_STATE, "s2amd_world_set_refit_order: a refit order is not offered together with a reset list (s2amd_world_set_resets)");
+	}
 	HIP_TRY(hipSetDevice(s->device));
 	s->refitOrderCount = 0;
 	s->stepBackValid = false;

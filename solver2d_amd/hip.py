@@ -43,6 +43,7 @@ EXPORTS = [
     "s2amd_world_set_episodes", "s2amd_world_set_episode_report", "s2amd_world_episode_rewards", "s2amd_world_episode_flags",
     "s2amd_world_export_episode_step", "s2amd_world_export_episode_step_async", "s2amd_world_episode_states", "s2amd_world_episode_rule_states",
     "s2amd_world_episode_events", "s2amd_world_episode_counts",
+    "s2amd_world_set_resets", "s2amd_world_set_reset_report", "s2amd_world_reset_agents", "s2amd_world_reset_states", "s2amd_world_reset_counts",
     "s2amd_world_set_sensors", "s2amd_world_set_sensor_report", "s2amd_world_sensor_inside", "s2amd_world_sensor_events", "s2amd_world_sensor_states",
     "s2amd_world_set_ray_sensors", "s2amd_world_set_ray_report", "s2amd_world_ray_states", "s2amd_world_ray_ranges", "s2amd_world_export_ray_ranges",
     "s2amd_world_ray_events",
@@ -175,6 +176,11 @@ def load(fast=False):
     L.s2amd_world_episode_rule_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_episode_events.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
     L.s2amd_world_episode_counts.argtypes = [vp, vp]
+    L.s2amd_world_set_resets.argtypes = [vp, vp, i32, vp, i32, i32, ctypes.c_uint32]
+    L.s2amd_world_set_reset_report.argtypes = [vp, i32]
+    L.s2amd_world_reset_agents.argtypes = [vp, vp, i32]
+    L.s2amd_world_reset_states.argtypes = [vp, vp, i32, ctypes.POINTER(i32)]
+    L.s2amd_world_reset_counts.argtypes = [vp, vp]
     L.s2amd_world_set_sensors.argtypes = [vp, vp, i32]
     L.s2amd_world_set_sensor_report.argtypes = [vp, i32, i32]
     L.s2amd_world_sensor_inside.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -721,6 +727,40 @@ class Solver:
         """int32[8]: rules per status {EVALUATED, DISABLED, SKIPPED, SOURCE_OFF}, then agents done, terminated, truncated, at the time limit."""
         counts = np.zeros(8, dtype=np.int32)
         self._ck(self._L.s2amd_world_episode_counts(self._h, wire.as_ptr(counts)))
+        return counts
+
+    # ---- resets on the resident world (s2amd_world_set_resets, ...): finished agents restart on the device ----
+    def world_set_resets(self, bodies, joints, agents, seed=0):
+        """Replaces the whole persistent list (wire.reset_body_dtype and wire.reset_joint_dtype records, e.g. wire.resets_from_world) over
+        `agents` agents; agents = 0 clears it.  `seed` keys the jitter."""
+        bodies, joints = np.ascontiguousarray(bodies), np.ascontiguousarray(joints)
+        assert bodies.dtype == wire.reset_body_dtype and joints.dtype == wire.reset_joint_dtype
+        self._ck(self._L.s2amd_world_set_resets(self._h, wire.as_ptr(bodies) if len(bodies) else None, len(bodies), wire.as_ptr(joints) if len(joints) else None,
+                                                len(joints), int(agents), int(seed) & 0xFFFFFFFF))
+        self._world_resets = int(agents)
+
+    def world_set_reset_report(self, flags):
+        """wire.RESET_ON_EPISODE_END: every world_step resets the agents whose episode ended in it, behind its episode pass;
+        wire.RESET_REPORT_STATES opens world_reset_states.  0: a step enqueues nothing."""
+        self._ck(self._L.s2amd_world_set_reset_report(self._h, int(flags)))
+
+    def world_reset_agents(self, agents=None):
+        """The reset pass between steps for the agents listed (None: every agent); enqueued like an edit, waits for nothing."""
+        if agents is None:
+            self._ck(self._L.s2amd_world_reset_agents(self._h, None, wire.RESET_ALL))
+            return
+        agents = np.ascontiguousarray(agents, dtype=np.int32)
+        self._ck(self._L.s2amd_world_reset_agents(self._h, wire.as_ptr(agents) if len(agents) else None, len(agents)))
+
+    def world_reset_states(self):
+        """wire.reset_state_dtype records, one per agent: how often it has been reset, and whether the last pass did."""
+        return self._world_list(self._L.s2amd_world_reset_states, wire.reset_state_dtype, getattr(self, "_world_resets", 0))
+
+    def world_reset_counts(self):
+        """int32[8] of the last pass: agents reset, bodies applied, bodies skipped, joints applied, joints skipped, shapes moved,
+        contacts emptied, source off."""
+        counts = np.zeros(8, dtype=np.int32)
+        self._ck(self._L.s2amd_world_reset_counts(self._h, wire.as_ptr(counts)))
         return counts
 
     # ---- force fields on the resident world (s2amd_world_apply_fields, s2amd_world_set_fields): writes addressed by region ----

@@ -512,3 +512,41 @@ def episode_rule(kind, agent, channel=-1, frame=0, minus=None, shape=0, gain=1.0
 def episode_rule_list(rules):
     """A list of the records above (or an array of them) as one contiguous wire.episode_rule_dtype array."""
     return np.ascontiguousarray(np.array(list(rules), dtype=episode_rule_dtype)) if len(rules) else np.zeros(0, dtype=episode_rule_dtype)
+
+
+# resets on the resident world (include/solver2d_amd.h: s2amd_world_set_resets, s2amd_world_set_reset_report, s2amd_world_reset_agents)
+MAX_RESET_AGENTS, MAX_RESET_BODIES, MAX_RESET_JOINTS = 16384, 65536, 65536
+RESET_DISABLED, RESET_JOINT_SETTINGS = 1, 2
+RESET_ON_EPISODE_END, RESET_REPORT_STATES = 1, 2
+RESET_ALL = -1
+# the counts of a pass, in order
+RESET_COUNT_AGENTS, RESET_COUNT_BODIES, RESET_COUNT_BODIES_SKIPPED, RESET_COUNT_JOINTS, RESET_COUNT_JOINTS_SKIPPED, RESET_COUNT_SHAPES, RESET_COUNT_CONTACTS, RESET_COUNT_SOURCE_OFF = range(8)
+# s2amdResetBody, s2amdResetJoint, s2amdResetState
+reset_body_dtype = np.dtype([("agent", np.int32), ("body", np.int32), ("flags", np.int32), ("position", np.float32, 2), ("rot", np.float32, 2),
+                             ("linearVelocity", np.float32, 2), ("angularVelocity", np.float32), ("positionJitter", np.float32, 2),
+                             ("velocityJitter", np.float32, 2), ("angularJitter", np.float32), ("reserved", np.int32)])
+reset_joint_dtype = np.dtype([("agent", np.int32), ("joint", np.int32), ("flags", np.int32), ("enableMotor", np.int32), ("enableLimit", np.int32),
+                              ("motorSpeed", np.float32), ("targetA", np.float32, 2)])
+reset_state_dtype = np.dtype([("resets", np.int32), ("triggered", np.int32), ("pad", np.int32, 2)])
+RESET_BODY_SIZE, RESET_JOINT_SIZE, RESET_STATE_SIZE = reset_body_dtype.itemsize, reset_joint_dtype.itemsize, reset_state_dtype.itemsize
+assert (RESET_BODY_SIZE, RESET_JOINT_SIZE, RESET_STATE_SIZE) == (64, 32, 16)
+
+
+def resets_from_world(bodies, joints, agent_of_body, agent_of_joint, joint_flags=RESET_JOINT_SETTINGS):
+    """The reset records of the arrays a caller uploads: one body record per body slot with agent_of_body[slot] >= 0 that is neither
+    free nor static, holding the slot's pose and velocities with no jitter, and one joint record per live joint slot with
+    agent_of_joint[slot] >= 0, holding the slot's settings (flags = joint_flags).  -> (wire.reset_body_dtype array, wire.reset_joint_dtype
+    array), each in slot order."""
+    agent_of_body, agent_of_joint = np.asarray(agent_of_body, dtype=np.int32), np.asarray(agent_of_joint, dtype=np.int32)
+    assert len(agent_of_body) == len(bodies) and len(agent_of_joint) == len(joints)
+    slots = np.flatnonzero((agent_of_body >= 0) & (bodies["type"] != BODY_FREE) & (bodies["type"] != BODY_STATIC))
+    rb = np.zeros(len(slots), dtype=reset_body_dtype)
+    rb["agent"], rb["body"] = agent_of_body[slots], slots
+    for name in ("position", "rot", "linearVelocity", "angularVelocity"):
+        rb[name] = bodies[name][slots]
+    slots = np.flatnonzero((agent_of_joint >= 0) & (joints["type"] != JOINT_FREE))
+    rj = np.zeros(len(slots), dtype=reset_joint_dtype)
+    rj["agent"], rj["joint"], rj["flags"] = agent_of_joint[slots], slots, joint_flags
+    for name in ("enableMotor", "enableLimit", "motorSpeed", "targetA"):
+        rj[name] = joints[name][slots]
+    return rb, rj
