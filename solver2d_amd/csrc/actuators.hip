@@ -383,22 +383,6 @@ void actuatorsForgetWorld(s2amdSolver* s)
 	s->actuatorStatesValid = false;
 }
 
-void actuatorsRelease(s2amdSolver* s)
-{
-	s->dActuators.release();
-	if (s->hostActionStage)
-	{
-		(void)hipHostFree(s->hostActionStage);
-		s->hostActionStage = nullptr;
-		s->hostActionStageBytes = 0;
-	}
-	if (s->evActionStaged)
-	{
-		(void)hipEventDestroy(s->evActionStaged);
-		s->evActionStaged = nullptr;
-	}
-}
-
 #pragma GCC visibility push(default)
 extern "C"
 {
@@ -482,29 +466,13 @@ int s2amd_world_set_actions(s2amdSolver* s, const float* hostValues, int32_t fir
 	// the pinned stage, as s2amd_world_edit's: the caller may reuse its array at once and the copy to the device is a true asynchronous
 	// one.  The copy of the call before may still be reading the stage: its event is waited for first.
 	const size_t bytes = (size_t)count * sizeof(float);
-	if (!s->evActionStaged)
+	if (int rc = s->actionStage.begin(bytes, std::max(reportRound((size_t)s->actuatorChannels * sizeof(float)), (size_t)4096)))
 	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evActionStaged, hipEventDisableTiming));
+		return rc;
 	}
-	else
-	{
-		HIP_TRY(hipEventSynchronize(s->evActionStaged));
-	}
-	if (s->hostActionStageBytes < bytes)
-	{
-		if (s->hostActionStage)
-		{
-			(void)hipHostFree(s->hostActionStage);
-			s->hostActionStage = nullptr;
-			s->hostActionStageBytes = 0;
-		}
-		const size_t want = std::max(reportRound((size_t)s->actuatorChannels * sizeof(float)), (size_t)4096);
-		HIP_TRY(hipHostMalloc((void**)&s->hostActionStage, want, hipHostMallocDefault));
-		s->hostActionStageBytes = want;
-	}
-	memcpy(s->hostActionStage, hostValues, bytes);
-	HIP_TRY(hipMemcpyAsync(actionBuffer(s) + first, s->hostActionStage, bytes, hipMemcpyHostToDevice, s->stream));
-	HIP_TRY(hipEventRecord(s->evActionStaged, s->stream));
+	memcpy(s->actionStage.buf.p, hostValues, bytes);
+	HIP_TRY(hipMemcpyAsync(actionBuffer(s) + first, s->actionStage.buf.p, bytes, hipMemcpyHostToDevice, s->stream));
+	HIP_TRY(s->actionStage.record(s->stream));
 	return S2AMD_OK;
 }
 

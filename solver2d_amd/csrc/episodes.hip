@@ -399,11 +399,6 @@ const int* episodeStepFlags(const s2amdSolver* s, int* agents)
 	return (const int*)((const char*)s->dEpisodes.p + layoutOf(s).flags);
 }
 
-void episodesRelease(s2amdSolver* s)
-{
-	s->dEpisodes.release();
-}
-
 #pragma GCC visibility push(default)
 extern "C"
 {
@@ -553,16 +548,14 @@ int s2amd_world_export_episode_step_async(s2amdSolver* s, void* deviceRewards, v
 		return rc;
 	}
 	HIP_TRY(hipSetDevice(s->device));
-	if (!s->evExport[slot])
-	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evExport[slot], hipEventDisableTiming));
-	}
+	hipEvent_t exported = nullptr;
+	HIP_TRY(exportEvent(s, slot, &exported));
 	if (count > 0 && (rc = enqueueStep(s, deviceRewards, deviceFlags)) != 0)
 	{
 		return rc;
 	}
 	// (recorded with no list too: s2amd_export_wait(slot) then returns at once)
-	HIP_TRY(hipEventRecord(s->evExport[slot], s->stream));
+	HIP_TRY(hipEventRecord(exported, s->stream));
 	return S2AMD_OK;
 }
 

@@ -452,24 +452,6 @@ void fieldsForgetWorld(s2amdSolver* s)
 	s->fieldStatesValid = false;
 }
 
-void fieldsRelease(s2amdSolver* s)
-{
-	s->dFieldList.release();
-	s->dFieldCall.release();
-	s->dFieldAdj.release();
-	if (s->hostFieldStage)
-	{
-		(void)hipHostFree(s->hostFieldStage);
-		s->hostFieldStage = nullptr;
-		s->hostFieldStageBytes = 0;
-	}
-	if (s->evFieldStaged)
-	{
-		(void)hipEventDestroy(s->evFieldStaged);
-		s->evFieldStaged = nullptr;
-	}
-}
-
 #pragma GCC visibility push(default)
 extern "C"
 {
@@ -493,35 +475,19 @@ int s2amd_world_apply_fields(s2amdSolver* s, const s2amdField* fields, int32_t c
 	// the pinned stage, as s2amd_world_edit's: the caller may reuse its list at once and the copy to the device is a true asynchronous
 	// one.  The copy of the call before may still be reading the stage: its event is waited for first.
 	const size_t listBytes = (size_t)count * sizeof(s2amdField);
-	if (!s->evFieldStaged)
+	if (int rc = s->fieldStage.begin(listBytes, std::max(reportRound(listBytes + listBytes / 2), (size_t)4096)))
 	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evFieldStaged, hipEventDisableTiming));
-	}
-	else
-	{
-		HIP_TRY(hipEventSynchronize(s->evFieldStaged));
-	}
-	if (s->hostFieldStageBytes < listBytes)
-	{
-		if (s->hostFieldStage)
-		{
-			(void)hipHostFree(s->hostFieldStage);
-			s->hostFieldStage = nullptr;
-			s->hostFieldStageBytes = 0;
-		}
-		const size_t want = std::max(reportRound(listBytes + listBytes / 2), (size_t)4096);
-		HIP_TRY(hipHostMalloc((void**)&s->hostFieldStage, want, hipHostMallocDefault));
-		s->hostFieldStageBytes = want;
+		return rc;
 	}
 	const FieldLayout l = fieldLayout(count);
 	if (int rc = s->dFieldCall.ensure(l.total))
 	{
 		return rc;
 	}
-	memcpy(s->hostFieldStage, fields, listBytes);
+	memcpy(s->fieldStage.buf.p, fields, listBytes);
 	char* base = (char*)s->dFieldCall.p;
-	HIP_TRY(hipMemcpyAsync(base + l.fields, s->hostFieldStage, listBytes, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipEventRecord(s->evFieldStaged, st));
+	HIP_TRY(hipMemcpyAsync(base + l.fields, s->fieldStage.buf.p, listBytes, hipMemcpyHostToDevice, st));
+	HIP_TRY(s->fieldStage.record(st));
 	if (int rc = enqueueFields(s, s->dFieldCall, count))
 	{
 		return rc;

@@ -393,11 +393,6 @@ int observationEnqueue(s2amdSolver* s, const s2amdStepParams*)
 	return S2AMD_OK;
 }
 
-void observersRelease(s2amdSolver* s)
-{
-	s->dObservers.release();
-}
-
 const float* observationRing(const s2amdSolver* s, int* channels, int* frames, int* head)
 {
 	*channels = s->observationChannels, *frames = s->observationFrames, *head = s->observationHead;
@@ -506,16 +501,14 @@ int s2amd_world_export_observations_async(s2amdSolver* s, void* deviceVector, in
 		return rc;
 	}
 	HIP_TRY(hipSetDevice(s->device));
-	if (!s->evExport[slot])
-	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evExport[slot], hipEventDisableTiming));
-	}
+	hipEvent_t exported = nullptr;
+	HIP_TRY(exportEvent(s, slot, &exported));
 	if (count > 0 && (rc = enqueueVector(s, deviceVector, hipMemcpyDeviceToDevice)) != 0)
 	{
 		return rc;
 	}
 	// (recorded with an empty list too: s2amd_export_wait(slot) then returns at once)
-	HIP_TRY(hipEventRecord(s->evExport[slot], s->stream));
+	HIP_TRY(hipEventRecord(exported, s->stream));
 	return S2AMD_OK;
 }
 

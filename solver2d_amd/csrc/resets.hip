@@ -460,22 +460,6 @@ int resetEnqueue(s2amdSolver* s, const s2amdStepParams*)
 	return S2AMD_OK;
 }
 
-void resetsRelease(s2amdSolver* s)
-{
-	s->dResets.release();
-	s->dResetMark.release();
-	if (s->hostResetStage)
-	{
-		(void)hipHostFree(s->hostResetStage);
-		s->hostResetStage = nullptr;
-	}
-	if (s->evResetStaged)
-	{
-		(void)hipEventDestroy(s->evResetStaged);
-		s->evResetStaged = nullptr;
-	}
-}
-
 #pragma GCC visibility push(default)
 extern "C"
 {
@@ -616,26 +600,19 @@ int s2amd_world_reset_agents(s2amdSolver* s, const int32_t* agents, int32_t coun
 		// the pinned stage, one word per agent: written here, copied asynchronously.  The copy of the call before may still be reading it:
 		// its event is waited for first (the edits' discipline, world_edit.hip).
 		const size_t bytes = (size_t)s->resetAgents * sizeof(int32_t);
-		if (!s->evResetStaged)
+		if (int rc = s->resetStage.begin(bytes, (size_t)S2AMD_MAX_RESET_AGENTS * sizeof(int32_t)))
 		{
-			HIP_TRY(hipEventCreateWithFlags(&s->evResetStaged, hipEventDisableTiming));
+			return rc;
 		}
-		else
-		{
-			HIP_TRY(hipEventSynchronize(s->evResetStaged));
-		}
-		if (!s->hostResetStage)
-		{
-			HIP_TRY(hipHostMalloc((void**)&s->hostResetStage, (size_t)S2AMD_MAX_RESET_AGENTS * sizeof(int32_t), hipHostMallocDefault));
-		}
-		memset(s->hostResetStage, 0, bytes);
+		int32_t* stage = (int32_t*)s->resetStage.buf.p;
+		memset(stage, 0, bytes);
 		for (int32_t i = 0; i < count; ++i)
 		{
-			s->hostResetStage[agents[i]] = 1;
+			stage[agents[i]] = 1;
 		}
 		char* at = (char*)s->dResets.p + layoutOf(s).trigger;
-		HIP_TRY(hipMemcpyAsync(at, s->hostResetStage, bytes, hipMemcpyHostToDevice, s->stream));
-		HIP_TRY(hipEventRecord(s->evResetStaged, s->stream));
+		HIP_TRY(hipMemcpyAsync(at, stage, bytes, hipMemcpyHostToDevice, s->stream));
+		HIP_TRY(s->resetStage.record(s->stream));
 		trigger = (const int*)at;
 	}
 	if (int rc = enqueuePass(s, trigger, s->resetAgents, ~0, everybody ? 1 : 0))

@@ -248,6 +248,42 @@ int s2amd_create(int device, s2amdSolver** out)
 	return S2AMD_OK;
 }
 
+// S2AMD_DEBUG_TIMES: the phase time stamps one workgroup of the last persistent step left in the pinned page
+static void printHostTimes(const s2amdSolver* s)
+{
+	int n = (int)s->hostTimes[255];
+	if (s->hostTimes[254] == 1ull && n > 1)
+	{
+		// pair_kernel.hip's tagged stamps: time per phase of the last step, one workgroup
+		static const char* names[16] = {"start", "load", "body stages", "warm starts", "interior rounds (last)", "hand-offs", "seam rounds (last)", "store",
+										"interior 0", "interior 1", "interior 2", "interior 3", "commit wait (self-contained)", "interior 5", "seam 0", "seam 1 | warm-start terms (body-centric)"};
+		double sum[16] = {0};
+		int count[16] = {0};
+		for (int i = 1; i < n && i < 250; ++i)
+		{
+			const unsigned tag = (unsigned)(s->hostTimes[i] & 15ull);
+			sum[tag] += 0.01 * (double)((s->hostTimes[i] >> 4) - (s->hostTimes[i - 1] >> 4));
+			count[tag] += 1;
+		}
+		fprintf(stderr, "[s2amd] pair-lane persistent step, one workgroup, us per phase (count):");
+		for (int t = 1; t < 16; ++t)
+		{
+			if (count[t] > 0)
+			{
+				fprintf(stderr, " %s %.1f (%d);", names[t], sum[t], count[t]);
+			}
+		}
+		fprintf(stderr, " total %.1f\n", 0.01 * (double)((s->hostTimes[n - 1] >> 4) - (s->hostTimes[0] >> 4)));
+		n = 0;
+	}
+	fprintf(stderr, "[s2amd] persistent step, one workgroup, wall_clock64 ticks (10 ns) since kernel start:");
+	for (int i = 1; i < n && i < 255; ++i)
+	{
+		fprintf(stderr, " %llu", s->hostTimes[i] - s->hostTimes[0]);
+	}
+	fprintf(stderr, "\n");
+}
+
 void s2amd_destroy(s2amdSolver* s)
 {
 	if (!s)
@@ -264,135 +300,54 @@ void s2amd_destroy(s2amdSolver* s)
 			spareClonesRelease(); // (... and the retired copies themselves -- megabytes of host vectors -- with the process's last solver)
 		}
 	}
+	// wait, then: the graphs, the device blocks, the pinned stages and blocks, the trees, the events, the streams
 	(void)hipStreamSynchronize(s->stream);
 	destroyGraph(s);
-	for (hipEvent_t e : s->sweepEvents)
-	{
-		(void)hipEventDestroy(e);
-	}
-	DevBuf* bufs[] = {&s->dBodies,		&s->dContacts,	  &s->dJoints,		 &s->dBodiesSaved,	 &s->dBodyFlags,	&s->soaBodies,
-					  &s->soaContacts,	&s->soaJoints,	  &s->dContactIndex, &s->dJointIndex,	 &s->dContactLocal, &s->dJointLocal,
-					  &s->dAdjOffsets,	&s->dAdjList,	  &s->dAdjHeavy,	  &s->dGatherIndex,	 &s->dOps,			 &s->dGroups.buf,	&s->dContactTail.buf,
-					  &s->dJointTail.buf, &s->dMsg,			  &s->dStripA.buf,	 &s->dStripB.buf,	 &s->dStripLean,	&s->dPersist,
-					  &s->dGranules,	&s->dOverflowBodies, &s->dPairLog, &s->dPersistOps, &s->dJacobi, &s->dJacobiGran,	  &s->dShapes,		 &s->dPairs,		 &s->dOrigins,		&s->dStatus,
-					  &s->dPointBytes,	&s->dWorldSummary, &s->dJointedKeys,	 &s->dContactStage, &s->dPairScratch,	  &s->dPairKeys,		 &s->dPatches,		 &s->dScanTmp,		 &s->dResident.buf,	 &s->dResidentDesc, &s->dResidentOps, &s->dWatched, &s->dRefitOrder, &s->dStepBack,
-					  &s->dSlotBytes,	  &s->dJointAdjRange, &s->dJointAdjList, &s->dShapeBoxes, &s->dMetricsRing, &s->dQuery, &s->dEdit};
-	for (DevBuf* b : bufs)
-	{
-		b->release();
-	}
-	reportsRelease(s);
-	fieldsRelease(s);
-	actuatorsRelease(s);
-	observersRelease(s);
-	episodesRelease(s);
-	resetsRelease(s);
-	treesFree(s);
-	if (s->hostError)
-	{
-		(void)hipHostFree(s->hostError);
-	}
 	if (s->pairQuery.exec)
 	{
 		(void)hipGraphExecDestroy(s->pairQuery.exec);
 	}
-	if (s->pairQuery.host)
+	const auto release = [](DevBuf& b) { b.release(); };
+	forEachStructureBuf(*s, release);
+	forEachRestBuf(*s, release);
+	reportsRelease(s);
+	for (PinnedStage* stage : {&s->editStage, &s->fieldStage, &s->actionStage, &s->resetStage})
 	{
-		(void)hipHostFree(s->pairQuery.host);
+		stage->release();
 	}
-	if (s->hostStepBack)
-	{
-		(void)hipHostFree(s->hostStepBack);
-	}
-	if (s->hostEditStage)
-	{
-		(void)hipHostFree(s->hostEditStage);
-	}
-	if (s->evEditStaged)
-	{
-		(void)hipEventDestroy(s->evEditStaged);
-	}
-	if (s->hostPairLog)
-	{
-		(void)hipHostFree(s->hostPairLog);
-		s->hostPairLog = nullptr;
-	}
-	if (s->hostSlotStage)
-	{
-		(void)hipHostFree(s->hostSlotStage);
-		s->hostSlotStage = nullptr;
-	}
-	if (s->hostWorldSummary)
-	{
-		(void)hipHostFree(s->hostWorldSummary);
-	}
-	if (s->hostPatches)
-	{
-		(void)hipHostFree(s->hostPatches);
-	}
+	s->stepBackStage.release();
+	s->slotStage.release();
 	if (s->hostTimes)
 	{
-		int n = (int)s->hostTimes[255];
-		if (s->hostTimes[254] == 1ull && n > 1)
-		{
-			// pair_kernel.hip's tagged stamps: time per phase of the last step, one workgroup
-			static const char* names[16] = {"start", "load", "body stages", "warm starts", "interior rounds (last)", "hand-offs", "seam rounds (last)", "store",
-											"interior 0", "interior 1", "interior 2", "interior 3", "commit wait (self-contained)", "interior 5", "seam 0", "seam 1 | warm-start terms (body-centric)"};
-			double sum[16] = {0};
-			int count[16] = {0};
-			for (int i = 1; i < n && i < 250; ++i)
-			{
-				const unsigned tag = (unsigned)(s->hostTimes[i] & 15ull);
-				sum[tag] += 0.01 * (double)((s->hostTimes[i] >> 4) - (s->hostTimes[i - 1] >> 4));
-				count[tag] += 1;
-			}
-			fprintf(stderr, "[s2amd] pair-lane persistent step, one workgroup, us per phase (count):");
-			for (int t = 1; t < 16; ++t)
-			{
-				if (count[t] > 0)
-				{
-					fprintf(stderr, " %s %.1f (%d);", names[t], sum[t], count[t]);
-				}
-			}
-			fprintf(stderr, " total %.1f\n", 0.01 * (double)((s->hostTimes[n - 1] >> 4) - (s->hostTimes[0] >> 4)));
-			n = 0;
-		}
-		fprintf(stderr, "[s2amd] persistent step, one workgroup, wall_clock64 ticks (10 ns) since kernel start:");
-		for (int i = 1; i < n && i < 255; ++i)
-		{
-			fprintf(stderr, " %llu", s->hostTimes[i] - s->hostTimes[0]);
-		}
-		fprintf(stderr, "\n");
-		(void)hipHostFree(s->hostTimes);
+		printHostTimes(s);
 	}
-	(void)hipEventDestroy(s->evBegin);
-	(void)hipEventDestroy(s->evEnd);
-	for (hipEvent_t e : s->evExport)
+	for (void* pinned : {(void*)s->hostError, (void*)s->pairQuery.host, (void*)s->hostPairLog, (void*)s->hostWorldSummary, (void*)s->hostPatches, (void*)s->hostTimes})
+	{
+		if (pinned)
+		{
+			(void)hipHostFree(pinned);
+		}
+	}
+	treesFree(s);
+	for (hipEvent_t e : s->sweepEvents)
+	{
+		(void)hipEventDestroy(e);
+	}
+	for (hipEvent_t e : {s->evBegin, s->evEnd, s->evExport[0], s->evExport[1], s->evExport[2], s->evExport[3], s->evFork[0], s->evFork[1], s->evJoin[0], s->evJoin[1],
+						 s->evJoin[2], s->evJoin[3]})
 	{
 		if (e)
 		{
 			(void)hipEventDestroy(e);
 		}
 	}
-	for (int i = 0; i < 2; ++i)
+	for (hipStream_t st : {s->side[0], s->side[1], s->stream})
 	{
-		if (s->evFork[i])
+		if (st)
 		{
-			(void)hipEventDestroy(s->evFork[i]);
-		}
-		if (s->side[i])
-		{
-			(void)hipStreamDestroy(s->side[i]);
+			(void)hipStreamDestroy(st);
 		}
 	}
-	for (int i = 0; i < 4; ++i)
-	{
-		if (s->evJoin[i])
-		{
-			(void)hipEventDestroy(s->evJoin[i]);
-		}
-	}
-	(void)hipStreamDestroy(s->stream);
 	delete s;
 }
 
@@ -844,13 +799,11 @@ int s2amd_export_poses_async(s2amdSolver* s, void* devicePoses, int32_t capacity
 		return fail(S2AMD_E_CAPACITY, "pose buffer missing or too small, or slot outside 0..3");
 	}
 	HIP_TRY(hipSetDevice(s->device));
-	if (!s->evExport[slot])
-	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evExport[slot], hipEventDisableTiming));
-	}
+	hipEvent_t exported = nullptr;
+	HIP_TRY(exportEvent(s, slot, &exported));
 	launchExportPoses(s->stream, (const s2amdBody*)s->dBodies.p, s->bodyCapacity, devicePoses);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(s->evExport[slot], s->stream));
+	HIP_TRY(hipEventRecord(exported, s->stream));
 	return S2AMD_OK;
 }
 
@@ -865,13 +818,11 @@ int s2amd_export_bodies_async(s2amdSolver* s, void* deviceRecords, int32_t capac
 		return fail(S2AMD_E_CAPACITY, "record buffer missing or too small, or slot outside 0..3");
 	}
 	HIP_TRY(hipSetDevice(s->device));
-	if (!s->evExport[slot])
-	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evExport[slot], hipEventDisableTiming));
-	}
+	hipEvent_t exported = nullptr;
+	HIP_TRY(exportEvent(s, slot, &exported));
 	launchExportPoses(s->stream, (const s2amdBody*)s->dBodies.p, s->bodyCapacity, deviceRecords, 1);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(s->evExport[slot], s->stream));
+	HIP_TRY(hipEventRecord(exported, s->stream));
 	return S2AMD_OK;
 }
 

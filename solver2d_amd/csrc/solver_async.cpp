@@ -225,14 +225,7 @@ namespace
 // every device allocation, pinned buffer and captured graph of the structure part: a copy must not share them with its original
 void forgetDeviceState(SolverStructure& t)
 {
-	DevBuf* bufs[] = {&t.dWatched, &t.dBodyFlags, &t.soaBodies, &t.soaContacts, &t.soaJoints, &t.dContactIndex, &t.dJointIndex, &t.dContactLocal, &t.dJointLocal,
-					  &t.dAdjOffsets, &t.dAdjList, &t.dAdjHeavy, &t.dPatches, &t.dJointAdjRange, &t.dJointAdjList, &t.dResidentDesc, &t.dResidentOps, &t.dStripLean,
-					  &t.dPersist, &t.dGranules, &t.dOverflowBodies, &t.dPersistOps, &t.dJacobi, &t.dJacobiGran, &t.dMsg, &t.dGroups.buf, &t.dContactTail.buf, &t.dJointTail.buf, &t.dStripA.buf, &t.dStripB.buf,
-					  &t.dResident.buf};
-	for (DevBuf* b : bufs)
-	{
-		b->p = nullptr, b->bytes = 0;
-	}
+	forEachStructureBuf(t, [](DevBuf& b) { b = DevBuf{}; });
 	t.dGroups = DeviceGroupTable{}, t.dContactTail = DeviceGroupTable{}, t.dJointTail = DeviceGroupTable{}, t.dStripA = DeviceGroupTable{}, t.dStripB = DeviceGroupTable{};
 	t.dResident = DeviceGroupTable{};
 	t.hostPatches = nullptr, t.hostPatchCapacity = 0;
@@ -263,14 +256,7 @@ void releaseDeviceState(s2amdSolver* c)
 	}
 	destroyGraph(c);
 	SolverStructure& t = *c;
-	DevBuf* bufs[] = {&t.dWatched, &t.dBodyFlags, &t.soaBodies, &t.soaContacts, &t.soaJoints, &t.dContactIndex, &t.dJointIndex, &t.dContactLocal, &t.dJointLocal,
-					  &t.dAdjOffsets, &t.dAdjList, &t.dAdjHeavy, &t.dPatches, &t.dJointAdjRange, &t.dJointAdjList, &t.dResidentDesc, &t.dResidentOps, &t.dStripLean,
-					  &t.dPersist, &t.dGranules, &t.dOverflowBodies, &t.dPersistOps, &t.dJacobi, &t.dJacobiGran, &t.dMsg, &t.dGroups.buf, &t.dContactTail.buf, &t.dJointTail.buf, &t.dStripA.buf, &t.dStripB.buf,
-					  &t.dResident.buf};
-	for (DevBuf* b : bufs)
-	{
-		b->release();
-	}
+	forEachStructureBuf(t, [](DevBuf& b) { b.release(); });
 	if (t.hostPatches)
 	{
 		if (devPoolOn())
@@ -606,6 +592,18 @@ int asyncRequest(s2amdSolver* s, int solverType, bool search, bool forceStrips)
 // step that asks for the first overflow build).  So once a world has its structure, blocks of the sizes a copy will ask for -- the live
 // structure's own -- and one pinned patch buffer go into the pool while nothing depends on the step's latency (the upload, or the first
 // step's tail).  Twice the structure's device memory: tens of megabytes at 60k constraints.
+static int poolStock(size_t bytes, bool* full)
+{
+	void* p = nullptr;
+	HIP_TRY(hipMalloc(&p, bytes));
+	if (!devPoolGive(p, bytes))
+	{
+		(void)hipFree(p);
+		*full = true;
+	}
+	return S2AMD_OK;
+}
+
 int asyncPrewarm(s2amdSolver* s, int solverType)
 {
 	if (s->poolWarmed || s->optAsyncBuild == 0 || s->isClone || s->structureDirty)
@@ -615,20 +613,17 @@ int asyncPrewarm(s2amdSolver* s, int solverType)
 	s->poolWarmed = true;
 	HIP_TRY(hipSetDevice(s->device));
 	SolverStructure& t = *s;
-	const DevBuf* bufs[] = {&t.dWatched, &t.dBodyFlags, &t.soaBodies, &t.soaContacts, &t.soaJoints, &t.dContactIndex, &t.dJointIndex, &t.dContactLocal, &t.dJointLocal,
-							&t.dAdjOffsets, &t.dAdjList, &t.dAdjHeavy, &t.dPatches, &t.dJointAdjRange, &t.dJointAdjList, &t.dResidentDesc, &t.dResidentOps, &t.dStripLean,
-							&t.dPersist, &t.dGranules, &t.dOverflowBodies, &t.dPersistOps, &t.dJacobi, &t.dJacobiGran, &t.dMsg, &t.dGroups.buf, &t.dContactTail.buf, &t.dJointTail.buf, &t.dStripA.buf, &t.dStripB.buf,
-							&t.dResident.buf};
-	for (const DevBuf* b : bufs)
-	{
-		const size_t bytes = std::max<size_t>(b->bytes, 4096);
-		void* p = nullptr;
-		HIP_TRY(hipMalloc(&p, bytes));
-		if (!devPoolGive(p, bytes))
+	int rc = S2AMD_OK;
+	bool full = false;
+	forEachStructureBuf(t, [&](const DevBuf& b) {
+		if (rc == S2AMD_OK && !full)
 		{
-			(void)hipFree(p);
-			break;
+			rc = poolStock(std::max<size_t>(b.bytes, 4096), &full);
 		}
+	});
+	if (rc)
+	{
+		return rc;
 	}
 	void* pinned = nullptr;
 	const size_t pinnedBytes = 8192 * sizeof(uint4);
@@ -657,7 +652,7 @@ int asyncPrewarm(s2amdSolver* s, int solverType)
 		return S2AMD_OK;
 	}
 	const int requestedWas = s->asyncRequested;
-	int rc = asyncRequest(s, solverType, false, true);
+	rc = asyncRequest(s, solverType, false, true);
 	if (rc)
 	{
 		return rc;

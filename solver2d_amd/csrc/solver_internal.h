@@ -131,6 +131,67 @@ struct DevBuf
 	}
 };
 
+// pinned host block whose contents nobody keeps: it grows by free-and-allocate.  Like DevBuf it owns nothing (solvers are copied)
+struct PinnedBuf
+{
+	void* p = nullptr;
+	size_t bytes = 0;
+
+	// at least `need` bytes: a smaller block is freed and one of `want` bytes takes its place
+	int grow(size_t need, size_t want)
+	{
+		if (bytes >= need)
+		{
+			return S2AMD_OK;
+		}
+		release();
+		HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+		bytes = want;
+		return S2AMD_OK;
+	}
+	void release()
+	{
+		if (p)
+		{
+			(void)hipHostFree(p);
+		}
+		p = nullptr;
+		bytes = 0;
+	}
+};
+
+// A pinned stage and the event of the copy that reads it: the caller's data is copied into the stage, so the caller may reuse its
+// memory at once and the copy to the device is a true asynchronous one.  begin, fill buf.p, hipMemcpyAsync from it, record.
+struct PinnedStage
+{
+	PinnedBuf buf;
+	hipEvent_t copied = nullptr;
+
+	// the copy of the call before may still be reading the stage: its event is waited for before the block is written or replaced
+	int begin(size_t need, size_t want)
+	{
+		if (!copied)
+		{
+			HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+		}
+		else
+		{
+			HIP_TRY(hipEventSynchronize(copied));
+		}
+		return buf.grow(need, want);
+	}
+	hipError_t record(hipStream_t st) { return hipEventRecord(copied, st); }
+	void release()
+	{
+		buf.release();
+		if (copied)
+		{
+			(void)hipEventDestroy(copied);
+			copied = nullptr;
+		}
+	}
+};
+
 
 bool isPositionSolver(int type);
 bool rotIsFixedPoint(float s, float c);
@@ -331,6 +392,8 @@ struct IncrementalStrips
 // structure knows it, every table derived from it and their device copies, the SoA families (carved per structure), the captured step
 // graph.  Kept apart from the rest of the solver so that a build can run on a copy of the solver in a worker thread while the steps go
 // on with the structure they have, and its result be adopted by swapping this part (solver_async.cpp).
+// A DevBuf added here is added to forEachStructureBuf below the struct: a copy forgets, a copy's end and s2amd_destroy release, and
+// the workers' pool is stocked by that list alone.
 struct SolverStructure
 {
 	// host shadows of the graph structure (refreshed by every upload)
@@ -455,6 +518,18 @@ struct SolverStructure
 	int graphLaunches = 0;
 };
 
+// every DevBuf of the structure part, in the order asyncPrewarm stocks the workers' pool in
+template <typename F> void forEachStructureBuf(SolverStructure& t, F&& f)
+{
+	for (DevBuf* b : {&t.dWatched, &t.dBodyFlags, &t.soaBodies, &t.soaContacts, &t.soaJoints, &t.dContactIndex, &t.dJointIndex, &t.dContactLocal, &t.dJointLocal,
+					  &t.dAdjOffsets, &t.dAdjList, &t.dAdjHeavy, &t.dPatches, &t.dJointAdjRange, &t.dJointAdjList, &t.dResidentDesc, &t.dResidentOps, &t.dStripLean,
+					  &t.dPersist, &t.dGranules, &t.dOverflowBodies, &t.dPersistOps, &t.dJacobi, &t.dJacobiGran, &t.dMsg, &t.dGroups.buf, &t.dContactTail.buf,
+					  &t.dJointTail.buf, &t.dStripA.buf, &t.dStripB.buf, &t.dResident.buf})
+	{
+		f(*b);
+	}
+}
+
 // What the host keeps for one report of the resident world (report_host.cpp).  All its device memory is one block, carved by the
 // report's layout function and sized by its prepare (at s2amd_world_upload and when its setter turns it on): a step allocates nothing
 // and waits for nothing -- the getters do.
@@ -472,6 +547,8 @@ struct ReportState
 struct AsyncBuild;
 
 // ... and the rest: the device, the wire arrays and the world chain's arrays, what the host knows of them, the options, the plan.
+// A DevBuf added here is added to forEachRestBuf below the struct (s2amd_destroy releases that list); a report's block is its
+// ReportState's (reportsRelease), the trees' are DeviceTrees' (treesFree).  A pinned block or stage is added to s2amd_destroy.
 struct SolverRest
 {
 	int device = 0;
@@ -502,13 +579,12 @@ struct SolverRest
 	int shapeCapacity = 0, liveShapes = 0, jointedCount = 0;
 	bool worldResident = false;
 	int* hostWorldSummary = nullptr; // pinned: the per-step counters of both stages
-	uint8_t* hostSlotStage = nullptr; // pinned, contactCapacity bytes: where the per-slot byte arrays land (syncDeadSlots, fetchPointCounts) -- a copy
-									  // straight into a std::vector's pageable memory cost 0.8 ms per call at 140k slots, 7.5 ms the first time (r5)
-	size_t hostSlotStageBytes = 0;
+	PinnedBuf slotStage; // contactCapacity bytes: where the per-slot byte arrays land (syncDeadSlots, fetchPointCounts) -- a copy
+						 // straight into a std::vector's pageable memory cost 0.8 ms per call at 140k slots, 7.5 ms the first time (r5)
 	// s2amd_world_step's speculative read-back for s2amd_world_download_step (a caller that set a refit order will ask for the poses
 	// and the re-inflated boxes right after the step): enqueued behind stage 4, landed by the step's own synchronisation
-	char* hostStepBack = nullptr; // pinned: {count, 0, 0, 0}, `stepBackBoxes` s2amdMovedBox records, then bodyCapacity poses at stepBackPoseOffset
-	size_t hostStepBackBytes = 0, stepBackPoseOffset = 0;
+	PinnedBuf stepBackStage; // {count, 0, 0, 0}, `stepBackBoxes` s2amdMovedBox records, then bodyCapacity poses at stepBackPoseOffset
+	size_t stepBackPoseOffset = 0;
 	int stepBackBoxes = 0;
 	bool stepBackValid = false;
 	bool stepBackListFresh = false; // this step's list of re-inflated shapes is on the device (enqueueStepBack ran; launchTreeEnlarge reads it)
@@ -537,9 +613,7 @@ struct SolverRest
 	DevBuf dQuery;			// the queries on the resident world (query_host.h: scene_query.hip, proximity_query.hip, contact_query.hip, shape_cast.hip): the records, the passes' scratch and the results of one call, carved from offset 0; grows on demand, kept between calls (sensor_report.hip writes a list longer than its block's room here too, for the getter that asked)
 	std::vector<int32_t> hQueryStage; // ... where a slot-list call's {offsets, entries[, distances]} land before they are split into the caller's arrays
 	DevBuf dEdit;					  // world edits (world_edit.hip): the skip count, the staged list, the sort's keys and scratch of one call; grows on demand, kept between calls
-	char* hostEditStage = nullptr;	  // ... the pinned copy of the caller's list the device copy reads, and the event of that copy (the next call waits for it before it overwrites the stage)
-	size_t hostEditStageBytes = 0;
-	hipEvent_t evEditStaged = nullptr;
+	PinnedStage editStage;			  // ... the pinned copy of the caller's list the device copy reads
 	std::vector<uint32_t> hEditBodyStamp, hEditJointStamp; // ... the last call (editGeneration) that edited a body / joint slot: how a call notices a target that occurs twice
 	uint32_t editGeneration = 0;
 	DevBuf dRefitOrder, dStepBack; // s2amd_world_set_refit_order; staging of s2amd_world_download_step {count, moved boxes} and the poses
@@ -608,9 +682,7 @@ struct SolverRest
 	bool fieldAdjValid = false;		 // ... built at the first field use after an upload (s2amd_world_upload clears this)
 	long fieldAdjBuilds = 0;		 // how often it was built, since s2amd_create
 	bool fieldStatesValid = false;	 // a step has applied the persistent list since it was set and since the last upload
-	char* hostFieldStage = nullptr;	 // the pinned copy of a one-shot call's list the device copy reads, and the event of that copy
-	size_t hostFieldStageBytes = 0;
-	hipEvent_t evFieldStaged = nullptr;
+	PinnedStage fieldStage;			 // the pinned copy of a one-shot call's list the device copy reads
 	// actuators (actuators.hip; s2amd_world_set_actuators, s2amd_world_set_actions, s2amd_world_import_actions): a write in front of the
 	// persistent fields, kept and released beside them
 	std::vector<s2amdActuator> hActuators; // the persistent list as the caller set it: held across uploads
@@ -619,9 +691,7 @@ struct SolverRest
 	DevBuf dActuators;					   // {two sets of status counts, the list, the order by target, the terms, the states, the action buffer}, written by the setter
 	long actuatorPasses = 0;			   // passes since the list was set: pass k counts into set k & 1 and clears the other
 	bool actuatorStatesValid = false;	   // a step has applied the list since it was set and since the last upload
-	float* hostActionStage = nullptr;	   // the pinned copy of s2amd_world_set_actions' values the device copy reads, and the event of that copy
-	size_t hostActionStageBytes = 0;
-	hipEvent_t evActionStaged = nullptr;
+	PinnedStage actionStage;			   // the pinned copy of s2amd_world_set_actions' values the device copy reads
 	// observers (observers.hip; s2amd_world_set_observers, s2amd_world_set_observation_report: S2AMD_OBSERVATION_REPORT_*): the ninth of a
 	// step.  Its ReportState carries the flags alone: the device block belongs to the list, as the actuators', and is written by the setter
 	ReportState observationReport;
@@ -652,8 +722,7 @@ struct SolverRest
 	long resetPasses = 0;		  // passes since the counters went to zero: pass k counts into set k & 1, reads agent records k & 1 and writes the other
 	bool resetCountsKnown = false; // a pass has run (or found its source off) since the list was set and since the last upload
 	bool resetSourceOff = false;  // ... and it was a step whose episode pass did not run: nothing was enqueued
-	int32_t* hostResetStage = nullptr; // the pinned copy of a one-shot call's triggers the device copy reads, and the event of that copy
-	hipEvent_t evResetStaged = nullptr;
+	PinnedStage resetStage;		  // the pinned copy of a one-shot call's triggers the device copy reads: one word per agent the header allows, allocated once
 	int optIncremental = 1; // created contacts are placed into the existing structure when they fit (0: always rebuild)
 	// A created contact that cannot be placed (an LDS group or a strip owns one of its bodies, or one of them is a hub) and has
 	// no manifold points yet is only WATCHED: no entry in the structure -- it would be a no-op there -- until stage 3 finds
@@ -787,9 +856,29 @@ struct SolverRest
 	float asyncWaitMs = 0.0f;
 };
 
+// every DevBuf of the rest that is not a report's block, in declaration order
+template <typename F> void forEachRestBuf(SolverRest& r, F&& f)
+{
+	for (DevBuf* b : {&r.dBodies, &r.dContacts, &r.dJoints, &r.dBodiesSaved, &r.dShapes, &r.dPairs, &r.dOrigins, &r.dStatus, &r.dPointBytes, &r.dWorldSummary,
+					  &r.dJointedKeys, &r.dContactStage, &r.dPairScratch, &r.dPairKeys, &r.dScanTmp, &r.dOps, &r.dSeparated, &r.dPairLog, &r.dShapeBoxes, &r.dQuery,
+					  &r.dEdit, &r.dRefitOrder, &r.dStepBack, &r.dSlotBytes, &r.dMetricsRing, &r.dFieldList, &r.dFieldCall, &r.dFieldAdj, &r.dActuators,
+					  &r.dObservers, &r.dEpisodes, &r.dResets, &r.dResetMark, &r.dGatherIndex})
+	{
+		f(*b);
+	}
+}
+
 struct s2amdSolver : SolverStructure, SolverRest
 {
 };
+
+// the export event of a slot 0..3 (s2amd_export_wait waits for it), created at its first use
+inline hipError_t exportEvent(s2amdSolver* s, int slot, hipEvent_t* event)
+{
+	const hipError_t e = s->evExport[slot] ? hipSuccess : hipEventCreateWithFlags(&s->evExport[slot], hipEventDisableTiming);
+	*event = s->evExport[slot];
+	return e;
+}
 
 // The constraint graph changed (an upload, a manifold that gained or lost its points, a contact slot written): the
 // structure is rebuilt at the next step.  The strip structure costs several milliseconds of host time (more with
@@ -917,32 +1006,27 @@ int gridReportPrepare(s2amdSolver* s);
 int gridReportEnqueue(s2amdSolver* s, const s2amdStepParams* params);
 int observationPrepare(s2amdSolver* s); // (observers.hip: re-bases the history; the block is the setter's)
 int observationEnqueue(s2amdSolver* s, const s2amdStepParams* params);
-void observersRelease(s2amdSolver* s);
 // What the episode pass reads of the observers in front of it: the ring on the device, nullptr when the observation report did not run
 // this step or no list is set; channels, frames (those of the list whether or not it reported, 0 with no list) and the row of frame 0.
 const float* observationRing(const s2amdSolver* s, int* channels, int* frames, int* head);
 int episodePrepare(s2amdSolver* s); // (episodes.hip: re-bases the accounting; the block is the setter's)
 int episodeEnqueue(s2amdSolver* s, const s2amdStepParams* params);
-void episodesRelease(s2amdSolver* s);
 // What the reset pass reads of the episodes in front of it: the flags word per agent on the device, nullptr when the episode pass did
 // not run this step or no list is set; *agents: the episode list's.
 const int* episodeStepFlags(const s2amdSolver* s, int* agents);
 int resetPrepare(s2amdSolver* s); // (resets.hip: the mark bytes for the world just uploaded, the counters to zero; the block is the setter's)
 int resetEnqueue(s2amdSolver* s, const s2amdStepParams* params);
-void resetsRelease(s2amdSolver* s);
 // What the observation pass reads of the reports in front of it, on the device: nullptr means "not this step" (the source report's
 // stepFlags), and the count is that of the list whether or not it reported.
 const s2amdBodyContactSum* contactReportBodySums(const s2amdSolver* s); // contact_report.hip: bodyCapacity records
 const float* rayReportRanges(const s2amdSolver* s, int* rayCount);		 // ray_report.hip: one float per ray
 const float* actuatorsActionBuffer(const s2amdSolver* s, int* channels); // actuators.hip: nullptr with no list
-// force_field.hip: the persistent list in front of stage 3 (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
+// force_field.hip: the persistent list in front of stage 3 (nothing with an empty list); what s2amd_world_upload does
 int fieldsStepEnqueue(s2amdSolver* s);
 void fieldsForgetWorld(s2amdSolver* s);
-void fieldsRelease(s2amdSolver* s);
-// actuators.hip: the persistent list in front of the fields (nothing with an empty list); what s2amd_world_upload and s2amd_destroy do
+// actuators.hip: the persistent list in front of the fields (nothing with an empty list); what s2amd_world_upload does
 int actuatorsStepEnqueue(s2amdSolver* s);
 void actuatorsForgetWorld(s2amdSolver* s);
-void actuatorsRelease(s2amdSolver* s);
 
 // report_host.cpp: the walks over the table ...
 void reportsForget(s2amdSolver* s);									 // no report is of the last step any more (a new upload)

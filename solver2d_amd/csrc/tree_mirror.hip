@@ -1062,6 +1062,11 @@ void treesFree(s2amdSolver* s)
 {
 	if (s->trees)
 	{
+		// (a rebuild may still be in flight on the trees' own stream -- a step that returned early never joined it: drained before its blocks go)
+		if (s->trees->stream)
+		{
+			(void)hipStreamSynchronize(s->trees->stream);
+		}
 		for (DevBuf& b : s->trees->block)
 		{
 			b.release();
@@ -1070,7 +1075,6 @@ void treesFree(s2amdSolver* s)
 		s->trees->dRefitPos.release();
 		if (s->trees->stream)
 		{
-			(void)hipStreamSynchronize(s->trees->stream);
 			(void)hipStreamDestroy(s->trees->stream);
 			(void)hipEventDestroy(s->trees->evStart);
 			(void)hipEventDestroy(s->trees->evDone);

@@ -237,16 +237,11 @@ int enqueueStepBack(s2amdSolver* s)
 	}
 	const size_t hostPose = ((16 + (size_t)guess * sizeof(s2amdMovedBox)) + 255) & ~size_t(255);
 	const size_t hostBytes = hostPose + (size_t)nb * sizeof(float4);
-	if (s->hostStepBackBytes < hostBytes)
+	if ((rc = s->stepBackStage.grow(hostBytes, hostBytes + hostBytes / 2)) != 0)
 	{
-		if (s->hostStepBack)
-		{
-			(void)hipHostFree(s->hostStepBack);
-			s->hostStepBack = nullptr, s->hostStepBackBytes = 0;
-		}
-		HIP_TRY(hipHostMalloc((void**)&s->hostStepBack, hostBytes + hostBytes / 2, hipHostMallocDefault));
-		s->hostStepBackBytes = hostBytes + hostBytes / 2;
+		return rc;
 	}
+	char* hostBack = (char*)s->stepBackStage.p;
 	char* base = (char*)s->dStepBack.p;
 	const int n = s->refitOrderCount;
 	const int tiles = (n + S2_BLOCK - 1) / S2_BLOCK;
@@ -260,8 +255,8 @@ int enqueueStepBack(s2amdSolver* s)
 		(const float*)s->dOrigins.p, nb, (float4*)(base + poseOffset));
 	HIP_TRY(hipGetLastError());
 	s->stepBackListFresh = true; // (launchTreeEnlarge: the re-inflated shapes are a list on the device from here on)
-	HIP_TRY(hipMemcpyAsync(s->hostStepBack, base, 16 + (size_t)guess * sizeof(s2amdMovedBox), hipMemcpyDeviceToHost, s->stream));
-	HIP_TRY(hipMemcpyAsync(s->hostStepBack + hostPose, base + poseOffset, (size_t)nb * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipMemcpyAsync(hostBack, base, 16 + (size_t)guess * sizeof(s2amdMovedBox), hipMemcpyDeviceToHost, s->stream));
+	HIP_TRY(hipMemcpyAsync(hostBack + hostPose, base + poseOffset, (size_t)nb * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
 	s->stepBackBoxes = guess;
 	s->stepBackPoseOffset = hostPose;
 	return S2AMD_OK;
@@ -359,11 +354,11 @@ int syncDeadSlots(s2amdSolver* s)
 	slotBytesKernel<<<gridFor((size_t)nc), dim3(S2_BLOCK), 0, s->stream>>>((const s2amdPairState*)s->dPairs.p, (const uint8_t*)s->dPointBytes.p, nc,
 																			 (uint8_t*)s->dSlotBytes.p);
 	HIP_TRY(hipGetLastError());
-	if (s->hostSlotStage && s->hostSlotStageBytes >= (size_t)nc)
+	if (s->slotStage.p && s->slotStage.bytes >= (size_t)nc)
 	{
-		HIP_TRY(hipMemcpyAsync(s->hostSlotStage, s->dSlotBytes.p, (size_t)nc, hipMemcpyDeviceToHost, s->stream));
+		HIP_TRY(hipMemcpyAsync(s->slotStage.p, s->dSlotBytes.p, (size_t)nc, hipMemcpyDeviceToHost, s->stream));
 		HIP_TRY(hipStreamSynchronize(s->stream));
-		memcpy(s->hSlotBytes.data(), s->hostSlotStage, (size_t)nc);
+		memcpy(s->hSlotBytes.data(), s->slotStage.p, (size_t)nc);
 	}
 	else
 	{
@@ -402,11 +397,11 @@ int fetchPointCounts(s2amdSolver* s)
 			s->hPointBytes[(size_t)i] = s->hSlotBytes[(size_t)i] == 0xff ? 0 : s->hSlotBytes[(size_t)i];
 		}
 	}
-	else if (s->hostSlotStage && s->hostSlotStageBytes >= (size_t)nc)
+	else if (s->slotStage.p && s->slotStage.bytes >= (size_t)nc)
 	{
-		HIP_TRY(hipMemcpyAsync(s->hostSlotStage, s->dPointBytes.p, (size_t)nc, hipMemcpyDeviceToHost, s->stream));
+		HIP_TRY(hipMemcpyAsync(s->slotStage.p, s->dPointBytes.p, (size_t)nc, hipMemcpyDeviceToHost, s->stream));
 		HIP_TRY(hipStreamSynchronize(s->stream));
-		memcpy(s->hPointBytes.data(), s->hostSlotStage, (size_t)nc);
+		memcpy(s->hPointBytes.data(), s->slotStage.p, (size_t)nc);
 	}
 	else
 	{
@@ -634,16 +629,9 @@ int s2amd_world_upload(s2amdSolver* s, const s2amdBody* bodies, int32_t bodyCapa
 		// (a stream for the first worker-thread build, made now while nothing is stepping: creating one later stalls the step that asks;
 		// and the staging block of syncDeadSlots, whose first hipMalloc cost the first request 3 ms)
 		workerStreamGive(workerStreamTake());
-		if (s->hostSlotStageBytes < (size_t)contactCapacity)
+		if ((rc = s->slotStage.grow((size_t)contactCapacity, std::max<size_t>((size_t)contactCapacity, 4096))) != 0)
 		{
-			if (s->hostSlotStage)
-			{
-				(void)hipHostFree(s->hostSlotStage);
-				s->hostSlotStage = nullptr, s->hostSlotStageBytes = 0;
-			}
-			const size_t want = std::max<size_t>((size_t)contactCapacity, 4096);
-			HIP_TRY(hipHostMalloc((void**)&s->hostSlotStage, want, hipHostMallocDefault));
-			s->hostSlotStageBytes = want;
+			return rc;
 		}
 		// (and the patch list's buffers -- solver_incremental.cpp: incrementalFlush: the first placed contact used to make them, 0.8 ms)
 		if (s->hostPatches == nullptr)
@@ -1178,16 +1166,16 @@ int s2amd_world_download_step(s2amdSolver* s, float* poses, int32_t bodyCapacity
 	{
 		return fail(S2AMD_E_CAPACITY, "moved-box array too small");
 	}
-	if (s->stepBackValid && s->lastMovedCount <= s->stepBackBoxes && ((const int32_t*)s->hostStepBack)[0] == s->lastMovedCount)
+	if (s->stepBackValid && s->lastMovedCount <= s->stepBackBoxes && ((const int32_t*)s->stepBackStage.p)[0] == s->lastMovedCount)
 	{
 		// the step brought them along (enqueueStepBack)
 		if (s->lastMovedCount > 0)
 		{
-			memcpy(moved, s->hostStepBack + 16, (size_t)s->lastMovedCount * sizeof(s2amdMovedBox));
+			memcpy(moved, (const char*)s->stepBackStage.p + 16, (size_t)s->lastMovedCount * sizeof(s2amdMovedBox));
 		}
 		if (poses && s->bodyCapacity > 0)
 		{
-			memcpy(poses, s->hostStepBack + s->stepBackPoseOffset, (size_t)s->bodyCapacity * sizeof(float4));
+			memcpy(poses, (const char*)s->stepBackStage.p + s->stepBackPoseOffset, (size_t)s->bodyCapacity * sizeof(float4));
 		}
 		return S2AMD_OK;
 	}

@@ -157,7 +157,7 @@ int checkAndStage(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count, in
 		s->editGeneration = 0;
 	}
 	const uint32_t generation = ++s->editGeneration;
-	s2amdWorldEdit* stage = (s2amdWorldEdit*)s->hostEditStage;
+	s2amdWorldEdit* stage = (s2amdWorldEdit*)s->editStage.buf.p;
 	bool repeated = false;
 	for (int32_t i = 0; i < count; ++i)
 	{
@@ -205,25 +205,9 @@ int s2amd_world_edit(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count,
 	// the pinned stage: the caller's list is copied while it is checked, so the caller may reuse it at once and the copy to the device
 	// is a true asynchronous one.  The copy of the call before may still be reading the stage: its event is waited for first.
 	const size_t listBytes = (size_t)count * sizeof(s2amdWorldEdit);
-	if (!s->evEditStaged)
+	if (int rc = s->editStage.begin(listBytes, std::max(reportRound(listBytes + listBytes / 2), (size_t)4096)))
 	{
-		HIP_TRY(hipEventCreateWithFlags(&s->evEditStaged, hipEventDisableTiming));
-	}
-	else
-	{
-		HIP_TRY(hipEventSynchronize(s->evEditStaged));
-	}
-	if (s->hostEditStageBytes < listBytes)
-	{
-		if (s->hostEditStage)
-		{
-			(void)hipHostFree(s->hostEditStage);
-			s->hostEditStage = nullptr;
-			s->hostEditStageBytes = 0;
-		}
-		const size_t want = std::max(reportRound(listBytes + listBytes / 2), (size_t)4096);
-		HIP_TRY(hipHostMalloc((void**)&s->hostEditStage, want, hipHostMallocDefault));
-		s->hostEditStageBytes = want;
+		return rc;
 	}
 	int32_t bad = -1;
 	const int repeated = checkAndStage(s, edits, count, &bad);
@@ -255,8 +239,8 @@ int s2amd_world_edit(s2amdSolver* s, const s2amdWorldEdit* edits, int32_t count,
 	{
 		HIP_TRY(hipMemsetAsync(base, 0, sizeof(int), st));
 	}
-	HIP_TRY(hipMemcpyAsync(base + listAt, s->hostEditStage, listBytes, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipEventRecord(s->evEditStaged, st));
+	HIP_TRY(hipMemcpyAsync(base + listAt, s->editStage.buf.p, listBytes, hipMemcpyHostToDevice, st));
+	HIP_TRY(s->editStage.record(st));
 	s2amdBody* bodies = (s2amdBody*)s->dBodies.p;
 	s2amdJoint* joints = (s2amdJoint*)s->dJoints.p;
 	if (!repeated)

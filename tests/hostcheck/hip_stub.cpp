@@ -2,7 +2,8 @@
 // partition, incremental placement, the world chain's bookkeeping, the reference-side binding's pack / unpack -- can run under
 // AddressSanitizer + UndefinedBehaviorSanitizer on a box without a GPU (tests/hostcheck/Makefile, tests/test_hostcheck.py).
 // "Device" memory is heap memory (so an out-of-bounds hipMemcpy into a device table is an ASan report), copies are memcpy,
-// streams / events / graphs are inert handles, and kernels are never run: hipLaunchKernel returns success and does nothing --
+// graphs are inert handles, a stream or an event is a one-byte heap block that its destroy call frees (so one that is never destroyed
+// is a leak and one destroyed twice an ASan report), and kernels are never run: hipLaunchKernel returns success and does nothing --
 // with S2_HOSTCHECK_TRACE_LAUNCHES set it prints one line per launch first: "LAUNCH <kernel symbol> grid <x> block <x> lds <bytes>"
 // (which kernel the host picked and the dynamic LDS it asked for are host decisions: tests/test_wide_island_kinds_host.py).
 // While S2_HOSTCHECK_TRACE_CALLS is set (looked up at every call, so a program can switch it) the stub prints what a call sequence
@@ -248,15 +249,19 @@ hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t)
 
 hipError_t hipStreamCreateWithFlags(hipStream_t* stream, unsigned int)
 {
-	*stream = (hipStream_t)s_dummy;
+	*stream = (hipStream_t)malloc(1);
 	return hipSuccess;
 }
 hipError_t hipStreamCreate(hipStream_t* stream)
 {
-	*stream = (hipStream_t)s_dummy;
+	*stream = (hipStream_t)malloc(1);
 	return hipSuccess;
 }
-hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t stream)
+{
+	free(stream);
+	return hipSuccess;
+}
 hipError_t hipStreamSynchronize(hipStream_t)
 {
 	if (traceCalls())
@@ -284,15 +289,19 @@ hipError_t hipDeviceCanAccessPeer(int* can, int, int)
 hipError_t hipDeviceEnablePeerAccess(int, unsigned int) { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* event)
 {
-	*event = (hipEvent_t)s_dummy;
+	*event = (hipEvent_t)malloc(1);
 	return hipSuccess;
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t* event, unsigned)
 {
-	*event = (hipEvent_t)s_dummy;
+	*event = (hipEvent_t)malloc(1);
 	return hipSuccess;
 }
-hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t event)
+{
+	free(event);
+	return hipSuccess;
+}
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t)

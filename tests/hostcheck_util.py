@@ -109,7 +109,7 @@ def assert_kernel_resources(target, report, kernels, floor, every_row=False, tot
 
 def run_sanitized(tmp_path, source, marker, timeout=600, trace_calls=False):
     """tests/hostcheck/<source> as a stand-alone program under ASan + UBSan on the stand-in HIP runtime: built, run, and clean --
-    exit code 0, `marker` in its output, no sanitizer report.  trace_calls: the stand-in's call trace on, and stderr kept apart so
+    exit code 0, `marker` in its output, no sanitizer report, nothing leaked.  trace_calls: the stand-in's call trace on, and stderr kept apart so
     that stdout is the program's transcript.  Returns stdout's bytes."""
     subprocess.check_call(["make", "-s", "-j8", "-C", HOSTCHECK])
     build = os.path.join(HOSTCHECK, "_build")
@@ -120,7 +120,7 @@ def run_sanitized(tmp_path, source, marker, timeout=600, trace_calls=False):
                            "-x", "hip", os.path.join(HOSTCHECK, source), "-o", exe, "-L", build, "-ls2amd_hostcheck",
                            "-Wl,-rpath," + build, "-Wl,-rpath," + os.path.dirname(asan_runtime())])
     env = dict(os.environ)
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0:exitcode=23"
+    env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=0:exitcode=23"
     env["UBSAN_OPTIONS"] = "print_stacktrace=1:halt_on_error=1:exitcode=24"
     if trace_calls:
         env["S2_HOSTCHECK_TRACE_CALLS"] = "1"
@@ -129,7 +129,7 @@ def run_sanitized(tmp_path, source, marker, timeout=600, trace_calls=False):
     err = p.stderr.decode(errors="replace") if trace_calls else ""
     tail = (out[-2000:], err[-4000:]) if trace_calls else out[-4000:]
     assert p.returncode == 0 and marker in out, tail
-    assert "AddressSanitizer" not in out + err and "runtime error" not in out + err, tail
+    assert "AddressSanitizer" not in out + err and "LeakSanitizer" not in out + err and "runtime error" not in out + err, tail
     return p.stdout
 
 
