@@ -10,9 +10,10 @@
 // not depend on thread timing), by swapping the SolverStructure part of the two solver objects.
 //
 // What happens to the graph between request and adoption is logged and replayed on the copy first: a destroyed contact leaves it as it
-// leaves the live structure (incrementalRemove), a created one is placed or deferred exactly as s2amd_world_set_contacts does it on the
-// live structure (incrementalApply / deferCreated).  Anything the copy cannot take -- a contact that fits nowhere, a watched manifold
-// that gained its points, an upload, an option that changes the structure -- drops the build; the next step that finds one due asks again.
+// leaves the live structure, a created one is placed or deferred as s2amd_world_set_contacts does it on the live structure -- both
+// through the front of solver_incremental.cpp (destroyedContact, routeCreated).  Anything the copy cannot take -- a contact that fits
+// nowhere, a watched manifold that gained its points, an upload, an option that changes the structure -- drops the build; the next
+// step that finds one due asks again.
 #include "solver_internal.h"
 
 #include <atomic>
@@ -685,16 +686,10 @@ static bool replay(s2amdSolver* c, const std::vector<AsyncBuild::Event>& log)
 		}
 		if (e.kind == 1)
 		{
-			if (c->hContactEdge[(size_t)e.slot])
-			{
-				c->hContactDead[(size_t)e.slot] = 1;
-				unwatchSlot(c, e.slot);
-				const int32_t one = e.slot;
-				incrementalRemove(c, &one, 1);
-			}
+			destroyedContact(c, e.slot);
 			continue;
 		}
-		if (canDeferCreated(c, e.slot, e.a, e.b))
+		if (routeCreated(c, e.slot, e.a, e.b, false, 0u) == CREATED_WATCH)
 		{
 			deferCreated(c, e.slot, e.a, e.b);
 			continue;
@@ -704,10 +699,7 @@ static bool replay(s2amdSolver* c, const std::vector<AsyncBuild::Event>& log)
 		{
 			return false;
 		}
-		c->hContactA[(size_t)e.slot] = e.a;
-		c->hContactB[(size_t)e.slot] = e.b;
-		c->hContactEdge[(size_t)e.slot] = 1;
-		c->hContactDead[(size_t)e.slot] = 0;
+		commitEdge(c, e.slot, e.a, e.b);
 	}
 	return incrementalFlush(c) == S2AMD_OK && hipStreamSynchronize(c->stream) == hipSuccess;
 }
@@ -796,8 +788,7 @@ bool asyncAdopt(s2amdSolver* s, int solverType, int* rcOut)
 		{
 			if (c->hContactWatched[(size_t)i] && s->hContactPoints[(size_t)i] > 0 && c->inc.positionOfSlot[(size_t)i] == -1)
 			{
-				if (c->hContactEdge[(size_t)i] && !c->hContactDead[(size_t)i] && c->stripInc.valid &&
-					(stripCanPlace(c, c->hContactA[(size_t)i], c->hContactB[(size_t)i]) || overflowCanPlace(c, c->hContactA[(size_t)i], c->hContactB[(size_t)i])))
+				if (c->hContactEdge[(size_t)i] && !c->hContactDead[(size_t)i] && flipPlaceable(c, c->hContactA[(size_t)i], c->hContactB[(size_t)i], c->stripInc.valid ? FLIP_STRIPS : 0u))
 				{
 					flipped.push_back(ContactChange{i, c->hContactA[(size_t)i], c->hContactB[(size_t)i]});
 				}

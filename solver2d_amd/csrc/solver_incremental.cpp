@@ -1,14 +1,13 @@
-// Incremental updates of the constraint-graph structure: a created contact gets a place in the existing sweep order
-// instead of a rebuild (IncrementalGlobal in solver_internal.h says what is kept and why the launch sequence survives).
-//
-// The reference creates and destroys contacts every step (src/world.c:125-168 -> src/contact.c:137-229).  Destruction
-// never touches the structure here (the entry lingers as a no-op until the next rebuild); this file handles creation:
-// for a new contact between bodies a and b of the GLOBAL part
+// Incremental updates of the constraint-graph structure: a created contact gets a place in the existing sweep order instead of a
+// rebuild, and a destroyed one gives its place back (IncrementalGlobal and IncrementalStrips in solver_internal.h say what is kept and
+// why the launch sequence survives).  The reference creates and destroys contacts every step (src/world.c:125-168 ->
+// src/contact.c:137-229).  A new contact between bodies a and b of the GLOBAL part gets
 //   * colour = the lowest parallel colour batch that is unused on both writable bodies AND still has a free position;
 //   * position = the lowest free position of that batch (its contactIndex goes from -1 to the contact's pool slot);
-//   * its two entries (k << 1 | side) are inserted into the bodies' incidence lists at their place in sweep order, so the
-//     body-centric warm start and the Jacobi apply keep adding in sweep order.
+//   * its two entries (k << 1 | side) in the bodies' incidence lists at their place in sweep order, so the body-centric warm start and
+//     the Jacobi apply keep adding in sweep order.
 // The result is a proper colouring and a valid sweep order like any other: the oracle sweeps in it (parity link L2).
+// The end of the file is the front the callers use: what becomes of a created, destroyed or flipped contact.
 #include "solver_internal.h"
 
 #include <cstddef>
@@ -16,6 +15,10 @@
 
 namespace
 {
+
+// (defined with the front at the end of the file)
+bool ownedByLdsGroup(const s2amdSolver* s, int body);
+bool overflowCanPlace(const s2amdSolver* s, int a, int b);
 
 struct Patcher
 {
@@ -33,7 +36,38 @@ struct Patcher
 	}
 	void listEntry(int e) { word(s->dAdjList.p, (size_t)e, (uint32_t)inc.adjList[(size_t)e]); }
 	void heavyEntry(int i) { word(s->dAdjHeavy.p, (size_t)i, (uint32_t)inc.heavy[(size_t)i]); }
+	// position k of the sweep order becomes the entry of contact `slot`; `local`: with these group-local body slots (the tail, a strip or
+	// seam round, the overflow region -- a colour batch's kernels read the bodies' pool slots instead)
+	void writeEntry(int k, int slot, const int2* local = nullptr)
+	{
+		s->contacts.order[(size_t)k] = slot;
+		word(s->dContactIndex.p, (size_t)k, (uint32_t)slot);
+		if (local)
+		{
+			s->contacts.local[(size_t)k] = *local;
+			word(s->dContactLocal.p, 2 * (size_t)k, (uint32_t)local->x);
+			word(s->dContactLocal.p, 2 * (size_t)k + 1, (uint32_t)local->y);
+		}
+	}
+	// ... and a free position again: an empty record
+	void clearEntry(int k, bool localToo)
+	{
+		s->contacts.order[(size_t)k] = -1;
+		word(s->dContactIndex.p, (size_t)k, (uint32_t)-1);
+		if (localToo)
+		{
+			s->contacts.local[(size_t)k] = make_int2(0, 0);
+			word(s->dContactLocal.p, 2 * (size_t)k, 0u);
+			word(s->dContactLocal.p, 2 * (size_t)k + 1, 0u);
+		}
+	}
 };
+
+bool placeTrace()
+{
+	static const bool on = getenv("S2AMD_DEBUG_PLACE") != nullptr;
+	return on;
+}
 
 bool writable(const s2amdSolver* s, int body)
 {
@@ -183,8 +217,7 @@ bool stripHome(const s2amdSolver* s, int a, int b, int& table, int& group, int& 
 {
 	const char* why = "";
 	const bool ok = stripHomeWhy(s, a, b, table, group, la, lb, why, mover);
-	static const bool debug = getenv("S2AMD_DEBUG_PLACE") != nullptr;
-	if (!ok && debug)
+	if (!ok && placeTrace())
 	{
 		const IncrementalStrips& m = s->stripInc;
 		fprintf(stderr, "[s2amd] no strip home for (%d, %d): %s (strips %d, %d)\n", a, b, why, m.ownerStrip[(size_t)a], m.ownerStrip[(size_t)b]);
@@ -324,24 +357,22 @@ static void stripAdopt(s2amdSolver* s, Patcher& p, int body, int to)
 	const int* ids = s->dStripA.view.bodyIds;
 	const int from = m.ownerStrip[(size_t)body], fromSlot = m.ownerSlot[(size_t)body];
 	// the old entry stays where it is, as a read-only copy nothing refers to
-	std::vector<int>& fromMoved = m.movedList[(size_t)from];
-	if (fromMoved.empty())
-	{
-		const HostGroupTable& h = s->hStripA;
-		fromMoved.assign(h.bodyIds.begin() + h.bodyOffsets[(size_t)from], h.bodyIds.begin() + h.bodyOffsets[(size_t)from + 1]);
-	}
-	fromMoved[(size_t)fromSlot] = body;
+	auto movedList = [&](int strip) -> std::vector<int>& { // (the host copy of a strip's list starts as the build's)
+		std::vector<int>& list = m.movedList[(size_t)strip];
+		if (list.empty())
+		{
+			const HostGroupTable& h = s->hStripA;
+			list.assign(h.bodyIds.begin() + h.bodyOffsets[(size_t)strip], h.bodyIds.begin() + h.bodyOffsets[(size_t)strip + 1]);
+		}
+		return list;
+	};
+	movedList(from)[(size_t)fromSlot] = body;
 	p.word(ids, (size_t)(m.stripBodyBase[(size_t)from] + fromSlot), (uint32_t)body);
 	// the receiving list: behind the table on its first adoption (with room for the next ones)
 	const int nb = m.stripBodyCount[(size_t)to];
-	std::vector<int>& list = m.movedList[(size_t)to];
+	std::vector<int>& list = movedList(to);
 	if (nb >= m.stripListCapacity[(size_t)to])
 	{
-		const HostGroupTable& h = s->hStripA;
-		if (list.empty())
-		{
-			list.assign(h.bodyIds.begin() + h.bodyOffsets[(size_t)to], h.bodyIds.begin() + h.bodyOffsets[(size_t)to + 1]);
-		}
 		const int base = m.spareIdsNext;
 		m.spareIdsNext += nb + S2_STRIP_ADOPT_SLACK;
 		m.stripBodyBase[(size_t)to] = base, m.stripListCapacity[(size_t)to] = nb + S2_STRIP_ADOPT_SLACK;
@@ -354,11 +385,6 @@ static void stripAdopt(s2amdSolver* s, Patcher& p, int body, int to)
 		m.roundMask[0].resize((size_t)(newOff + nb + S2_STRIP_ADOPT_SLACK), 0u);
 		std::copy(m.roundMask[0].begin() + off, m.roundMask[0].begin() + off + nb, m.roundMask[0].begin() + newOff);
 		m.bodyOffset[0][(size_t)to] = newOff;
-	}
-	else if (list.empty())
-	{
-		const HostGroupTable& h = s->hStripA;
-		list.assign(h.bodyIds.begin() + h.bodyOffsets[(size_t)to], h.bodyIds.begin() + h.bodyOffsets[(size_t)to + 1]);
 	}
 	list.resize((size_t)nb);
 	list.push_back((int)((uint32_t)body | S2G_OWNED));
@@ -393,8 +419,7 @@ static void stripAdopt(s2amdSolver* s, Patcher& p, int body, int to)
 	}
 	m.adopted += 1;
 	m.touched = true;
-	static const bool debug = getenv("S2AMD_DEBUG_PLACE") != nullptr;
-	if (debug)
+	if (placeTrace())
 	{
 		fprintf(stderr, "[s2amd] body %d moves from strip %d (slot %d) to strip %d (slot %d, list at %d)\n", body, from, fromSlot, to, nb, m.stripBodyBase[(size_t)to]);
 	}
@@ -459,8 +484,7 @@ static void seamExtend(s2amdSolver* s, Patcher& p, int sm, int g, int body)
 	m.roundMask[1][(size_t)(m.bodyOffset[1][(size_t)g] + slot)] = 0u;
 	m.seamBodiesAdded += 1;
 	m.touched = true;
-	static const bool debug = getenv("S2AMD_DEBUG_PLACE") != nullptr;
-	if (debug)
+	if (placeTrace())
 	{
 		fprintf(stderr, "[s2amd] seam %d (group %d) now carries body %d of strip %d: local %d, export %d on side %d (own slot %d), import of strip %d on side %d at LDS %d (its own bodies %d, imports %d + %d)\n", sm, g,
 				body, sx, slot, index, sideX, m.ownerSlot[(size_t)body], so, sideO, ldsSlot, nbO, dO.importCount[0], dO.importCount[1]);
@@ -496,8 +520,7 @@ bool stripPlace(s2amdSolver* s, Patcher& p, const ContactChange& ch)
 	const bool wa = writable(s, ch.a), wb = writable(s, ch.b);
 	const uint32_t used = (wa ? m.roundMask[table][(size_t)(off + la)] : 0u) | (wb ? m.roundMask[table][(size_t)(off + lb)] : 0u);
 	auto take = [&](IncrementalStrips::Round& round, int r) {
-		const int k = round.freePositions.back();
-		round.freePositions.pop_back();
+		const int k = round.freePositions.take();
 		if (wa)
 		{
 			m.roundMask[table][(size_t)(off + la)] |= 1u << r;
@@ -506,13 +529,10 @@ bool stripPlace(s2amdSolver* s, Patcher& p, const ContactChange& ch)
 		{
 			m.roundMask[table][(size_t)(off + lb)] |= 1u << r;
 		}
-		s->contacts.order[(size_t)k] = ch.slot;
-		s->contacts.local[(size_t)k] = make_int2(la, lb);
+		const int2 local = make_int2(la, lb);
+		p.writeEntry(k, ch.slot, &local);
 		m.positionOfSlot[(size_t)ch.slot] = k;
 		s->inc.positionOfSlot[(size_t)ch.slot] = -2;
-		p.word(s->dContactIndex.p, (size_t)k, (uint32_t)ch.slot);
-		p.word(s->dContactLocal.p, 2 * (size_t)k, (uint32_t)la);
-		p.word(s->dContactLocal.p, 2 * (size_t)k + 1, (uint32_t)lb);
 		m.touched = true;
 		m.placed += 1;
 		s->placedTotal += 1;
@@ -603,8 +623,7 @@ bool stripPlace(s2amdSolver* s, Patcher& p, const ContactChange& ch)
 		take(round, r);
 		return true;
 	}
-	static const bool debug = getenv("S2AMD_DEBUG_PLACE") != nullptr;
-	if (debug)
+	if (placeTrace())
 	{
 		fprintf(stderr, "[s2amd] no free round for (%d, %d) in table %d group %d: rounds %d, used mask %x\n", ch.a, ch.b, table, group, n, used);
 	}
@@ -662,15 +681,11 @@ bool overflowPlace(s2amdSolver* s, Patcher& p, const ContactChange& ch)
 		}
 		m.overflowBodyIds = std::move(ids);
 	}
-	const int k = m.overflowFree.back();
-	m.overflowFree.pop_back();
-	s->contacts.order[(size_t)k] = ch.slot;
-	s->contacts.local[(size_t)k] = make_int2(entry[0], entry[1]);
+	const int k = m.overflowFree.take();
+	const int2 local = make_int2(entry[0], entry[1]);
+	p.writeEntry(k, ch.slot, &local);
 	m.positionOfSlot[(size_t)ch.slot] = k;
 	s->inc.positionOfSlot[(size_t)ch.slot] = -2;
-	p.word(s->dContactIndex.p, (size_t)k, (uint32_t)ch.slot);
-	p.word(s->dContactLocal.p, 2 * (size_t)k, (uint32_t)entry[0]);
-	p.word(s->dContactLocal.p, 2 * (size_t)k + 1, (uint32_t)entry[1]);
 	m.overflowUsed += 1;
 	m.overflowPlaced += 1;
 	s->placedTotal += 1;
@@ -690,63 +705,54 @@ bool stripRemove(s2amdSolver* s, Patcher& p, int slot)
 	const int k = m.positionOfSlot[(size_t)slot];
 	if (k >= m.overflowBegin && k < m.overflowEnd)
 	{
-		// an overflow position (no round, no local slots): free again; the launch sequence loses its sweeps
-		s->contacts.order[(size_t)k] = -1;
-		p.word(s->dContactIndex.p, (size_t)k, (uint32_t)-1);
+		// an overflow position (no round): free again; the launch sequence loses its sweeps.  (Its two words of dContactLocal stay: nothing
+		// reads them for an empty record, and the next contact here writes them.)
+		p.clearEntry(k, false);
+		// entries of the overflow workgroup's body list that no other overflow contact refers to become free
+		const int2 mine = s->contacts.local[(size_t)k];
+		bool used[2] = {false, false};
+		for (int o = m.overflowBegin; o < m.overflowEnd; ++o)
 		{
-			// entries of the overflow workgroup's body list that no other overflow contact refers to become free
-			const int2 mine = s->contacts.local[(size_t)k];
-			bool used[2] = {false, false};
-			for (int o = m.overflowBegin; o < m.overflowEnd; ++o)
+			if (o != k && s->contacts.order[(size_t)o] >= 0)
 			{
-				if (o != k && s->contacts.order[(size_t)o] >= 0)
-				{
-					const int2 l = s->contacts.local[(size_t)o];
-					used[0] = used[0] || l.x == mine.x || l.y == mine.x;
-					used[1] = used[1] || l.x == mine.y || l.y == mine.y;
-				}
+				const int2 l = s->contacts.local[(size_t)o];
+				used[0] = used[0] || l.x == mine.x || l.y == mine.x;
+				used[1] = used[1] || l.x == mine.y || l.y == mine.y;
 			}
-			const int e[2] = {mine.x, mine.y};
-			for (int side = 0; side < 2; ++side)
-			{
-				if (!used[side] && e[side] >= 0 && e[side] < (int)m.overflowBodyIds.size() && m.overflowBodyIds[(size_t)e[side]] >= 0)
-				{
-					m.overflowBodyIds[(size_t)e[side]] = -1;
-					p.word(s->dOverflowBodies.p, (size_t)e[side], (uint32_t)-1);
-				}
-			}
-			s->contacts.local[(size_t)k] = make_int2(0, 0);
 		}
-		m.overflowFree.insert(std::upper_bound(m.overflowFree.begin(), m.overflowFree.end(), k, std::greater<int>()), k); // stays descending
+		const int e[2] = {mine.x, mine.y};
+		for (int side = 0; side < 2; ++side)
+		{
+			if (!used[side] && e[side] >= 0 && e[side] < (int)m.overflowBodyIds.size() && m.overflowBodyIds[(size_t)e[side]] >= 0)
+			{
+				m.overflowBodyIds[(size_t)e[side]] = -1;
+				p.word(s->dOverflowBodies.p, (size_t)e[side], (uint32_t)-1);
+			}
+		}
+		s->contacts.local[(size_t)k] = make_int2(0, 0);
+		m.overflowFree.give(k);
 		m.overflowUsed -= 1;
-		m.positionOfSlot[(size_t)slot] = -1;
-		s->inc.positionOfSlot[(size_t)slot] = -1;
-		s->slackPositions += 1;
 		s->layoutGeneration += 1;
-		return true;
 	}
-	IncrementalStrips::Round& round = m.rounds[(size_t)m.roundOfPosition[(size_t)(k - m.base)]];
-	const int off = m.bodyOffset[round.table][(size_t)round.group];
-	const int2 l = s->contacts.local[(size_t)k];
-	const int oa = s->hContactA[(size_t)slot], ob = s->hContactB[(size_t)slot]; // the endpoints the structure knows
-	if (oa >= 0 && oa < (int)s->hBodyFlags.size() && writable(s, oa))
+	else
 	{
-		m.roundMask[round.table][(size_t)(off + l.x)] &= ~(1u << round.round);
+		IncrementalStrips::Round& round = m.rounds[(size_t)m.roundOfPosition[(size_t)(k - m.base)]];
+		const int off = m.bodyOffset[round.table][(size_t)round.group];
+		const int ends[2] = {s->hContactA[(size_t)slot], s->hContactB[(size_t)slot]}; // the endpoints the structure knows
+		const int local[2] = {s->contacts.local[(size_t)k].x, s->contacts.local[(size_t)k].y};
+		for (int side = 0; side < 2; ++side)
+		{
+			if (ends[side] >= 0 && ends[side] < (int)s->hBodyFlags.size() && writable(s, ends[side]))
+			{
+				m.roundMask[round.table][(size_t)(off + local[side])] &= ~(1u << round.round);
+			}
+		}
+		p.clearEntry(k, true);
+		round.freePositions.give(k);
+		m.touched = true;
 	}
-	if (ob >= 0 && ob < (int)s->hBodyFlags.size() && writable(s, ob))
-	{
-		m.roundMask[round.table][(size_t)(off + l.y)] &= ~(1u << round.round);
-	}
-	s->contacts.order[(size_t)k] = -1;
-	s->contacts.local[(size_t)k] = make_int2(0, 0);
-	p.word(s->dContactIndex.p, (size_t)k, (uint32_t)-1);
-	p.word(s->dContactLocal.p, 2 * (size_t)k, 0u);
-	p.word(s->dContactLocal.p, 2 * (size_t)k + 1, 0u);
-	std::vector<int>& fp = round.freePositions;
-	fp.insert(std::upper_bound(fp.begin(), fp.end(), k, std::greater<int>()), k); // stays descending
 	m.positionOfSlot[(size_t)slot] = -1;
 	s->inc.positionOfSlot[(size_t)slot] = -1;
-	m.touched = true;
 	s->slackPositions += 1;
 	return true;
 }
@@ -768,34 +774,12 @@ static bool removeEntry(s2amdSolver* s, Patcher& p, int slot)
 		return kOld == -1; // -1: no entry (nothing to do); -2: it lives in an LDS group or a strip
 	}
 	const int bi = inc.colorOfPosition[(size_t)kOld];
-	if (bi < 0)
+	// (in the sequential tail: a free position again when the tail is laid out with slack -- IncrementalGlobal::tailFree)
+	if (bi < 0 && (kOld < inc.tailBegin || kOld >= inc.tailEnd || inc.tailBodyCapacity == 0))
 	{
-		// in the sequential tail: a free position again when the tail is laid out with slack (IncrementalGlobal::tailFree)
-		if (kOld < inc.tailBegin || kOld >= inc.tailEnd || inc.tailBodyCapacity == 0)
-		{
-			return false;
-		}
-		const int oa = s->hContactA[(size_t)slot], ob = s->hContactB[(size_t)slot];
-		for (int side = 0; side < 2; ++side)
-		{
-			const int body = side == 0 ? oa : ob;
-			if (body >= 0 && body < (int)s->hBodyFlags.size() && writable(s, body))
-			{
-				adjRemove(p, body, (kOld << 1) | side);
-			}
-		}
-		s->contacts.order[(size_t)kOld] = -1;
-		s->contacts.local[(size_t)kOld] = make_int2(0, 0);
-		p.word(s->dContactIndex.p, (size_t)kOld, (uint32_t)-1);
-		p.word(s->dContactLocal.p, 2 * (size_t)kOld, 0u);
-		p.word(s->dContactLocal.p, 2 * (size_t)kOld + 1, 0u);
-		inc.tailFree.insert(std::upper_bound(inc.tailFree.begin(), inc.tailFree.end(), kOld, std::greater<int>()), kOld); // stays descending
-		inc.positionOfSlot[(size_t)slot] = -1;
-		inc.removed += 1;
-		s->slackPositions += 1;
-		return true;
+		return false;
 	}
-	const int cid = inc.colorIdOfBatch[(size_t)bi];
+	const int cid = bi < 0 ? 64 * W : inc.colorIdOfBatch[(size_t)bi];
 	const int oa = s->hContactA[(size_t)slot], ob = s->hContactB[(size_t)slot]; // the endpoints the structure knows
 	for (int side = 0; side < 2; ++side)
 	{
@@ -809,10 +793,8 @@ static bool removeEntry(s2amdSolver* s, Patcher& p, int slot)
 			adjRemove(p, body, (kOld << 1) | side);
 		}
 	}
-	s->contacts.order[(size_t)kOld] = -1;
-	p.word(s->dContactIndex.p, (size_t)kOld, (uint32_t)-1);
-	std::vector<int>& fp = inc.freePositions[(size_t)bi];
-	fp.insert(std::upper_bound(fp.begin(), fp.end(), kOld, std::greater<int>()), kOld); // stays descending
+	p.clearEntry(kOld, bi < 0); // (a colour batch's positions have no local slots)
+	(bi < 0 ? inc.tailFree : inc.freePositions[(size_t)bi]).give(kOld);
 	inc.positionOfSlot[(size_t)slot] = -1;
 	inc.removed += 1;
 	s->slackPositions += 1;
@@ -853,8 +835,26 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 		inc.fallbacks += 1;
 		return false;
 	};
+	// the slack itself is used up -- free positions (a world that creates contacts by the thousand per step), room in the incidence lists --:
+	// the rebuild lays out more
+	auto slackUsedUp = [&](const char* why) {
+		s->slackShift = std::min(s->slackShift + 1, 3);
+		s->slackBumped = true;
+		return giveUp(why);
+	};
 	Patcher p{s, inc};
-	SweepSet& cs = s->contacts;
+	// position k of the global part is the contact's: its entries in the two incidence lists (false: no room), the counters
+	auto listed = [&](const ContactChange& ch, int k, bool wa, bool wb) {
+		inc.positionOfSlot[(size_t)ch.slot] = k;
+		if ((wa && !adjInsert(p, ch.a, (k << 1) | 0)) || (wb && !adjInsert(p, ch.b, (k << 1) | 1)))
+		{
+			return false;
+		}
+		inc.inserted += 1;
+		s->placedTotal += 1;
+		s->slackPositions -= 1;
+		return true;
+	};
 	const int W = 4;
 	inc.placedInGlobalPart = false;
 	for (const ContactChange& ch : changes)
@@ -883,19 +883,13 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 		if ((s->hBodyFlagsFinal[(size_t)ch.a] & S2F_IN_GROUP) != 0 || (s->hBodyFlagsFinal[(size_t)ch.b] & S2F_IN_GROUP) != 0)
 		{
 			// a strip owns a body: a free position of one of its rounds (IncrementalStrips); an LDS group's tables are not placeable into
-			if (stripPlace(s, p, ch))
+			if (stripPlace(s, p, ch) || overflowPlace(s, p, ch))
 			{
 				inc.inserted += 1;
 				unwatchSlot(s, ch.slot); // structural from here on: its manifold may gain and lose points at no cost
 				continue;
 			}
-			if (overflowPlace(s, p, ch))
-			{
-				inc.inserted += 1;
-				unwatchSlot(s, ch.slot);
-				continue;
-			}
-			s->dirtyByGroups = s->dirtyByGroups || ownedByLdsGroup(s, ch.a) || ownedByLdsGroup(s, ch.b);
+			blameGroupsFor(s, ch.a, ch.b);
 			return giveUp("body owned by a group or strip");
 		}
 		inc.placedInGlobalPart = true;
@@ -955,24 +949,14 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 					inc.tailBodyCount += fresh;
 					p.word(s->dContactTail.view.bodyOffsets, 1, (uint32_t)inc.tailBodyCount);
 				}
-				const int k = inc.tailFree.back();
-				inc.tailFree.pop_back();
-				cs.order[(size_t)k] = ch.slot;
-				cs.local[(size_t)k] = make_int2(local[0], local[1]);
-				inc.positionOfSlot[(size_t)ch.slot] = k;
-				p.word(s->dContactIndex.p, (size_t)k, (uint32_t)ch.slot);
-				p.word(s->dContactLocal.p, 2 * (size_t)k, (uint32_t)local[0]);
-				p.word(s->dContactLocal.p, 2 * (size_t)k + 1, (uint32_t)local[1]);
-				if ((wa && !adjInsert(p, ch.a, (k << 1) | 0)) || (wb && !adjInsert(p, ch.b, (k << 1) | 1)))
+				const int k = inc.tailFree.take();
+				const int2 slots = make_int2(local[0], local[1]);
+				p.writeEntry(k, ch.slot, &slots);
+				if (!listed(ch, k, wa, wb))
 				{
-					s->slackShift = std::min(s->slackShift + 1, 3);
-					s->slackBumped = true;
-					return giveUp(inc.adjFailure == 2 ? "list of heavy bodies full (tail)" : "incidence list full");
+					return slackUsedUp(inc.adjFailure == 2 ? "list of heavy bodies full (tail)" : "incidence list full");
 				}
-				inc.inserted += 1;
 				inc.tailPlaced += 1;
-				s->placedTotal += 1;
-				s->slackPositions -= 1;
 				unwatchSlot(s, ch.slot);
 				continue;
 			}
@@ -986,10 +970,7 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 			}
 			if (!anyFree || inc.ignoreColours)
 			{
-				// the slack itself is used up (a world that creates contacts by the thousand per step): the rebuild lays out more
-				s->slackShift = std::min(s->slackShift + 1, 3);
-				s->slackBumped = true;
-				return giveUp("no free position");
+				return slackUsedUp("no free position");
 			}
 			// every colour batch is taken on these bodies: the rebuild adds empty ones for the next such contact.  (Twice as many
 			// every time -- up to 16 -- was measured on the Tumbler filled from scratch, r4: fewer rebuilds, 57 instead of 67 of 120
@@ -1003,8 +984,7 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 		{
 			s->layoutGeneration += 1; // the batch was empty: its launches were left out of the captured step graph (Executor::emptyBatch)
 		}
-		const int k = inc.freePositions[(size_t)chosen].back();
-		inc.freePositions[(size_t)chosen].pop_back();
+		const int k = inc.freePositions[(size_t)chosen].take();
 		if (!inc.ignoreColours)
 		{
 			const int cid = inc.colorIdOfBatch[(size_t)chosen];
@@ -1017,18 +997,11 @@ bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes)
 				inc.colorBits[(size_t)ch.b * W + (size_t)(cid / 64)] |= 1ull << (cid % 64);
 			}
 		}
-		cs.order[(size_t)k] = ch.slot;
-		inc.positionOfSlot[(size_t)ch.slot] = k;
-		p.word(s->dContactIndex.p, (size_t)k, (uint32_t)ch.slot);
-		if ((wa && !adjInsert(p, ch.a, (k << 1) | 0)) || (wb && !adjInsert(p, ch.b, (k << 1) | 1)))
+		p.writeEntry(k, ch.slot);
+		if (!listed(ch, k, wa, wb))
 		{
-			s->slackShift = std::min(s->slackShift + 1, 3);
-			s->slackBumped = true;
-			return giveUp(inc.adjFailure == 2 ? "list of heavy bodies full" : "incidence lists full");
+			return slackUsedUp(inc.adjFailure == 2 ? "list of heavy bodies full" : "incidence lists full");
 		}
-		inc.inserted += 1;
-		s->placedTotal += 1;
-		s->slackPositions -= 1;
 	}
 	return true;
 }
@@ -1105,12 +1078,32 @@ int incrementalFlush(s2amdSolver* s)
 	return S2AMD_OK;
 }
 
-// ---- deferred contacts (solver_internal.h: optDefer) ----
-bool canDeferCreated(const s2amdSolver* s, int slot, int a, int b)
+// ---- the front: what becomes of a created, destroyed or flipped contact ----
+namespace
+{
+
+// two distinct bodies of a structure that stands
+bool twoBodies(const s2amdSolver* s, int a, int b)
 {
 	const int nb = (int)s->hBodyFlagsFinal.size();
-	if (s->optDefer == 0 || s->structureDirty || slot < 0 || slot >= (int)s->inc.positionOfSlot.size() || a < 0 || b < 0 || a >= nb || b >= nb || a == b ||
-		(int)s->hContactWatched.size() != s->contactCapacity)
+	return !s->structureDirty && a >= 0 && b >= 0 && a < nb && b < nb && a != b;
+}
+
+// ... one of them a hub as that structure knows them
+bool hubOfStructure(const s2amdSolver* s, int a, int b)
+{
+	return s->hBodyHub.size() == s->hBodyFlagsFinal.size() && (s->hBodyHub[(size_t)a] || s->hBodyHub[(size_t)b]);
+}
+
+bool inGroups(const s2amdSolver* s, int a, int b)
+{
+	return ((s->hBodyFlagsFinal[(size_t)a] | s->hBodyFlagsFinal[(size_t)b]) & S2F_IN_GROUP) != 0;
+}
+
+// a created contact that can be watched instead of placed (solver_internal.h: optDefer)
+bool canDeferCreated(const s2amdSolver* s, int slot, int a, int b)
+{
+	if (s->optDefer == 0 || !twoBodies(s, a, b) || slot < 0 || slot >= (int)s->inc.positionOfSlot.size() || (int)s->hContactWatched.size() != s->contactCapacity)
 	{
 		return false;
 	}
@@ -1118,25 +1111,19 @@ bool canDeferCreated(const s2amdSolver* s, int slot, int a, int b)
 	{
 		return false; // the slot still has an entry (a destroyed contact's, lingering): that one has to go first
 	}
-	const bool owned = ((s->hBodyFlagsFinal[(size_t)a] | s->hBodyFlagsFinal[(size_t)b]) & S2F_IN_GROUP) != 0;
-	const bool hub = (int)s->hBodyHub.size() == nb && (s->hBodyHub[(size_t)a] || s->hBodyHub[(size_t)b]);
-	return owned || hub;
+	return inGroups(s, a, b) || hubOfStructure(s, a, b);
 }
 
-// a watched manifold between these bodies got its first points: can it take a place in the strips (instead of a rebuild)?
+// an LDS group or a resident island (not a strip) holds the body: nothing can be placed on it
 bool ownedByLdsGroup(const s2amdSolver* s, int body)
 {
 	return body >= 0 && body < (int)s->hBodyLdsOwned.size() && s->hBodyLdsOwned[(size_t)body] != 0;
 }
 
+// a watched manifold between these bodies got its first points: can it take a place in the strips (instead of a rebuild)?
 bool stripCanPlace(const s2amdSolver* s, int a, int b)
 {
-	const int nb = (int)s->hBodyFlagsFinal.size();
-	if (!s->stripInc.valid || s->structureDirty || a < 0 || b < 0 || a >= nb || b >= nb || a == b)
-	{
-		return false;
-	}
-	if ((int)s->hBodyHub.size() == nb && (s->hBodyHub[(size_t)a] || s->hBodyHub[(size_t)b]))
+	if (!s->stripInc.valid || !twoBodies(s, a, b) || hubOfStructure(s, a, b))
 	{
 		return false;
 	}
@@ -1144,11 +1131,12 @@ bool stripCanPlace(const s2amdSolver* s, int a, int b)
 	return stripHome(s, a, b, table, group, la, lb, &mover);
 }
 
+// ... or, failing that, a free position of the overflow region behind the strips (IncrementalStrips::overflowFree): the steps run sliced
+// until a worker thread's structure that holds the contact is adopted
 bool overflowCanPlace(const s2amdSolver* s, int a, int b)
 {
 	const IncrementalStrips& m = s->stripInc;
-	const int nb = (int)s->hBodyFlagsFinal.size();
-	if (!m.valid || m.overflowFree.empty() || s->optOverflow == 0 || s->optIncremental == 0 || s->structureDirty || a < 0 || b < 0 || a >= nb || b >= nb || a == b)
+	if (!m.valid || m.overflowFree.empty() || s->optOverflow == 0 || s->optIncremental == 0 || !twoBodies(s, a, b))
 	{
 		return false;
 	}
@@ -1156,42 +1144,96 @@ bool overflowCanPlace(const s2amdSolver* s, int a, int b)
 	// from a worker thread while the steps go on: the world chain
 	// (a worker's copy takes overflow contacts too -- the changes replayed on it at its adoption: the structure that replaces the live one
 	// may itself run sliced until the next one is adopted)
-	if (!(asyncBuildsOn(s) || (s->isClone && s->optAsyncBuild != 0)) || !s->persistValid || s->persistFailed || s->optWide == 0 || s->optPersist == 0)
-	{
-		return false;
-	}
-	if ((int)s->hBodyHub.size() == nb && (s->hBodyHub[(size_t)a] || s->hBodyHub[(size_t)b]))
+	if (!(asyncBuildsOn(s) || (s->isClone && s->optAsyncBuild != 0)) || !s->persistValid || s->persistFailed || s->optWide == 0 || s->optPersist == 0 || hubOfStructure(s, a, b))
 	{
 		return false;
 	}
 	// both bodies live in the strips (owned by one, or read-only replicas of bodies nothing writes)
-	auto inStrips = [&](int body) {
-		const bool writes = (s->hBodyFlags[(size_t)body] & (s->inc.solverClass == 1 ? S2F_WRITE_POS : S2F_WRITE_VEL)) != 0;
-		return !writes || (body < (int)m.ownerStrip.size() && m.ownerStrip[(size_t)body] >= 0);
-	};
+	auto inStrips = [&](int body) { return !writable(s, body) || (body < (int)m.ownerStrip.size() && m.ownerStrip[(size_t)body] >= 0); };
 	return inStrips(a) && inStrips(b);
 }
 
+// ... or, between two bodies of the global part, a colour position or a free position of the sequential tail (IncrementalGlobal::tailFree)?
 bool tailCanPlace(const s2amdSolver* s, int a, int b)
 {
-	const int nb = (int)s->hBodyFlagsFinal.size();
 	// (r6: with or without a tail -- a pile of boxes pressed together has hundreds of bodies with more than S2_HUB_DEGREE potential
 	// contacts and no colour small enough to make a tail; their manifolds take a free colour position like any created contact, and only
 	// the one that finds none -- incrementalApply -- costs the build that every one of them used to cost: 134 of 200 wreck steps under XPBD)
-	if (!s->inc.valid || s->inc.ignoreColours || (s->optFlipColours == 0 && s->inc.tailFree.empty()) || s->optIncremental == 0 || s->structureDirty || a < 0 || b < 0 ||
-		a >= nb || b >= nb || a == b)
-	{
-		return false;
-	}
-	return ((s->hBodyFlagsFinal[(size_t)a] | s->hBodyFlagsFinal[(size_t)b]) & S2F_IN_GROUP) == 0;
+	return s->inc.valid && !s->inc.ignoreColours && (s->optFlipColours != 0 || !s->inc.tailFree.empty()) && s->optIncremental != 0 && twoBodies(s, a, b) && !inGroups(s, a, b);
 }
 
-void deferCreated(s2amdSolver* s, int slot, int a, int b)
+} // namespace
+
+bool flipPlaceable(const s2amdSolver* s, int a, int b, unsigned places)
+{
+	return (places & FLIP_ANYWHERE) != 0 || ((places & FLIP_STRIPS) != 0 && (stripCanPlace(s, a, b) || overflowCanPlace(s, a, b))) ||
+		   ((places & FLIP_GLOBAL) != 0 && tailCanPlace(s, a, b));
+}
+
+CreatedRoute routeCreated(const s2amdSolver* s, int slot, int a, int b, bool hasPoints, unsigned flipPlaces)
+{
+	if (hasPoints)
+	{
+		return flipPlaceable(s, a, b, flipPlaces) && canDeferCreated(s, slot, a, b) ? CREATED_WATCH_AND_FLIP : CREATED_PLACE;
+	}
+	return canDeferCreated(s, slot, a, b) ? CREATED_WATCH : CREATED_PLACE;
+}
+
+bool touchesHub(const s2amdSolver* s, int a, int b)
+{
+	const int n = (int)s->hBodyHub.size();
+	return (a >= 0 && a < n && s->hBodyHub[(size_t)a]) || (b >= 0 && b < n && s->hBodyHub[(size_t)b]);
+}
+
+void blameGroupsFor(s2amdSolver* s, int a, int b)
+{
+	s->dirtyByGroups = s->dirtyByGroups || ownedByLdsGroup(s, a) || ownedByLdsGroup(s, b);
+}
+
+void commitEdge(s2amdSolver* s, int slot, int a, int b)
 {
 	s->hContactA[(size_t)slot] = a;
 	s->hContactB[(size_t)slot] = b;
 	s->hContactEdge[(size_t)slot] = 1;
 	s->hContactDead[(size_t)slot] = 0;
+}
+
+bool destroyedContact(s2amdSolver* s, int slot)
+{
+	if (!s->hContactEdge[(size_t)slot])
+	{
+		return false;
+	}
+	s->hContactDead[(size_t)slot] = 1; // the entry leaves the structure where it can, else lingers as a no-op
+	unwatchSlot(s, slot);
+	const int32_t one = slot;
+	incrementalRemove(s, &one, 1);
+	return true;
+}
+
+bool placeFlipped(s2amdSolver* s, const std::vector<ContactChange>& flipped)
+{
+	const bool placed = incrementalApply(s, flipped);
+	if (placed && s->inc.placedInGlobalPart)
+	{
+		noteGraphTouched(s); // (a place in the strips leaves the strips where they are)
+	}
+	return placed;
+}
+
+bool placeCreated(s2amdSolver* s, const std::vector<ContactChange>& created, bool allowed)
+{
+	const bool placed = allowed && placeFlipped(s, created);
+	for (const ContactChange& ch : created)
+	{
+		commitEdge(s, ch.slot, ch.a, ch.b); // (after the slot's old entry was found: incrementalApply)
+	}
+	return placed;
+}
+
+void deferCreated(s2amdSolver* s, int slot, int a, int b)
+{
+	commitEdge(s, slot, a, b);
 	if (!s->hContactWatched[(size_t)slot])
 	{
 		s->hContactWatched[(size_t)slot] = 1;

@@ -261,6 +261,19 @@ struct StepPlan
 	bool usesDq0 = false;
 };
 
+// Free positions of one range of the sweep order (a colour batch, the tail's slack, a round of a strip or seam, the overflow region),
+// kept descending: the lowest is handed out first, and a build pushes a range's positions from the highest down.
+struct FreeList : std::vector<int>
+{
+	int take()
+	{
+		const int k = back();
+		pop_back();
+		return k;
+	}
+	void give(int k) { insert(std::upper_bound(begin(), end(), k, std::greater<int>()), k); }
+};
+
 // Host mirror of the GLOBAL part's tables (colour batches over HBM-resident bodies), kept between steps so that a created
 // contact can be given a place in the sweep order WITHOUT rebuilding the structure (solver_incremental.cpp):
 //   * every parallel colour batch is laid out with slack -- free positions whose contactIndex is -1 (an empty record, no
@@ -281,7 +294,7 @@ struct IncrementalGlobal
 	bool colourFreePlaced = false;		// ... and a contact was placed that way: no other solver may run on this structure
 	std::vector<int> colorIdOfBatch;	// bit index of a batch in colorBits (a spare batch gets an id above every colour of the tail)
 	std::vector<int> batchBegin, batchEnd; // position range of every parallel batch, slack included
-	std::vector<std::vector<int>> freePositions; // per batch, descending: pop_back() hands out the lowest free position
+	std::vector<FreeList> freePositions; // per batch
 	std::vector<uint64_t> colorBits;	// 4 words per body: colours in use on the body (global part)
 	std::vector<int> positionOfSlot;	// contact slot -> position k in the sweep order, -1
 	std::vector<int> colorOfPosition;	// position -> colour batch (parallel batches only), -1
@@ -300,7 +313,7 @@ struct IncrementalGlobal
 	// position of a sequential sweep is a valid one.  A body the tail does not stage yet is appended to its body list
 	// (S2_TAIL_BODY_SLACK more fit its LDS and its table).  Entries of the tail can be removed like any other.
 	int tailBegin = 0, tailEnd = 0;				// positions of the tail, slack included (0, 0: no tail)
-	std::vector<int> tailFree;					// descending: pop_back() hands out the lowest
+	FreeList tailFree;
 	std::unordered_map<int, int> tailBodySlot;	// body -> local slot in the tail's body list
 	int tailBodyCount = 0, tailBodyCapacity = 0;
 	long tailPlaced = 0;
@@ -322,7 +335,7 @@ struct IncrementalStrips
 	struct Round
 	{
 		int table, group, round; // table 0: strip interiors (hStripA), 1: seams (hStripB)
-		std::vector<int> freePositions; // descending: pop_back() hands out the lowest
+		FreeList freePositions;
 	};
 	std::vector<Round> rounds;
 	std::vector<int> roundOfPosition;	// [end - base] -> index into rounds
@@ -373,7 +386,7 @@ struct IncrementalStrips
 	// sequential sweep is a valid one: the oracle sweeps in it).  ~75 launches and ~0.5 ms per step instead of 3 and 0.15 -- for the
 	// dozen steps a worker thread needs to build a structure that holds the contact (solver_async.cpp), adopted at a step boundary.
 	int overflowBegin = 0, overflowEnd = 0; // positions of the overflow region in contacts.order (0, 0: none)
-	std::vector<int> overflowFree;			// descending: pop_back() hands out the lowest
+	FreeList overflowFree;
 	int overflowUsed = 0;
 	long overflowPlaced = 0;
 	// ... round 5, later: the overflow contacts swept INSIDE the persistent launch by one more workgroup (wide_kernel.hip:
@@ -1100,22 +1113,34 @@ struct ContactChange
 {
 	int slot, a, b; // a < 0: the slot's old entry is only removed
 };
-// Gives every change a place in the existing structure (removing the slot's previous entry first); false: one of them
-// does not fit -- the caller marks the graph changed (full rebuild; nothing has reached the device).
-bool canDeferCreated(const s2amdSolver* s, int slot, int a, int b);
-void deferCreated(s2amdSolver* s, int slot, int a, int b);
+// The front for graph changes: what becomes of a contact that was created, destroyed, or whose watched manifold gained its first points
+// ("flipped").  Its callers -- refreshShadows, s2amd_world_set_contacts, s2amd_world_step, the worker's copy in solver_async.cpp -- keep
+// the order of their steps and what only they know (where the flush goes, what is logged).
+void commitEdge(s2amdSolver* s, int slot, int a, int b); // the host shadows of a slot that holds a live contact between a and b
+bool touchesHub(const s2amdSolver* s, int a, int b);	 // (either body may lie outside the bodies the structure knows)
+bool destroyedContact(s2amdSolver* s, int slot);		 // dead, unwatched, out of the structure where it can leave; false: the slot held none
+void blameGroupsFor(s2amdSolver* s, int a, int b);		 // a contact that found no place has a body an LDS group holds (groupPatienceNow)
+void deferCreated(s2amdSolver* s, int slot, int a, int b); // watched, not structural (optDefer)
 void unwatchSlot(s2amdSolver* s, int slot);
 int uploadWatched(s2amdSolver* s);
-bool stripCanPlace(const s2amdSolver* s, int a, int b);
-bool ownedByLdsGroup(const s2amdSolver* s, int body); // an LDS group or a resident island (not a strip) holds the body: nothing can be placed on it
-// ... or, failing that, a free position of the overflow region behind the strips (IncrementalStrips::overflowFree): the steps run sliced
-// until a worker thread's structure that holds the contact is adopted
-bool overflowCanPlace(const s2amdSolver* s, int a, int b);
-// ... or, between two bodies of the global part, a colour position or a free position of the sequential tail (IncrementalGlobal::tailFree)?
-bool tailCanPlace(const s2amdSolver* s, int a, int b);
+// The places a caller admits for a flipped manifold: any free position (a structure built for s2Solve_Jacobi); a strip or seam round, else
+// an overflow position behind the strips; between two bodies of the global part a colour position or one of the sequential tail.
+// The callers admit different sets, and the differences are behaviour.
+enum FlipPlaces : unsigned { FLIP_ANYWHERE = 1u, FLIP_STRIPS = 2u, FLIP_GLOBAL = 4u };
+bool flipPlaceable(const s2amdSolver* s, int a, int b, unsigned places);
+// A created contact is placed now, or watched until its manifold has points (the caller defers it), or -- created with points where the
+// flip can be placed -- watched and flipped in the same call: the sequence the world chain goes through in two.
+enum CreatedRoute { CREATED_PLACE, CREATED_WATCH, CREATED_WATCH_AND_FLIP };
+CreatedRoute routeCreated(const s2amdSolver* s, int slot, int a, int b, bool hasPoints, unsigned flipPlaces);
+// Created contacts, in pool order: a place for each when `allowed` and all fit, their shadows either way; flipped ones: a place for each.
+// false: the caller marks the graph changed.
+bool placeCreated(s2amdSolver* s, const std::vector<ContactChange>& created, bool allowed);
+bool placeFlipped(s2amdSolver* s, const std::vector<ContactChange>& flipped);
+// Gives every change a place in the existing structure (removing the slot's previous entry first); false: one of them
+// does not fit -- the caller marks the graph changed (full rebuild; nothing has reached the device).
 bool incrementalApply(s2amdSolver* s, const std::vector<ContactChange>& changes);
-// Destroyed contacts give their place back (colour, position, list entries) where the entry is in the global part's
-// parallel batches; elsewhere (LDS group, strip, sequential tail) the entry lingers as a no-op until the next rebuild.
+// Destroyed contacts give their place back (colour, position, list entries; a round of a strip, an overflow position, a position of a
+// tail laid out with slack); an entry in an LDS group's tables lingers as a no-op until the next rebuild.
 void incrementalRemove(s2amdSolver* s, const int32_t* slots, int count);
 // enqueues the patch list built by incrementalApply on the solver's stream
 int incrementalFlush(s2amdSolver* s);

@@ -126,10 +126,10 @@ int refreshShadows(s2amdSolver* s, const s2amdBody* bodies, int nb, const s2amdC
 	const bool placeFlips = s->inc.valid && s->inc.ignoreColours && s->optIncremental != 0 && !s->structureDirty && !newWorld;
 	// ... and under the soft contact solvers' strips a flipped manifold takes a free position of a strip or seam round where it fits
 	const bool stripFlips = s->inc.valid && s->stripInc.valid && s->optIncremental != 0 && !s->structureDirty && !newWorld;
+	const unsigned flipPlaces = (placeFlips ? FLIP_ANYWHERE : 0u) | (stripFlips ? FLIP_STRIPS : 0u);
 	bool hubTouched = false;			// something happened to a contact on a hub body: decided by a rebuild
-	auto onHub = [&](int a, int b) {
-		return !s->hBodyHub.empty() && (int)s->hBodyHub.size() == nb && a >= 0 && b >= 0 && a < nb && b < nb && (s->hBodyHub[(size_t)a] || s->hBodyHub[(size_t)b]);
-	};
+	// (the hubs of a structure built for as many bodies as these arrays hold; the bodies of an edge lie inside the arrays)
+	auto onHub = [&](int a, int b) { return (int)s->hBodyHub.size() == nb && touchesHub(s, a, b); };
 	for (int i = 0; i < nc; ++i)
 	{
 		const s2amdContact& c = contacts[i];
@@ -161,32 +161,29 @@ int refreshShadows(s2amdSolver* s, const s2amdBody* bodies, int nb, const s2amdC
 			unwatchSlot(s, i);
 			continue;
 		}
-		if (edge && pc == 0 && !newWorld && (!s->hContactEdge[i] || s->hContactA[i] != c.bodyA || s->hContactB[i] != c.bodyB) &&
-			canDeferCreated(s, i, c.bodyA, c.bodyB))
-		{
-			deferred.push_back(ContactChange{i, c.bodyA, c.bodyB});
-			continue;
-		}
-		if (edge && pc > 0 && (placeFlips || (stripFlips && (stripCanPlace(s, c.bodyA, c.bodyB) || overflowCanPlace(s, c.bodyA, c.bodyB))) || (!newWorld && onHub(c.bodyA, c.bodyB) && tailCanPlace(s, c.bodyA, c.bodyB))) &&
-			(!s->hContactEdge[i] || s->hContactA[i] != c.bodyA || s->hContactB[i] != c.bodyB) && canDeferCreated(s, i, c.bodyA, c.bodyB))
-		{
-			// created AND touching at first sight (the caller ran stage 3 itself): the world chain, which sees the contact created
-			// without points and its manifold gain them in its own stage 3, watches it first and places it with the flips --
-			// same sequence here, so that both routes hand out the same positions
-			deferred.push_back(ContactChange{i, c.bodyA, c.bodyB});
-			flipped.push_back(ContactChange{i, c.bodyA, c.bodyB});
-			continue;
-		}
 		if (edge && (!s->hContactEdge[i] || s->hContactA[i] != c.bodyA || s->hContactB[i] != c.bodyB))
 		{
+			// a created contact.  One that touches at first sight (the caller ran stage 3 itself) may take the tail only on a hub: the world
+			// chain, which sees the contact created without points and its manifold gain them in its own stage 3, watches it first and
+			// places it with the flips -- same sequence here, so that both routes hand out the same positions
+			const CreatedRoute route = newWorld ? CREATED_PLACE : routeCreated(s, i, c.bodyA, c.bodyB, pc > 0, flipPlaces | (pc > 0 && onHub(c.bodyA, c.bodyB) ? FLIP_GLOBAL : 0u));
+			if (route != CREATED_PLACE)
+			{
+				deferred.push_back(ContactChange{i, c.bodyA, c.bodyB});
+				if (route == CREATED_WATCH_AND_FLIP)
+				{
+					flipped.push_back(ContactChange{i, c.bodyA, c.bodyB});
+				}
+				continue;
+			}
 			created.push_back(ContactChange{i, c.bodyA, c.bodyB}); // (shadows of this slot are written below, after the old entry was found)
-			hubTouched = hubTouched || (!s->hBodyHub.empty() && (int)s->hBodyHub.size() == nb && (s->hBodyHub[(size_t)c.bodyA] || s->hBodyHub[(size_t)c.bodyB]));
+			hubTouched = hubTouched || onHub(c.bodyA, c.bodyB);
 			continue;
 		}
 		if (edge && !s->hContactWatched.empty() && s->hContactWatched[(size_t)i] && (oldPoints > 0) != (pc > 0))
 		{
 			// a watched manifold (on a hub body, or deferred) gained or lost its points (solver_internal.h: hContactWatched)
-			if (placeFlips || (stripFlips && (stripCanPlace(s, c.bodyA, c.bodyB) || overflowCanPlace(s, c.bodyA, c.bodyB))) || (!newWorld && tailCanPlace(s, c.bodyA, c.bodyB)))
+			if (flipPlaceable(s, c.bodyA, c.bodyB, flipPlaces | (newWorld ? 0u : FLIP_GLOBAL))) // (the tail for any watched contact, on a hub or deferred)
 			{
 				if (pc > 0 && i < (int)s->inc.positionOfSlot.size() && s->inc.positionOfSlot[(size_t)i] == -1)
 				{
@@ -198,7 +195,7 @@ int refreshShadows(s2amdSolver* s, const s2amdBody* bodies, int nb, const s2amdC
 				hubTouched = true;
 				s->dirtyReason = "watched manifold flipped";
 				s->dirtyByWatched = true;
-				s->dirtyByGroups = s->dirtyByGroups || ownedByLdsGroup(s, c.bodyA) || ownedByLdsGroup(s, c.bodyB);
+				blameGroupsFor(s, c.bodyA, c.bodyB);
 			}
 		}
 		if (!edge && s->hContactEdge[i])
@@ -214,25 +211,7 @@ int refreshShadows(s2amdSolver* s, const s2amdBody* bodies, int nb, const s2amdC
 	if (!created.empty())
 	{
 		// created contacts: a place in the existing structure when that is all that happened and they fit, else a rebuild
-		const bool placed = !changed && !hubTouched && incrementalApply(s, created);
-		for (const ContactChange& ch : created)
-		{
-			s->hContactA[(size_t)ch.slot] = ch.a;
-			s->hContactB[(size_t)ch.slot] = ch.b;
-			s->hContactEdge[(size_t)ch.slot] = 1;
-			s->hContactDead[(size_t)ch.slot] = 0;
-		}
-		if (placed)
-		{
-			if (s->inc.placedInGlobalPart)
-			{
-				noteGraphTouched(s);
-			}
-		}
-		else
-		{
-			changed = true;
-		}
+		changed = !placeCreated(s, created, !changed && !hubTouched) || changed;
 	}
 	changed = changed || hubTouched;
 	if (!changed)
@@ -242,30 +221,13 @@ int refreshShadows(s2amdSolver* s, const s2amdBody* bodies, int nb, const s2amdC
 			deferCreated(s, ch.slot, ch.a, ch.b);
 		}
 		// (after this step's created contacts, before its destroyed ones: the order the world chain does it in)
-		if (!flipped.empty())
-		{
-			if (incrementalApply(s, flipped))
-			{
-				if (s->inc.placedInGlobalPart)
-				{
-					noteGraphTouched(s); // (a place in the strips leaves the strips where they are)
-				}
-			}
-			else
-			{
-				changed = true;
-			}
-		}
+		changed = !flipped.empty() && !placeFlipped(s, flipped);
 	}
 	else
 	{
 		for (const ContactChange& ch : deferred)
 		{
-			// the structure is rebuilt anyway: an ordinary potential constraint of the new one
-			s->hContactA[(size_t)ch.slot] = ch.a;
-			s->hContactB[(size_t)ch.slot] = ch.b;
-			s->hContactEdge[(size_t)ch.slot] = 1;
-			s->hContactDead[(size_t)ch.slot] = 0;
+			commitEdge(s, ch.slot, ch.a, ch.b); // the structure is rebuilt anyway: an ordinary potential constraint of the new one
 		}
 	}
 	if (!changed)

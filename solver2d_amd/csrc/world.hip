@@ -780,45 +780,37 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 			// ... and under the soft contact solvers a manifold between bodies of the strips takes a free position of a strip or
 			// seam round (solver_internal.h: IncrementalStrips); every other flip rebuilds the structure
 			bool handled = false;
-			bool byGroups = false; // (a flipped manifold on a body an LDS group holds: SolverRest::groupPatienceNow)
+			std::vector<ContactChange> flipped;
 			const bool jacobi = s->inc.valid && s->inc.ignoreColours && s->optIncremental != 0;
 			const bool strips = s->inc.valid && s->stripInc.valid && s->optIncremental != 0;
 			// ... and (r4) a manifold between bodies of the global part takes a free colour position or, a hub's, a free position of
 			// the sequential tail (solver_internal.h: IncrementalGlobal::tailFree)
-			const bool tail = s->inc.valid && !s->inc.ignoreColours && s->optIncremental != 0 && (s->optFlipColours != 0 || !s->inc.tailFree.empty()); // (r6: a free colour position will do: tailCanPlace)
-			auto inGlobalPart = [&](int a, int b) { return tailCanPlace(s, a, b); };
+			const bool tail = s->inc.valid && !s->inc.ignoreColours && s->optIncremental != 0 && (s->optFlipColours != 0 || !s->inc.tailFree.empty()); // (r6: a free colour position will do: FLIP_GLOBAL)
 			if (jacobi || strips || tail)
 			{
 				if ((rcMid = fetchPointCounts(s)) != 0)
 				{
 					return rcMid;
 				}
-				std::vector<ContactChange> flipped;
 				bool placeable = true;
 				for (int i = 0; i < nc; ++i)
 				{
 					if (s->hContactWatched[(size_t)i] && s->hContactPoints[(size_t)i] > 0 && s->hContactEdge[(size_t)i] && !s->hContactDead[(size_t)i] &&
 						s->inc.positionOfSlot[(size_t)i] == -1)
 					{
-						flipped.push_back(ContactChange{i, s->hContactA[(size_t)i], s->hContactB[(size_t)i]});
-						byGroups = byGroups || ownedByLdsGroup(s, s->hContactA[(size_t)i]) || ownedByLdsGroup(s, s->hContactB[(size_t)i]);
-						// (r5: ... or, where it fits no strip round, an overflow position behind the strips: the steps run sliced until a
-						// worker thread's structure is adopted -- solver_internal.h: IncrementalStrips)
-						placeable = placeable && (jacobi || inGlobalPart(s->hContactA[(size_t)i], s->hContactB[(size_t)i]) ||
-												  (strips && (stripCanPlace(s, s->hContactA[(size_t)i], s->hContactB[(size_t)i]) ||
-															  overflowCanPlace(s, s->hContactA[(size_t)i], s->hContactB[(size_t)i]))));
+						const int a = s->hContactA[(size_t)i], b = s->hContactB[(size_t)i];
+						flipped.push_back(ContactChange{i, a, b});
+						// (the global part is asked whatever `tail` says, and before the strips; r5: ... or, where it fits no strip round, an
+						// overflow position behind the strips: the steps run sliced until a worker thread's structure is adopted)
+						placeable = placeable && (flipPlaceable(s, a, b, (jacobi ? FLIP_ANYWHERE : 0u) | FLIP_GLOBAL) || flipPlaceable(s, a, b, strips ? FLIP_STRIPS : 0u));
 					}
 				}
-				handled = placeable && (flipped.empty() || incrementalApply(s, flipped));
+				handled = placeable && (flipped.empty() || placeFlipped(s, flipped));
 				if (handled && !flipped.empty())
 				{
 					if ((rcMid = incrementalFlush(s)) != 0)
 					{
 						return rcMid;
-					}
-					if (s->inc.placedInGlobalPart)
-					{
-						noteGraphTouched(s);
 					}
 					s->gatherIndexDirty = true;
 				}
@@ -830,7 +822,10 @@ int s2amd_world_step(s2amdSolver* s, const s2amdStepParams* params, s2amdWorldSt
 					s->dirtyReason = "watched manifold flipped";
 					s->dirtyByWatched = true;
 				}
-				s->dirtyByGroups = s->dirtyByGroups || byGroups;
+				for (const ContactChange& ch : flipped)
+				{
+					blameGroupsFor(s, ch.a, ch.b); // (a flipped manifold on a body an LDS group holds: SolverRest::groupPatienceNow)
+				}
 				static const bool debugPrep = getenv("S2AMD_DEBUG_PREP") != nullptr;
 				if (debugPrep)
 				{
@@ -1321,9 +1316,6 @@ int s2amd_world_set_contacts(s2amdSolver* s, const int32_t* slots, int32_t count
 	std::sort(byslot.begin(), byslot.end(), [&](int x, int y) { return slots[x] < slots[y]; });
 	std::vector<ContactChange> created;
 	bool hubTouched = false; // a contact on a hub body came or went: which of its contacts are structural is decided by a rebuild
-	auto onHub = [&](int a, int b) {
-		return !s->hBodyHub.empty() && ((a >= 0 && a < (int)s->hBodyHub.size() && s->hBodyHub[(size_t)a]) || (b >= 0 && b < (int)s->hBodyHub.size() && s->hBodyHub[(size_t)b]));
-	};
 	for (int i : byslot)
 	{
 		const int k = slots[i];
@@ -1338,12 +1330,8 @@ int s2amd_world_set_contacts(s2amdSolver* s, const int32_t* slots, int32_t count
 		}
 		if (!edge)
 		{
-			if (s->hContactEdge[(size_t)k])
+			if (destroyedContact(s, k)) // the caller's s2DestroyContact
 			{
-				s->hContactDead[(size_t)k] = 1; // the caller's s2DestroyContact: the entry leaves the structure where it can, else lingers as a no-op
-				unwatchSlot(s, k);
-				const int32_t one = k;
-				incrementalRemove(s, &one, 1);
 				asyncLogDestroyed(s, k);
 			}
 			continue;
@@ -1355,56 +1343,36 @@ int s2amd_world_set_contacts(s2amdSolver* s, const int32_t* slots, int32_t count
 				asyncDrop(s); // (created with points already: not what a build in flight replays)
 			}
 			asyncLogCreated(s, k, c.bodyA, c.bodyB);
-			if (pc == 0 && canDeferCreated(s, k, c.bodyA, c.bodyB))
+			if (pc == 0 && routeCreated(s, k, c.bodyA, c.bodyB, false, 0u) == CREATED_WATCH)
 			{
 				deferCreated(s, k, c.bodyA, c.bodyB); // watched until stage 3 finds its first manifold points
 				continue;
 			}
 			created.push_back(ContactChange{k, c.bodyA, c.bodyB});
-			hubTouched = hubTouched || onHub(c.bodyA, c.bodyB);
+			hubTouched = hubTouched || touchesHub(s, c.bodyA, c.bodyB);
 			continue;
 		}
 		s->hContactDead[(size_t)k] = 0; // the same pair again in its old slot
 	}
-	if (!created.empty())
+	if (!created.empty() && !placeCreated(s, created, !hubTouched))
 	{
-		const bool placed = !hubTouched && incrementalApply(s, created);
-		for (const ContactChange& ch : created)
-		{
-			s->hContactA[(size_t)ch.slot] = ch.a;
-			s->hContactB[(size_t)ch.slot] = ch.b;
-			s->hContactEdge[(size_t)ch.slot] = 1;
-			s->hContactDead[(size_t)ch.slot] = 0;
-		}
-		if (placed)
-		{
-			int rcFlush = incrementalFlush(s);
-			if (rcFlush)
-			{
-				return rcFlush;
-			}
-			if (s->inc.placedInGlobalPart)
-			{
-				noteGraphTouched(s);
-			}
-		}
-		else
-		{
-			noteGraphChanged(s);
-		}
+		noteGraphChanged(s);
 	}
 	else
 	{
-		int rcFlush = incrementalFlush(s); // (removals)
+		int rcFlush = incrementalFlush(s); // (placements and removals)
 		if (rcFlush)
 		{
 			return rcFlush;
 		}
-		if (s->persistValid)
+		if (created.empty())
 		{
-			s->persist.allTwoPoints = stripsAllTwoPoints(s) ? 1 : 0;
+			if (s->persistValid)
+			{
+				s->persist.allTwoPoints = stripsAllTwoPoints(s) ? 1 : 0;
+			}
+			s->residentAllTwoPoints = residentAllTwoPoints(s) ? 1 : 0;
 		}
-		s->residentAllTwoPoints = residentAllTwoPoints(s) ? 1 : 0;
 	}
 	s->gatherIndexDirty = true;
 	return S2AMD_OK;
